@@ -10,6 +10,7 @@ SURVEY §8(f)).  Default workload = BASELINE configs[1] (Replica room0 full conf
 the other BASELINE configurations.  For the staged configurations the stage of step i follows the reference schedule of a
 60-iteration frame batch (25 middle / 12 fine / 23 color, src/Mapper.py:403-410), interleaved so that any window carries that
 mix.  The K steps are timed ``--windows`` (default 3) times; the MEDIAN window is reported.  Prints ONE JSON line.
+``--dump-outputs DIR`` also writes the loss and the gradients of the last timed step as DIR/<name>.npy (`dump_outputs`).
 """
 import argparse
 import ctypes
@@ -19,10 +20,12 @@ import os
 import sys
 import time
 import types
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -157,6 +160,32 @@ def build_scene(cfg_id, dev, seed=0):
         frames.append((c2w, depth, color))
     return {"cfg": cfg, "C": C, "bound": bound, "renderer": renderer, "dec": dec, "grids": grids, "frames": frames,
             "intr": (H, W, fx, fy, cx, cy)}
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: name -> array written as out_dir/<name>.npy in float32 (float64 stays float64).  Above DUMP_BYTES in
+    all, every array over 1 MB keeps the same fraction of its elements: a sorted sample of flat positions drawn from a
+    generator seeded by the name, so every run keeps the same positions.  -> summary record for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    budget = DUMP_BYTES - 4096 * len(arrays)                   # (room for the .npy headers)
+    small = sum(a.nbytes for a in arrays.values() if a.nbytes <= 1 << 20)
+    big = sum(a.nbytes for a in arrays.values()) - small
+    frac = min(1.0, (budget - small) / big) if big else 1.0
+    sampled, written = {}, 0
+    for name, a in sorted(arrays.items()):
+        keep = a.size if a.nbytes <= 1 << 20 else int(a.size * frac)
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, keep, replace=False))
+            sampled[name] = f"{keep} of {a.size} elements"
+            a = a.reshape(-1)[idx]
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        written += os.path.getsize(path)
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": written, "sampled": sampled}
 
 
 def cpu_baseline(sc, n_rays, stages, weights, track_crop=None):
@@ -404,8 +433,12 @@ def measure(args, cfg_id, scaling, world, rank, dev, sharded, role="headline", r
     if tracking:
         cam = frames[0][0][:3].clone().requires_grad_(True)       # the pose under optimisation (gradient w.r.t. the 3x4 matrix)
 
+    dump = bool(args.dump_outputs) and headline
+    last_out = {}                           # --dump-outputs: what the latest step() handed its caller (graph memory after a capture)
+
     def step(it, timed, finish=True):
         stage = stage_of(it)
+        last_out.clear()
         for g in grids.values():
             g.grad = None
         for p in params:
@@ -448,6 +481,12 @@ def measure(args, cfg_id, scaling, world, rank, dev, sharded, role="headline", r
             nsa.backward(loss)
         renderer.profile_events = None
         renderer.profile_fwd_events = None
+        if dump:                                                  # the loss and every gradient the step produced
+            last_out["loss"] = loss
+            if tracking:
+                last_out["pose.grad"] = cam.grad
+            last_out.update({f"{k}.grad": g.grad for k, g in grids.items() if g.grad is not None})
+            last_out.update({f"{n}.grad": p.grad for n, p in dec.named_parameters() if p.grad is not None})
         return stage
 
     # Warm-up: eager iterations.  First untimed ones (code load, allocator, LDS attribute), then 5 per stage with HIP
@@ -479,6 +518,8 @@ def measure(args, cfg_id, scaling, world, rank, dev, sharded, role="headline", r
     use_graph = not args.eager and (not sharded or dist_mode == "captured")
     segments = {}
     graphs = {}
+    graph_out = {}                          # stage -> last_out of its captured graph (per-stage graphs / segments)
+    window_out = {}                         # last_out of the window graph's last captured step
     window_graph = None
     if use_graph:
         # The iteration is a handful of launches; one hipGraph per stage (identical kernel sequence, fresh torch.randint
@@ -502,6 +543,7 @@ def measure(args, cfg_id, scaling, world, rank, dev, sharded, role="headline", r
                 with torch.cuda.graph(gph, capture_error_mode=cap_mode):
                     st_name = step(st_i, False)
                 graphs[st_name] = gph
+                graph_out[st_name] = dict(last_out)
             torch.cuda.synchronize()
             for gph in graphs.values():                 # first replays pay the one-time upload of the executable graph:
                 for _ in range(3):                      # part of the warm-up, not of the timed region
@@ -520,6 +562,7 @@ def measure(args, cfg_id, scaling, world, rank, dev, sharded, role="headline", r
                     with torch.cuda.graph(wg, capture_error_mode=cap_mode):
                         for i in range(args.steps):
                             stages_in_window.append(step(i, False))
+                    window_out = dict(last_out)
                     torch.cuda.synchronize()
                     for _ in range(2):
                         wg.replay()
@@ -552,6 +595,7 @@ def measure(args, cfg_id, scaling, world, rank, dev, sharded, role="headline", r
                 seg = nsa.graphs.SegmentedStep(first, shard.reduce_deferred, shard.scatter_deferred, warmup=2, device=dev,
                                                generators=(shard.generator(dev),))
                 segments[stage_of(st_i)] = seg
+                graph_out[stage_of(st_i)] = dict(last_out)           # (the exchange writes into these gradients in place)
             torch.cuda.synchronize()
             for seg in segments.values():
                 for _ in range(3):
@@ -597,6 +641,17 @@ def measure(args, cfg_id, scaling, world, rank, dev, sharded, role="headline", r
             dt = float(tt.item())
         windows.append(dt)
     dt = sorted(windows)[len(windows) // 2]
+    dumped = None
+    if dump and rank == 0:                  # copied out before the untimed work below runs the path again
+        if use_graph and window_graph is not None:
+            out = window_out
+        elif use_graph or segments:
+            out = graph_out[stages[-1]]
+        else:
+            out = last_out
+        torch.cuda.synchronize()
+        dumped = dump_outputs(args.dump_outputs, {k: v.detach().contiguous().cpu().numpy() for k, v in out.items()})
+        dumped["last_step_stage"] = stages[-1]
     rays_iter = rays_rank * world
     # What share of the sampled rays passes the bounding-box pre-filter, i.e. is RENDERED (the others are removed from the batch
     # like the reference's compaction does, Mapper.py:471-481): the mean over 16 untimed draws of this rank (the keep bytes of
@@ -764,6 +819,8 @@ def measure(args, cfg_id, scaling, world, rank, dev, sharded, role="headline", r
                                          "iteration, the collective eager between them | eager: every launch from the host"}
         if shard_check is not None:
             res["shard_check"] = shard_check
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         res["kernel_ms"] = {f"render_bwd<{s}>": round(v[0], 4) for s, v in ksum.items()}
         if headline and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(sc, rays_rank, stages_cfg, mix, crop if tracking else None)
@@ -822,7 +879,13 @@ def main():
     ap.add_argument("--no-strong-record", dest="strong_record", action="store_false")
     ap.add_argument("--dense-exchange", action="store_true",
                     help="multi-GPU: all-reduce the whole feature-grid gradients instead of the frustum-selected voxel rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step of the timed configuration returned (the loss and "
+                         "every gradient it produced) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed sample of each "
+                         "large array beyond that); the same arguments give the same inputs in every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))                          # `python bench.py --gpus N`: launch the N ranks ourselves
     if "WORLD_SIZE" in os.environ and args.gpus > 1 and int(os.environ["WORLD_SIZE"]) != args.gpus:

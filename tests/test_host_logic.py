@@ -162,6 +162,34 @@ def test_bench_gpus_n_fails_loudly_without_n_devices():
     assert r.returncode != 0 and r.stdout.strip() == "" and "--gpus 2" in r.stderr and "device" in r.stderr, (r.returncode, r.stdout, r.stderr[-500:])
 
 
+def test_bench_dump_outputs_stays_under_64_mb_with_a_fixed_sample(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 / float64 .npy files, at most 64 MB in all; arrays over 1 MB are cut to a
+    sample whose positions are the same in every run, smaller ones are written whole."""
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"loss": np.float32(2.5), "grid_fine.grad": rng.standard_normal((1, 32, 70, 70, 70), dtype=np.float32),
+              "grid_color.grad": rng.standard_normal((1, 32, 40, 40, 40)).astype(np.float32),
+              "wide.grad": rng.standard_normal(3_000_000), "small.grad": rng.standard_normal((32, 96)).astype(np.float16)}
+    runs = []
+    for d in ("a", "b"):
+        rec = bench.dump_outputs(str(tmp_path / d), arrays)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == sorted(k + ".npy" for k in arrays)
+        assert rec["bytes"] == sum(os.path.getsize(tmp_path / d / f) for f in files) <= bench.DUMP_BYTES
+        assert sorted(rec["sampled"]) == ["grid_color.grad", "grid_fine.grad", "wide.grad"]
+        runs.append({f[:-4]: np.load(tmp_path / d / f) for f in files})
+    a, b = runs
+    assert a["loss"].shape == () and a["loss"] == np.float32(2.5)
+    assert a["small.grad"].dtype == np.float32 and np.array_equal(a["small.grad"], arrays["small.grad"].astype(np.float32))
+    assert a["wide.grad"].dtype == np.float64
+    for k in arrays:
+        assert np.array_equal(a[k], b[k]), k
+    v = a["grid_fine.grad"]
+    assert v.ndim == 1 and 0.3 * arrays["grid_fine.grad"].size < v.size < arrays["grid_fine.grad"].size
+    assert np.isin(v, arrays["grid_fine.grad"].reshape(-1)).all()
+    assert bench.dump_outputs(str(tmp_path / "c"), {"x": np.ones(1000, np.float32)})["sampled"] == {}
+
+
 def test_tile_liveness_reciprocal_is_an_exact_division():
     """nsr_kernels.h::tile_live divides a sample-point index by the samples per ray S with one multiplication by ceil(2^32 / S)
     (RenderParams.s_magic, nsr_api.cpp::build_params): exact for every point index a call can hold (< 2^25 points, S <= 64)."""
