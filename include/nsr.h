@@ -23,6 +23,7 @@
  *                           src/utils/Renderer.py:109,144 over ALL ranks' draws, without a collective (ABI 8)
  *   nsr_pose_grad        <- autograd of src/common.py:74-88 for that window (local BA, src/Mapper.py:417-419)
  *   nsr_pack_rows        <- (none) gather / scatter of the voxel rows + blobs that travel in the multi-GPU all-reduce
+ *   nsr_mc_* / nsr_point_masks / nsr_cc_* <- src/utils/Mesher.py:53-212,349-574  marching cubes, point_masks, mesh.split
  *
  * Conventions
  *   - all pointers are DEVICE pointers owned by the caller (PyTorch); the library never frees or
@@ -365,6 +366,45 @@ int nsr_frustum_mask(const float *w2c, const float *cam_center, double fx, doubl
  * and weight its loss by the mask instead of compacting.  bound_lo / bound_hi: HOST arrays of 3 doubles. */
 int nsr_aabb_keep(const float *rays_o, const float *rays_d, const float *gt_depth, int64_t n,
                   const double *bound_lo, const double *bound_hi, uint8_t *keep, float *kept_max, void *stream);
+
+/* --- Mesh extraction (src/utils/Mesher.py:349-574) ---------------------------------------------------------------------
+ * Marching cubes over a dense fp32 lattice vol [nx][ny][nz] (x slowest), welded: one vertex per lattice edge whose end values
+ * straddle `level` (a corner is above iff f > level), in lattice-edge-id order 3 * (linear index of the lower end) + axis;
+ * the vertex on the edge a -> a + e_axis is origin + (i + t) * spacing (fp64) with t = (level - f_a) / (f_b - f_a) in fp32.
+ * Faces index those vertices, in cell order, then in the order of the case table; a cell face is cut by a rule of its own
+ * four signs (crack-free); face normals point toward decreasing field.  Bit-identical output run to run.
+ *   nsr_mc_workspace_bytes   device scratch for both calls (-1 for a dimension below 2 or more than 2^31 points)
+ *   nsr_mc_count             writes counts[0] = n_verts, counts[1] = n_faces (int64, device) and fills the workspace
+ *   nsr_mc_emit              after nsr_mc_count on the same workspace: verts [n_verts][3] fp64, faces [n_faces][3] int32;
+ *                            fails when n_verts or 3 * n_faces exceeds INT32_MAX.  origin / spacing: HOST arrays of 3. */
+int64_t nsr_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int nsr_mc_count(const float *vol, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace, int64_t *counts, void *stream);
+int nsr_mc_emit(const float *vol, int32_t nx, int32_t ny, int32_t nz, float level, const double *origin, const double *spacing,
+                void *workspace, int64_t n_verts, int64_t n_faces, double *verts, int32_t *faces, void *stream);
+
+/* Seen / forecast / unseen classification of points [n][3] fp32 (Mesher.point_masks, :53-212) against K cameras given as
+ * w2c = inv(c2w) computed in fp64 and cast to fp32, rows 0..2 ([K][12] device).  mode 0: get_mask_use_all_frames (frustum
+ * and z < 0); 1: keyframes without depth test (projected depth < limit[k] = max(depth_k) * 1.1, [K] device); 2: keyframes
+ * with depth test (depth [K][H][W] device sampled as F.grid_sample(bilinear, zeros, align_corners=True); seen within
+ * +-2.4; forecast below the maximum sampled depth over the point's chunk of `chunk` points -- the reference's
+ * points_batch_size).  out[i]: 0 unseen, 1 seen, 2 forecast.  workspace: nsr_point_masks_workspace_floats floats (mode 2). */
+int64_t nsr_point_masks_workspace_floats(int64_t n, int64_t chunk, int32_t K);
+int nsr_point_masks(const float *points, int64_t n, int64_t chunk, int32_t mode, int32_t K, const float *w2c, const float *depth,
+                    const float *limit, int32_t H, int32_t W, double fx, double fy, double cx, double cy, float *workspace,
+                    uint8_t *out, void *stream);
+
+/* Connected components over pairs of elements (faces sharing an edge, trimesh's face_adjacency): nsr_cc_init once, then
+ * nsr_cc_round with round = 0, 1, ... until *changed (device) != round + 1 after a round; parent[i] is then the largest
+ * element index of i's component.  Indices in `pairs` must be < n < 2^32 - 1. */
+int nsr_cc_init(int64_t n, uint32_t *parent, uint32_t *changed, void *stream);
+int nsr_cc_round(const int32_t *pairs, int64_t n_pairs, int64_t n, uint32_t *parent, uint32_t *changed, int32_t round, void *stream);
+/* area[f] = |(v1 - v0) x (v2 - v0)| / 2 in fp64 */
+int nsr_face_areas(const double *verts, const int32_t *faces, int64_t n_faces, double *area, void *stream);
+/* out[s] = sum of values[order[j]] for j in [seg[s], seg[s + 1]): keys [n] are the sorted keys (segment s = the run of equal
+ * keys starting at seg[s]; seg[n_seg] = n); summed in a fixed order (runs inside tiles of 256 positions, then the tiles in
+ * order): deterministic.  partial: [n] doubles of device scratch. */
+int nsr_segment_sums(const double *values, const int64_t *order, const int64_t *keys, int64_t n, const int64_t *seg, int64_t n_seg,
+                     double *partial, double *out, void *stream);
 
 #ifdef __cplusplus
 }

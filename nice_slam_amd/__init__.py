@@ -2,6 +2,7 @@
 path, drop-in behind the reference's Renderer / decoder / get_samples call surface.
 
     from nice_slam_amd import Renderer, NICE, get_samples, grid_init, load_bound
+    from nice_slam_amd import Mesher, marching_cubes
 
 No CPU / PyTorch fallback exists: every arithmetic entry point goes through libnsr.so.
 """
@@ -12,6 +13,8 @@ from .optim import FlatAdam, MaskedGridAdam  # noqa: F401
 from .frustum import FrustumSelector  # noqa: F401
 from .mapping import backward, get_samples_window, mapping_loss, seed_pixel_draws, tracking_loss  # noqa: F401
 from . import graphs  # noqa: F401
+from .mesher import Mesher, marching_cubes  # noqa: F401
 
 __all__ = ["Renderer", "NICE", "MLP", "MLP_no_xyz", "get_samples", "get_rays", "grid_init", "load_bound",
-           "to_channels_last", "MaskedGridAdam", "FlatAdam", "FrustumSelector", "aabb_keep", "get_samples_window", "mapping_loss", "tracking_loss", "seed_pixel_draws", "get_camera_from_tensor", "backward"]
+           "to_channels_last", "MaskedGridAdam", "FlatAdam", "FrustumSelector", "aabb_keep", "get_samples_window", "mapping_loss", "tracking_loss", "seed_pixel_draws", "get_camera_from_tensor", "backward",
+           "Mesher", "marching_cubes"]

@@ -126,6 +126,18 @@ SYMBOLS = (
     ("nsr_frustum_mask", C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_mc_workspace_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    ("nsr_mc_count", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_mc_emit", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_point_masks_workspace_floats", C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    ("nsr_point_masks", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_cc_init", C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_cc_round", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("nsr_face_areas", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("nsr_segment_sums", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
 )
 
 

@@ -815,3 +815,141 @@ int nsr_camera_from_tensor(const float *cam, int64_t n, float *rt, const float *
 }
 
 }  // extern "C"
+
+// ---- mesh extraction (include/nsr.h, "Mesh extraction") ----
+namespace {
+constexpr int kMcThreads = 256;
+
+int mc_setup(nsr::McParams &P, const float *vol, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace, const char *what) {
+    if (nx < 2 || ny < 2 || nz < 2) return fail(std::string(what) + ": every lattice dimension must be at least 2");
+    const long long n = (long long)nx * ny * nz;
+    if (n > (1ll << 31)) return fail(std::string(what) + ": lattice larger than 2^31 points");
+    if (!vol || !workspace) return fail(std::string(what) + ": null pointer");
+    std::memset(&P, 0, sizeof(P));
+    P.vol = vol; P.nx = nx; P.ny = ny; P.nz = nz; P.n = n; P.level = level;
+    P.nblocks = (int)((n + kMcThreads - 1) / kMcThreads);
+    char *ws = static_cast<char *>(workspace);
+    const long long code_bytes = (n + 15) & ~15ll;
+    P.code = reinterpret_cast<unsigned char *>(ws);
+    P.voff = reinterpret_cast<int *>(ws + code_bytes);
+    P.blk = reinterpret_cast<long long *>(ws + code_bytes + ((4 * n + 15) & ~15ll));
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t nsr_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
+    if (nx < 2 || ny < 2 || nz < 2) return -1;
+    const long long n = (long long)nx * ny * nz;
+    if (n > (1ll << 31)) return -1;
+    const long long nb = (n + kMcThreads - 1) / kMcThreads;
+    return ((n + 15) & ~15ll) + ((4 * n + 15) & ~15ll) + 16 * nb;
+}
+
+int nsr_mc_count(const float *vol, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace, int64_t *counts, void *stream) {
+    nsr::McParams P;
+    if (int rc = mc_setup(P, vol, nx, ny, nz, level, workspace, "nsr_mc_count")) return rc;
+    if (!counts) return fail("nsr_mc_count: null pointer");
+    P.counts = reinterpret_cast<long long *>(counts);
+    NSR_LAUNCH(nsr::mc_count_kernel, dim3((unsigned)P.nblocks), dim3(kMcThreads), kMcThreads * 4, stream, P);
+    NSR_LAUNCH(nsr::mc_scan_kernel, dim3(1), dim3(1024), 2 * 1024 * 8, stream, P);
+    return finish("nsr_mc_count");
+}
+
+int nsr_mc_emit(const float *vol, int32_t nx, int32_t ny, int32_t nz, float level, const double *origin, const double *spacing,
+                void *workspace, int64_t n_verts, int64_t n_faces, double *verts, int32_t *faces, void *stream) {
+    nsr::McParams P;
+    if (int rc = mc_setup(P, vol, nx, ny, nz, level, workspace, "nsr_mc_emit")) return rc;
+    if (n_verts < 0 || n_faces < 0) return fail("nsr_mc_emit: negative count");
+    if (n_verts > 2147483647ll || 3 * n_faces > 2147483647ll) return fail("nsr_mc_emit: vertex or face index count does not fit in int32");
+    if (!origin || !spacing || (n_verts > 0 && !verts) || (n_faces > 0 && !faces)) return fail("nsr_mc_emit: null pointer");
+    if (n_verts == 0) return 0;
+    for (int k = 0; k < 3; ++k) { P.origin[k] = origin[k]; P.spacing[k] = spacing[k]; }
+    P.verts = verts; P.faces = faces;
+    NSR_LAUNCH(nsr::mc_emit_verts_kernel, dim3((unsigned)P.nblocks), dim3(kMcThreads), kMcThreads * 4, stream, P);
+    if (n_faces > 0) NSR_LAUNCH(nsr::mc_emit_faces_kernel, dim3((unsigned)P.nblocks), dim3(kMcThreads), kMcThreads * 4, stream, P);
+    return finish("nsr_mc_emit");
+}
+
+int64_t nsr_point_masks_workspace_floats(int64_t n, int64_t chunk, int32_t K) {
+    if (n < 0 || chunk < 1 || K < 0) return -1;
+    return ((n + chunk - 1) / chunk) * K;
+}
+
+int nsr_point_masks(const float *points, int64_t n, int64_t chunk, int32_t mode, int32_t K, const float *w2c, const float *depth,
+                    const float *limit, int32_t H, int32_t W, double fx, double fy, double cx, double cy, float *workspace,
+                    uint8_t *out, void *stream) {
+    if (n < 0 || chunk < 1 || K < 0) return fail("nsr_point_masks: negative count or chunk < 1");
+    if (mode < 0 || mode > 2) return fail("nsr_point_masks: mode must be 0 (all frames), 1 (keyframes) or 2 (keyframes, depth test)");
+    if (H < 2 || W < 2) return fail("nsr_point_masks: image must be at least 2 x 2");
+    if (n == 0) return 0;
+    if (!points || !out || (K > 0 && !w2c)) return fail("nsr_point_masks: null pointer");
+    if (K > 0 && mode == 1 && !limit) return fail("nsr_point_masks: mode 1 needs the per-keyframe depth limits");
+    if (K > 0 && mode == 2 && (!depth || !workspace)) return fail("nsr_point_masks: mode 2 needs the keyframe depths and a workspace");
+    nsr::MaskParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.pts = points; P.n = n; P.chunk = chunk; P.nchunks = (n + chunk - 1) / chunk;
+    P.K = K; P.mode = mode; P.H = H; P.W = W;
+    const double km[9] = {fx, 0.0, cx, 0.0, fy, cy, 0.0, 0.0, 1.0};
+    for (int i = 0; i < 9; ++i) P.kf[i] = (float)km[i];
+    P.w2c = w2c; P.depth = depth; P.limit = limit; P.cmax = workspace; P.out = out;
+    const int tb = 256;
+    const dim3 grid((unsigned)((n + tb - 1) / tb));
+    if (K > 0 && mode == 2) {
+        NSR_LAUNCH(nsr::point_mask_kernel<0>, dim3((unsigned)((P.nchunks * K + tb - 1) / tb)), dim3(tb), 0, stream, P);
+        NSR_LAUNCH(nsr::point_mask_kernel<1>, grid, dim3(tb), 0, stream, P);
+    }
+    NSR_LAUNCH(nsr::point_mask_kernel<2>, grid, dim3(tb), 0, stream, P);
+    return finish("nsr_point_masks");
+}
+
+int nsr_cc_init(int64_t n, uint32_t *parent, uint32_t *changed, void *stream) {
+    if (n < 0 || n >= (1ll << 32) - 1) return fail("nsr_cc_init: element count out of range");
+    if (!parent || !changed) return fail("nsr_cc_init: null pointer");
+    nsr::CcParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.n = n; P.parent = parent; P.changed = changed;
+    NSR_LAUNCH(nsr::cc_init_kernel, dim3((unsigned)(n / 256 + 1)), dim3(256), 0, stream, P);
+    return finish("nsr_cc_init");
+}
+
+int nsr_cc_round(const int32_t *pairs, int64_t n_pairs, int64_t n, uint32_t *parent, uint32_t *changed, int32_t round, void *stream) {
+    if (n < 0 || n >= (1ll << 32) - 1 || n_pairs < 0 || round < 0) return fail("nsr_cc_round: count or round out of range");
+    if (!parent || !changed || (n_pairs > 0 && !pairs)) return fail("nsr_cc_round: null pointer");
+    if (n == 0) return 0;
+    nsr::CcParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.pairs = pairs; P.n_pairs = n_pairs; P.n = n; P.parent = parent; P.changed = changed; P.round = (unsigned)round + 1u;
+    if (n_pairs > 0) NSR_LAUNCH(nsr::cc_hook_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, P);
+    NSR_LAUNCH(nsr::cc_jump_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, P);
+    return finish("nsr_cc_round");
+}
+
+int nsr_face_areas(const double *verts, const int32_t *faces, int64_t n_faces, double *area, void *stream) {
+    if (n_faces < 0) return fail("nsr_face_areas: negative count");
+    if (n_faces == 0) return 0;
+    if (!verts || !faces || !area) return fail("nsr_face_areas: null pointer");
+    nsr::CcParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.verts = verts; P.faces = faces; P.n = n_faces; P.area = area;
+    NSR_LAUNCH(nsr::face_area_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, stream, P);
+    return finish("nsr_face_areas");
+}
+
+int nsr_segment_sums(const double *values, const int64_t *order, const int64_t *keys, int64_t n, const int64_t *seg, int64_t n_seg,
+                     double *partial, double *out, void *stream) {
+    if (n < 0 || n_seg < 0) return fail("nsr_segment_sums: negative count");
+    if (n_seg == 0) return 0;
+    if (!values || !order || !keys || !seg || !partial || !out) return fail("nsr_segment_sums: null pointer");
+    nsr::CcParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.area = const_cast<double *>(values); P.order = reinterpret_cast<const long long *>(order);
+    P.keys = reinterpret_cast<const long long *>(keys); P.n = n; P.partial = partial;
+    P.seg = reinterpret_cast<const long long *>(seg); P.n_seg = n_seg; P.seg_area = out;
+    if (n > 0) NSR_LAUNCH(nsr::segment_partial_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, P);
+    NSR_LAUNCH(nsr::segment_area_kernel, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, stream, P);
+    return finish("nsr_segment_sums");
+}
+
+}  // extern "C"

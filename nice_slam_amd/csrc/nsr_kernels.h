@@ -1897,6 +1897,441 @@ NSR_KERNEL void camera_from_tensor_kernel(const CamParams P) {
     o[4] = g[3]; o[5] = g[7]; o[6] = g[11];
 }
 
+// ------------------------------------------------------------------------------------------------
+// Mesh extraction (Mesher.get_mesh, src/utils/Mesher.py:349-574).
+//
+// Marching cubes over a dense fp32 lattice [nx][ny][nz] (x slowest; skimage's volume after the reference's transpose,
+// :437-467), welded: one vertex per lattice edge whose end values straddle `level` (a corner is above iff f > level),
+// vertices in lattice-edge-id order 3 * (linear index of the lower end) + axis, faces in cell order, then table order.
+// No append counters: count (one byte per lattice point + per-block totals) -> one-block scan of the block totals ->
+// emit vertices (block scan + block offset; the point's first vertex id is kept) -> emit faces (block scan; a cell edge's
+// vertex id is its lower end's first id + the number of straddling axes below its own).  Every output is a function of the
+// input alone: bit-identical run to run.
+//
+// kMcTable (tools/gen_mc_table.py; construction in tests/mesh_reference.py::mc_table): per case, the triangle count and up
+// to five triangles as cell-edge triples.  Corner c sits at offset (c & 1, (c >> 1) & 1, (c >> 2) & 1); cell edge
+// e = 4 * axis + o1 + 2 * o2 with o1, o2 its offsets along the other two axes in increasing axis order.  Each cube face is
+// cut by a rule of its own four signs (runs of above corners cut off; an ambiguous face separates its above corners), so
+// cells sharing a face agree: crack-free.  Face normals (v1 - v0) x (v2 - v0) point toward decreasing field.
+// ------------------------------------------------------------------------------------------------
+constexpr unsigned char kMcTable[256][16] = {
+    {0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0}, {1,0,4,8,0,0,0,0,0,0,0,0,0,0,0,0}, {1,0,9,5,0,0,0,0,0,0,0,0,0,0,0,0}, {2,4,8,5,5,8,9,0,0,0,0,0,0,0,0,0},
+    {1,1,10,4,0,0,0,0,0,0,0,0,0,0,0,0}, {2,0,1,8,8,1,10,0,0,0,0,0,0,0,0,0}, {2,0,9,5,1,10,4,0,0,0,0,0,0,0,0,0}, {3,1,10,5,5,10,9,9,10,8,0,0,0,0,0,0},
+    {1,1,5,11,0,0,0,0,0,0,0,0,0,0,0,0}, {2,0,4,8,1,5,11,0,0,0,0,0,0,0,0,0}, {2,0,9,1,1,9,11,0,0,0,0,0,0,0,0,0}, {3,1,4,11,11,4,9,9,4,8,0,0,0,0,0,0},
+    {2,4,5,10,10,5,11,0,0,0,0,0,0,0,0,0}, {3,0,5,8,8,5,10,10,5,11,0,0,0,0,0,0}, {3,0,9,4,4,9,10,10,9,11,0,0,0,0,0,0}, {2,8,9,10,10,9,11,0,0,0,0,0,0,0,0,0},
+    {1,2,8,6,0,0,0,0,0,0,0,0,0,0,0,0}, {2,0,4,2,2,4,6,0,0,0,0,0,0,0,0,0}, {2,0,9,5,2,8,6,0,0,0,0,0,0,0,0,0}, {3,2,9,6,6,9,4,4,9,5,0,0,0,0,0,0},
+    {2,1,10,4,2,8,6,0,0,0,0,0,0,0,0,0}, {3,0,1,2,2,1,6,6,1,10,0,0,0,0,0,0}, {3,0,9,5,1,10,4,2,8,6,0,0,0,0,0,0}, {4,1,10,5,5,10,9,9,10,2,2,10,6,0,0,0},
+    {2,1,5,11,2,8,6,0,0,0,0,0,0,0,0,0}, {3,0,4,2,2,4,6,1,5,11,0,0,0,0,0,0}, {3,0,9,1,1,9,11,2,8,6,0,0,0,0,0,0}, {4,1,4,11,11,4,9,9,4,2,2,4,6,0,0,0},
+    {3,2,8,6,4,5,10,10,5,11,0,0,0,0,0,0}, {4,0,5,2,2,5,6,6,5,10,10,5,11,0,0,0}, {4,0,9,4,4,9,10,10,9,11,2,8,6,0,0,0}, {3,2,9,6,6,9,10,10,9,11,0,0,0,0,0,0},
+    {1,2,7,9,0,0,0,0,0,0,0,0,0,0,0,0}, {2,0,4,8,2,7,9,0,0,0,0,0,0,0,0,0}, {2,0,2,5,5,2,7,0,0,0,0,0,0,0,0,0}, {3,2,7,8,8,7,4,4,7,5,0,0,0,0,0,0},
+    {2,1,10,4,2,7,9,0,0,0,0,0,0,0,0,0}, {3,0,1,8,8,1,10,2,7,9,0,0,0,0,0,0}, {3,0,2,5,5,2,7,1,10,4,0,0,0,0,0,0}, {4,1,10,5,5,10,7,7,10,2,2,10,8,0,0,0},
+    {2,1,5,11,2,7,9,0,0,0,0,0,0,0,0,0}, {3,0,4,8,1,5,11,2,7,9,0,0,0,0,0,0}, {3,0,2,1,1,2,11,11,2,7,0,0,0,0,0,0}, {4,1,4,11,11,4,7,7,4,2,2,4,8,0,0,0},
+    {3,2,7,9,4,5,10,10,5,11,0,0,0,0,0,0}, {4,0,5,8,8,5,10,10,5,11,2,7,9,0,0,0}, {4,0,2,4,4,2,10,10,2,11,11,2,7,0,0,0}, {3,2,7,8,8,7,10,10,7,11,0,0,0,0,0,0},
+    {2,6,7,8,8,7,9,0,0,0,0,0,0,0,0,0}, {3,0,4,9,9,4,7,7,4,6,0,0,0,0,0,0}, {3,0,8,5,5,8,7,7,8,6,0,0,0,0,0,0}, {2,4,6,5,5,6,7,0,0,0,0,0,0,0,0,0},
+    {3,1,10,4,6,7,8,8,7,9,0,0,0,0,0,0}, {4,0,1,9,9,1,7,7,1,6,6,1,10,0,0,0}, {4,0,8,5,5,8,7,7,8,6,1,10,4,0,0,0}, {3,1,10,5,5,10,7,7,10,6,0,0,0,0,0,0},
+    {3,1,5,11,6,7,8,8,7,9,0,0,0,0,0,0}, {4,0,4,9,9,4,7,7,4,6,1,5,11,0,0,0}, {4,0,8,1,1,8,11,11,8,7,7,8,6,0,0,0}, {3,1,4,11,11,4,7,7,4,6,0,0,0,0,0,0},
+    {4,4,5,10,10,5,11,6,7,8,8,7,9,0,0,0}, {5,0,6,9,9,6,7,0,5,6,6,5,10,10,5,11}, {5,0,11,4,4,11,10,0,8,11,11,8,7,7,8,6}, {2,6,7,10,10,7,11,0,0,0,0,0,0,0,0,0},
+    {1,3,6,10,0,0,0,0,0,0,0,0,0,0,0,0}, {2,0,4,8,3,6,10,0,0,0,0,0,0,0,0,0}, {2,0,9,5,3,6,10,0,0,0,0,0,0,0,0,0}, {3,3,6,10,4,8,5,5,8,9,0,0,0,0,0,0},
+    {2,1,3,4,4,3,6,0,0,0,0,0,0,0,0,0}, {3,0,1,8,8,1,6,6,1,3,0,0,0,0,0,0}, {3,0,9,5,1,3,4,4,3,6,0,0,0,0,0,0}, {4,1,3,5,5,3,9,9,3,8,8,3,6,0,0,0},
+    {2,1,5,11,3,6,10,0,0,0,0,0,0,0,0,0}, {3,0,4,8,1,5,11,3,6,10,0,0,0,0,0,0}, {3,0,9,1,1,9,11,3,6,10,0,0,0,0,0,0}, {4,1,4,11,11,4,9,9,4,8,3,6,10,0,0,0},
+    {3,3,6,11,11,6,5,5,6,4,0,0,0,0,0,0}, {4,0,5,8,8,5,6,6,5,3,3,5,11,0,0,0}, {4,0,9,4,4,9,6,6,9,3,3,9,11,0,0,0}, {3,3,6,11,11,6,9,9,6,8,0,0,0,0,0,0},
+    {2,2,8,3,3,8,10,0,0,0,0,0,0,0,0,0}, {3,0,4,2,2,4,3,3,4,10,0,0,0,0,0,0}, {3,0,9,5,2,8,3,3,8,10,0,0,0,0,0,0}, {4,2,9,3,3,9,10,10,9,4,4,9,5,0,0,0},
+    {3,1,3,4,4,3,8,8,3,2,0,0,0,0,0,0}, {2,0,1,2,2,1,3,0,0,0,0,0,0,0,0,0}, {4,0,9,5,1,3,4,4,3,8,8,3,2,0,0,0}, {3,1,3,5,5,3,9,9,3,2,0,0,0,0,0,0},
+    {3,1,5,11,2,8,3,3,8,10,0,0,0,0,0,0}, {4,0,4,2,2,4,3,3,4,10,1,5,11,0,0,0}, {4,0,9,1,1,9,11,2,8,3,3,8,10,0,0,0}, {5,1,4,11,11,4,9,9,4,2,2,4,3,3,4,10},
+    {4,2,8,3,3,8,11,11,8,5,5,8,4,0,0,0}, {3,0,5,2,2,5,3,3,5,11,0,0,0,0,0,0}, {5,0,9,4,4,3,8,8,3,2,4,9,3,3,9,11}, {2,2,9,3,3,9,11,0,0,0,0,0,0,0,0,0},
+    {2,2,7,9,3,6,10,0,0,0,0,0,0,0,0,0}, {3,0,4,8,2,7,9,3,6,10,0,0,0,0,0,0}, {3,0,2,5,5,2,7,3,6,10,0,0,0,0,0,0}, {4,2,7,8,8,7,4,4,7,5,3,6,10,0,0,0},
+    {3,1,3,4,4,3,6,2,7,9,0,0,0,0,0,0}, {4,0,1,8,8,1,6,6,1,3,2,7,9,0,0,0}, {4,0,2,5,5,2,7,1,3,4,4,3,6,0,0,0}, {5,1,3,5,5,8,7,7,8,2,5,3,8,8,3,6},
+    {3,1,5,11,2,7,9,3,6,10,0,0,0,0,0,0}, {4,0,4,8,1,5,11,2,7,9,3,6,10,0,0,0}, {4,0,2,1,1,2,11,11,2,7,3,6,10,0,0,0}, {5,1,4,11,11,4,7,7,4,2,2,4,8,3,6,10},
+    {4,2,7,9,3,6,11,11,6,5,5,6,4,0,0,0}, {5,0,5,8,8,5,6,6,5,3,3,5,11,2,7,9}, {5,0,2,4,4,11,6,6,11,3,4,2,11,11,2,7}, {4,2,7,8,8,11,6,6,11,3,8,7,11,0,0,0},
+    {3,3,7,10,10,7,8,8,7,9,0,0,0,0,0,0}, {4,0,4,9,9,4,7,7,4,3,3,4,10,0,0,0}, {4,0,8,5,5,8,7,7,8,3,3,8,10,0,0,0}, {3,3,7,10,10,7,4,4,7,5,0,0,0,0,0,0},
+    {4,1,3,4,4,3,8,8,3,9,9,3,7,0,0,0}, {3,0,1,9,9,1,7,7,1,3,0,0,0,0,0,0}, {5,0,8,5,5,8,7,7,8,3,3,8,1,1,8,4}, {2,1,3,5,5,3,7,0,0,0,0,0,0,0,0,0},
+    {4,1,5,11,3,7,10,10,7,8,8,7,9,0,0,0}, {5,0,4,9,9,4,7,7,4,3,3,4,10,1,5,11}, {5,0,8,1,1,8,11,11,8,7,7,8,3,3,8,10}, {4,1,4,11,11,4,7,7,4,3,3,4,10,0,0,0},
+    {5,3,4,11,11,4,5,3,7,4,4,7,8,8,7,9}, {4,0,3,9,9,3,7,0,5,3,3,5,11,0,0,0}, {2,0,8,4,3,7,11,0,0,0,0,0,0,0,0,0}, {1,3,7,11,0,0,0,0,0,0,0,0,0,0,0,0},
+    {1,3,11,7,0,0,0,0,0,0,0,0,0,0,0,0}, {2,0,4,8,3,11,7,0,0,0,0,0,0,0,0,0}, {2,0,9,5,3,11,7,0,0,0,0,0,0,0,0,0}, {3,3,11,7,4,8,5,5,8,9,0,0,0,0,0,0},
+    {2,1,10,4,3,11,7,0,0,0,0,0,0,0,0,0}, {3,0,1,8,8,1,10,3,11,7,0,0,0,0,0,0}, {3,0,9,5,1,10,4,3,11,7,0,0,0,0,0,0}, {4,1,10,5,5,10,9,9,10,8,3,11,7,0,0,0},
+    {2,1,5,3,3,5,7,0,0,0,0,0,0,0,0,0}, {3,0,4,8,1,5,3,3,5,7,0,0,0,0,0,0}, {3,0,9,1,1,9,3,3,9,7,0,0,0,0,0,0}, {4,1,4,3,3,4,7,7,4,9,9,4,8,0,0,0},
+    {3,3,10,7,7,10,5,5,10,4,0,0,0,0,0,0}, {4,0,5,8,8,5,10,10,5,3,3,5,7,0,0,0}, {4,0,9,4,4,9,10,10,9,3,3,9,7,0,0,0}, {3,3,10,7,7,10,9,9,10,8,0,0,0,0,0,0},
+    {2,2,8,6,3,11,7,0,0,0,0,0,0,0,0,0}, {3,0,4,2,2,4,6,3,11,7,0,0,0,0,0,0}, {3,0,9,5,2,8,6,3,11,7,0,0,0,0,0,0}, {4,2,9,6,6,9,4,4,9,5,3,11,7,0,0,0},
+    {3,1,10,4,2,8,6,3,11,7,0,0,0,0,0,0}, {4,0,1,2,2,1,6,6,1,10,3,11,7,0,0,0}, {4,0,9,5,1,10,4,2,8,6,3,11,7,0,0,0}, {5,1,10,5,5,10,9,9,10,2,2,10,6,3,11,7},
+    {3,1,5,3,3,5,7,2,8,6,0,0,0,0,0,0}, {4,0,4,2,2,4,6,1,5,3,3,5,7,0,0,0}, {4,0,9,1,1,9,3,3,9,7,2,8,6,0,0,0}, {5,1,4,3,3,4,7,7,4,9,9,4,2,2,4,6},
+    {4,2,8,6,3,10,7,7,10,5,5,10,4,0,0,0}, {5,0,5,2,2,5,6,6,5,10,10,5,3,3,5,7}, {5,0,9,4,4,9,10,10,9,3,3,9,7,2,8,6}, {4,2,9,6,6,9,10,10,9,3,3,9,7,0,0,0},
+    {2,2,3,9,9,3,11,0,0,0,0,0,0,0,0,0}, {3,0,4,8,2,3,9,9,3,11,0,0,0,0,0,0}, {3,0,2,5,5,2,11,11,2,3,0,0,0,0,0,0}, {4,2,3,8,8,3,4,4,3,5,5,3,11,0,0,0},
+    {3,1,10,4,2,3,9,9,3,11,0,0,0,0,0,0}, {4,0,1,8,8,1,10,2,3,9,9,3,11,0,0,0}, {4,0,2,5,5,2,11,11,2,3,1,10,4,0,0,0}, {5,1,10,5,5,2,11,11,2,3,5,10,2,2,10,8},
+    {3,1,5,3,3,5,2,2,5,9,0,0,0,0,0,0}, {4,0,4,8,1,5,3,3,5,2,2,5,9,0,0,0}, {2,0,2,1,1,2,3,0,0,0,0,0,0,0,0,0}, {3,1,4,3,3,4,2,2,4,8,0,0,0,0,0,0},
+    {4,2,3,9,9,3,5,5,3,4,4,3,10,0,0,0}, {5,0,5,8,8,5,10,10,5,3,3,5,2,2,5,9}, {3,0,2,4,4,2,10,10,2,3,0,0,0,0,0,0}, {2,2,3,8,8,3,10,0,0,0,0,0,0,0,0,0},
+    {3,3,11,6,6,11,8,8,11,9,0,0,0,0,0,0}, {4,0,4,9,9,4,11,11,4,3,3,4,6,0,0,0}, {4,0,8,5,5,8,11,11,8,3,3,8,6,0,0,0}, {3,3,11,6,6,11,4,4,11,5,0,0,0,0,0,0},
+    {4,1,10,4,3,11,6,6,11,8,8,11,9,0,0,0}, {5,0,1,9,9,6,11,11,6,3,9,1,6,6,1,10}, {5,0,8,5,5,8,11,11,8,3,3,8,6,1,10,4}, {4,1,10,5,5,6,11,11,6,3,5,10,6,0,0,0},
+    {4,1,5,3,3,5,6,6,5,8,8,5,9,0,0,0}, {5,0,4,9,9,3,5,5,3,1,9,4,3,3,4,6}, {3,0,8,1,1,8,3,3,8,6,0,0,0,0,0,0}, {2,1,4,3,3,4,6,0,0,0,0,0,0,0,0,0},
+    {5,3,9,6,6,9,8,3,10,9,9,10,5,5,10,4}, {2,0,5,9,3,10,6,0,0,0,0,0,0,0,0,0}, {4,0,3,4,4,3,10,0,8,3,3,8,6,0,0,0}, {1,3,10,6,0,0,0,0,0,0,0,0,0,0,0,0},
+    {2,6,10,7,7,10,11,0,0,0,0,0,0,0,0,0}, {3,0,4,8,6,10,7,7,10,11,0,0,0,0,0,0}, {3,0,9,5,6,10,7,7,10,11,0,0,0,0,0,0}, {4,4,8,5,5,8,9,6,10,7,7,10,11,0,0,0},
+    {3,1,11,4,4,11,6,6,11,7,0,0,0,0,0,0}, {4,0,1,8,8,1,6,6,1,7,7,1,11,0,0,0}, {4,0,9,5,1,11,4,4,11,6,6,11,7,0,0,0}, {5,1,8,5,5,8,9,1,11,8,8,11,6,6,11,7},
+    {3,1,5,10,10,5,6,6,5,7,0,0,0,0,0,0}, {4,0,4,8,1,5,10,10,5,6,6,5,7,0,0,0}, {4,0,9,1,1,9,10,10,9,6,6,9,7,0,0,0}, {5,1,7,10,10,7,6,1,4,7,7,4,9,9,4,8},
+    {2,4,5,6,6,5,7,0,0,0,0,0,0,0,0,0}, {3,0,5,8,8,5,6,6,5,7,0,0,0,0,0,0}, {3,0,9,4,4,9,6,6,9,7,0,0,0,0,0,0}, {2,6,8,7,7,8,9,0,0,0,0,0,0,0,0,0},
+    {3,2,8,7,7,8,11,11,8,10,0,0,0,0,0,0}, {4,0,4,2,2,4,7,7,4,11,11,4,10,0,0,0}, {4,0,9,5,2,8,7,7,8,11,11,8,10,0,0,0}, {5,2,10,7,7,10,11,2,9,10,10,9,4,4,9,5},
+    {4,1,11,4,4,11,8,8,11,2,2,11,7,0,0,0}, {3,0,1,2,2,1,7,7,1,11,0,0,0,0,0,0}, {5,0,9,5,1,11,4,4,11,8,8,11,2,2,11,7}, {4,1,2,5,5,2,9,1,11,2,2,11,7,0,0,0},
+    {4,1,5,10,10,5,8,8,5,2,2,5,7,0,0,0}, {5,0,4,2,2,4,7,7,10,5,5,10,1,7,4,10}, {5,0,9,1,1,9,10,10,7,8,8,7,2,10,9,7}, {2,1,4,10,2,9,7,0,0,0,0,0,0,0,0,0},
+    {3,2,8,7,7,8,5,5,8,4,0,0,0,0,0,0}, {2,0,5,2,2,5,7,0,0,0,0,0,0,0,0,0}, {4,0,9,4,4,7,8,8,7,2,4,9,7,0,0,0}, {1,2,9,7,0,0,0,0,0,0,0,0,0,0,0,0},
+    {3,2,6,9,9,6,11,11,6,10,0,0,0,0,0,0}, {4,0,4,8,2,6,9,9,6,11,11,6,10,0,0,0}, {4,0,2,5,5,2,11,11,2,10,10,2,6,0,0,0}, {5,2,5,8,8,5,4,2,6,5,5,6,11,11,6,10},
+    {4,1,11,4,4,11,6,6,11,2,2,11,9,0,0,0}, {5,0,1,8,8,1,6,6,1,2,2,1,9,9,1,11}, {5,0,2,5,5,2,11,11,2,1,1,2,4,4,2,6}, {2,1,11,5,2,6,8,0,0,0,0,0,0,0,0,0},
+    {4,1,5,10,10,5,6,6,5,2,2,5,9,0,0,0}, {5,0,4,8,1,5,10,10,5,6,6,5,2,2,5,9}, {3,0,2,1,1,2,10,10,2,6,0,0,0,0,0,0}, {4,1,2,10,10,2,6,1,4,2,2,4,8,0,0,0},
+    {3,2,6,9,9,6,5,5,6,4,0,0,0,0,0,0}, {4,0,5,8,8,5,6,6,5,2,2,5,9,0,0,0}, {2,0,2,4,4,2,6,0,0,0,0,0,0,0,0,0}, {1,2,6,8,0,0,0,0,0,0,0,0,0,0,0,0},
+    {2,8,10,9,9,10,11,0,0,0,0,0,0,0,0,0}, {3,0,4,9,9,4,11,11,4,10,0,0,0,0,0,0}, {3,0,8,5,5,8,11,11,8,10,0,0,0,0,0,0}, {2,4,10,5,5,10,11,0,0,0,0,0,0,0,0,0},
+    {3,1,11,4,4,11,8,8,11,9,0,0,0,0,0,0}, {2,0,1,9,9,1,11,0,0,0,0,0,0,0,0,0}, {4,0,8,5,5,8,11,11,8,1,1,8,4,0,0,0}, {1,1,11,5,0,0,0,0,0,0,0,0,0,0,0,0},
+    {3,1,5,10,10,5,8,8,5,9,0,0,0,0,0,0}, {4,0,4,9,9,10,5,5,10,1,9,4,10,0,0,0}, {2,0,8,1,1,8,10,0,0,0,0,0,0,0,0,0}, {1,1,4,10,0,0,0,0,0,0,0,0,0,0,0,0},
+    {2,4,5,8,8,5,9,0,0,0,0,0,0,0,0,0}, {1,0,5,9,0,0,0,0,0,0,0,0,0,0,0,0}, {1,0,8,4,0,0,0,0,0,0,0,0,0,0,0,0}, {0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0},
+};
+
+struct McParams {
+    const float *vol;
+    int nx, ny, nz, nblocks;
+    long long n;                   // nx * ny * nz
+    float level;
+    unsigned char *code;           // [n]: bits 0-2 straddling edge along x / y / z at this point, bits 3-5 triangles of its cell
+    int *voff;                     // [n]: first vertex id of the point's edges
+    long long *blk;                // [nblocks][2]: block vertex / face totals, then their exclusive offsets
+    long long *counts;             // [2]: n_verts, n_faces
+    double origin[3], spacing[3];
+    double *verts;                 // [V][3]
+    int *faces;                    // [F][3]
+};
+
+// exclusive prefix sum over the block (every thread must call it); *total = the block's sum
+NSR_DEV int block_excl_scan(int v, int *lds, int *total) {
+    const int t = tid(), nt = nthreads();
+    lds[t] = v;
+    block_sync();
+    for (int d = 1; d < nt; d <<= 1) {
+        const int add = t >= d ? lds[t - d] : 0;
+        block_sync();
+        lds[t] += add;
+        block_sync();
+    }
+    const int incl = lds[t];
+    *total = lds[nt - 1];
+    block_sync();
+    return incl - v;
+}
+
+NSR_DEV int mc_case(const McParams &P, long long p) {
+    const long long sx = (long long)P.ny * P.nz, sy = P.nz;
+    int c = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const long long q = p + (k & 1) * sx + ((k >> 1) & 1) * sy + ((k >> 2) & 1);
+        c |= (P.vol[q] > P.level ? 1 : 0) << k;
+    }
+    return c;
+}
+
+NSR_KERNEL void mc_count_kernel(const McParams P) {
+    int *lds = reinterpret_cast<int *>(lds_base());
+    const long long p = (long long)bid_x() * nthreads() + tid();
+    int nv = 0, nf = 0;
+    if (p < P.n) {
+        const int ix = (int)(p / ((long long)P.ny * P.nz)), iy = (int)((p / P.nz) % P.ny), iz = (int)(p % P.nz);
+        const long long step[3] = {(long long)P.ny * P.nz, (long long)P.nz, 1ll};
+        const int idx[3] = {ix, iy, iz}, dim[3] = {P.nx, P.ny, P.nz};
+        const bool a0 = P.vol[p] > P.level;
+        int code = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+            if (idx[a] + 1 < dim[a] && ((P.vol[p + step[a]] > P.level) != a0)) code |= 1 << a;
+        if (ix + 1 < P.nx && iy + 1 < P.ny && iz + 1 < P.nz) nf = kMcTable[mc_case(P, p)][0];
+        nv = __builtin_popcount(code);
+        P.code[p] = (unsigned char)(code | (nf << 3));
+    }
+    int tv, tf;
+    block_excl_scan(nv, lds, &tv);
+    block_excl_scan(nf, lds, &tf);
+    if (tid() == 0) {
+        P.blk[2 * bid_x()] = tv;
+        P.blk[2 * bid_x() + 1] = tf;
+    }
+}
+
+// one block: block totals -> exclusive block offsets (in place), grand totals -> counts
+NSR_KERNEL void mc_scan_kernel(const McParams P) {
+    long long *red = reinterpret_cast<long long *>(lds_base());         // [2][nthreads]
+    const int t = tid(), nt = nthreads();
+    const long long per = ((long long)P.nblocks + nt - 1) / nt;
+    const long long b0 = (long long)t * per;
+    const long long b1 = b0 + per < (long long)P.nblocks ? b0 + per : (long long)P.nblocks;
+    long long sv = 0, sf = 0;
+    for (long long b = b0; b < b1; ++b) { sv += P.blk[2 * b]; sf += P.blk[2 * b + 1]; }
+    red[t] = sv;
+    red[nt + t] = sf;
+    block_sync();
+    for (int d = 1; d < nt; d <<= 1) {
+        const long long av = t >= d ? red[t - d] : 0, af = t >= d ? red[nt + t - d] : 0;
+        block_sync();
+        red[t] += av;
+        red[nt + t] += af;
+        block_sync();
+    }
+    long long ov = red[t] - sv, of = red[nt + t] - sf;
+    for (long long b = b0; b < b1; ++b) {
+        const long long cv = P.blk[2 * b], cf = P.blk[2 * b + 1];
+        P.blk[2 * b] = ov;
+        P.blk[2 * b + 1] = of;
+        ov += cv;
+        of += cf;
+    }
+    if (t == nt - 1) {
+        P.counts[0] = red[t];
+        P.counts[1] = red[nt + t];
+    }
+}
+
+NSR_KERNEL void mc_emit_verts_kernel(const McParams P) {
+    int *lds = reinterpret_cast<int *>(lds_base());
+    const long long p = (long long)bid_x() * nthreads() + tid();
+    const int code = p < P.n ? (P.code[p] & 7) : 0;
+    int tot;
+    const int off = (int)P.blk[2 * bid_x()] + block_excl_scan(__builtin_popcount(code), lds, &tot);
+    if (p >= P.n) return;
+    P.voff[p] = off;
+    if (!code) return;
+    const int idx[3] = {(int)(p / ((long long)P.ny * P.nz)), (int)((p / P.nz) % P.ny), (int)(p % P.nz)};
+    const long long step[3] = {(long long)P.ny * P.nz, (long long)P.nz, 1ll};
+    const float fa = P.vol[p];
+    int v = off;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (!(code & (1 << a))) continue;
+        const float fb = P.vol[p + step[a]];
+        const float t = (P.level - fa) / (fb - fa);
+        double* out = P.verts + 3ll * v;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            double x = (double)idx[k];
+            if (k == a) x = x + (double)t;
+            out[k] = P.origin[k] + x * P.spacing[k];
+        }
+        ++v;
+    }
+}
+
+NSR_KERNEL void mc_emit_faces_kernel(const McParams P) {
+    int *lds = reinterpret_cast<int *>(lds_base());
+    const long long p = (long long)bid_x() * nthreads() + tid();
+    const int nf = p < P.n ? (P.code[p] >> 3) : 0;
+    int tot;
+    const long long off = P.blk[2 * bid_x() + 1] + block_excl_scan(nf, lds, &tot);
+    if (!nf) return;
+    const unsigned char *row = kMcTable[mc_case(P, p)];
+    const long long step[3] = {(long long)P.ny * P.nz, (long long)P.nz, 1ll};
+    for (int j = 0; j < nf; ++j) {
+        int *out = P.faces + 3 * (off + j);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int e = row[1 + 3 * j + k];
+            const int a = e >> 2, b1 = a == 0 ? 1 : 0, b2 = a == 2 ? 1 : 2;
+            const long long q = p + (e & 1) * step[b1] + ((e >> 1) & 1) * step[b2];
+            out[k] = P.voff[q] + __builtin_popcount(P.code[q] & ((1 << a) - 1));
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Seen / forecast / unseen classification of points (Mesher.point_masks, :53-212), one thread per point, every camera.
+//   mode 0  get_mask_use_all_frames (:88-125): frustum (edge 0 = seen, edge -1000 = forecast) and z < 0
+//   mode 1  keyframes, depth_test False (:178-191): + projected depth < limit[k] = max(keyframe depth) * 1.1
+//   mode 2  keyframes, depth_test True (:156-177): + seen within +-2.4 of the depth sampled the way
+//           F.grid_sample(bilinear, zeros, align_corners=True) does after the reference's normalisation; forecast below the
+//           maximum sampled depth over the point's points_batch_size chunk (:78-79, :166) -- a pass of its own (phase 1)
+// Pose algebra as the reference: w2c = inv(c2w) in fp64 on the host, cast to fp32; w2c @ [p, 1], x *= -1, K @ cam in fp32
+// (sequential sums), z + 1e-8, strict comparisons at the image edges.  Output byte: 0 unseen, 1 seen, 2 forecast.
+// ------------------------------------------------------------------------------------------------
+struct MaskParams {
+    const float *pts;              // [n][3]
+    long long n, chunk, nchunks;
+    int K, mode, H, W;
+    float kf[9];                   // the intrinsics matrix as K.float() (row-major)
+    const float *w2c;              // [K][12]: rows 0..2
+    const float *depth;            // [K][H][W] (mode 2)
+    const float *limit;            // [K] (mode 1)
+    float *cmax;                   // [nchunks][K] (mode 2)
+    unsigned char *out;            // [n]
+};
+
+struct MaskProj { float u, v, z, pd; };
+
+NSR_DEV MaskProj mask_project(const MaskParams &P, int k, float px, float py, float pz) {
+    const float *w = P.w2c + 12 * k;
+    float cam[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) cam[r] = ((w[r * 4 + 0] * px + w[r * 4 + 1] * py) + w[r * 4 + 2] * pz) + w[r * 4 + 3];
+    const float X = cam[0] * -1.f, Y = cam[1], Z = cam[2];
+    const float uh = (P.kf[0] * X + P.kf[1] * Y) + P.kf[2] * Z;
+    const float vh = (P.kf[3] * X + P.kf[4] * Y) + P.kf[5] * Z;
+    const float zh = (P.kf[6] * X + P.kf[7] * Y) + P.kf[8] * Z;
+    MaskProj R;
+    R.z = zh + 1e-8f;
+    R.u = uh / R.z;
+    R.v = vh / R.z;
+    R.pd = -Z;
+    return R;
+}
+
+NSR_DEV float mask_tap(const float *d, int H, int W, float y, float x) {
+    if (!(x > -1.f && x < (float)W && y > -1.f && y < (float)H)) return 0.f;
+    return d[(long long)(int)y * W + (int)x];
+}
+
+NSR_DEV float mask_depth_sample(const MaskParams &P, int k, float u, float v) {
+    const float gx = (u / (float)(P.W - 1)) * 2.f - 1.f;
+    const float gy = (v / (float)(P.H - 1)) * 2.f - 1.f;
+    const float x = ((gx + 1.f) / 2.f) * (float)(P.W - 1);           // ATen's un-normalisation (align_corners=True)
+    const float y = ((gy + 1.f) / 2.f) * (float)(P.H - 1);
+    const float xw = floorf(x), yn = floorf(y);
+    const float w = x - xw, e = 1.f - w, nn = y - yn, s = 1.f - nn;
+    const float *d = P.depth + (long long)k * P.H * P.W;
+    float o = 0.f;
+    o = o + mask_tap(d, P.H, P.W, yn, xw) * (s * e);
+    o = o + mask_tap(d, P.H, P.W, yn, xw + 1.f) * (s * w);
+    o = o + mask_tap(d, P.H, P.W, yn + 1.f, xw) * (nn * e);
+    o = o + mask_tap(d, P.H, P.W, yn + 1.f, xw + 1.f) * (nn * w);
+    return o;
+}
+
+// PHASE 0: cmax = 0; 1: per-(chunk, keyframe) maximum of the sampled depth; 2: classify
+template <int PHASE>
+NSR_KERNEL void point_mask_kernel(const MaskParams P) {
+    const long long i = (long long)bid_x() * nthreads() + tid();
+    if (PHASE == 0) {
+        if (i < P.nchunks * P.K) P.cmax[i] = 0.f;
+        return;
+    }
+    if (PHASE == 1) {
+        // every lane takes part in the wave maximum: no early exit.  A wave whose 64 points lie in one chunk reduces first and
+        // issues one atomic per keyframe (the whole lattice hits nchunks * K addresses); the maximum is taken on the bit
+        // patterns, like atomic_max_pos (samples are >= 0; a NaN wins, as in torch.max)
+        const bool live = i < P.n;
+        const long long ii = live ? i : 0;
+        const float px = P.pts[3 * ii], py = P.pts[3 * ii + 1], pz = P.pts[3 * ii + 2];
+        const int ch = live ? (int)(ii / P.chunk) : -1;
+        const bool one_chunk = ballot64(ch == shfl_i(ch, 0)) == ~0ull;
+        for (int k = 0; k < P.K; ++k) {
+            const MaskProj R = mask_project(P, k, px, py, pz);
+            float ds = live ? mask_depth_sample(P, k, R.u, R.v) : 0.f;
+            if (one_chunk) {
+#pragma unroll
+                for (int m = 32; m >= 1; m >>= 1) {
+                    const float o = shfl_xor(ds, m);
+                    ds = __builtin_bit_cast(unsigned, o) > __builtin_bit_cast(unsigned, ds) ? o : ds;
+                }
+                if ((tid() & 63) == 0) atomic_max_pos(P.cmax + (long long)ch * P.K + k, ds);
+            } else if (live) {
+                atomic_max_pos(P.cmax + (long long)ch * P.K + k, ds);
+            }
+        }
+        return;
+    }
+    if (i >= P.n) return;
+    const float px = P.pts[3 * i], py = P.pts[3 * i + 1], pz = P.pts[3 * i + 2];
+    const long long ch = i / P.chunk;
+    const float Wf = (float)P.W, Hf = (float)P.H;
+    bool seen = false, fore = false;
+    for (int k = 0; k < P.K && !seen; ++k) {
+        const MaskProj R = mask_project(P, k, px, py, pz);
+        bool s_in = (R.u < Wf) && (R.u > 0.f) && (R.v < Hf) && (R.v > 0.f) && (R.z < 0.f);
+        bool f_in = (R.u < (float)(P.W + 1000)) && (R.u > -1000.f) && (R.v < (float)(P.H + 1000)) && (R.v > -1000.f) && (R.z < 0.f);
+        if (P.mode == 2) {
+            const float ds = mask_depth_sample(P, k, R.u, R.v);
+            f_in = f_in && (R.pd < P.cmax[ch * P.K + k]);
+            s_in = s_in && (R.pd < ds + 2.4f) && (ds - 2.4f < R.pd);
+        } else if (P.mode == 1) {
+            f_in = f_in && (R.pd < P.limit[k]);
+            s_in = s_in && (R.pd < P.limit[k]);
+        }
+        seen = seen || s_in;
+        fore = fore || f_in;
+    }
+    P.out[i] = seen ? 1 : (fore ? 2 : 0);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Connected components of a mesh's faces (trimesh split(only_watertight=False), Mesher.py:487-498) over the pairs of faces
+// that share an edge: union-find with hooking by maximum (the device has no compare-and-swap primitive shared with the
+// emulator: parent[x] >= x only grows, so no cycles; a link lost to a larger one is found again in the next round) and
+// pointer jumping; rounds until no pair hooks.  The root of a component is its largest face index.  Face areas in fp64;
+// component areas over the faces sorted by component, in a fixed summation order (segment_partial / segment_area).
+// ------------------------------------------------------------------------------------------------
+struct CcParams {
+    const int *pairs;              // [n_pairs][2]
+    long long n_pairs, n;          // n: faces (or segments)
+    unsigned *parent;              // [n]
+    unsigned *changed;             // [1]: the last round (1-based) in which a pair hooked, 0 = none yet
+    unsigned round;
+    const double *verts;           // [V][3]
+    const int *faces;              // [F][3]
+    double *area;                  // [F]
+    const long long *seg;          // [n_seg + 1] run starts in `order`
+    const long long *order;        // [n] faces sorted by component
+    const long long *keys;         // [n] their sorted component keys
+    double *partial;               // [n] tile partial sums
+    long long n_seg;
+    double *seg_area;              // [n_seg]
+};
+
+NSR_DEV unsigned cc_find(const unsigned *parent, unsigned x) {
+    unsigned p = parent[x];
+    while (p != x) { x = p; p = parent[x]; }
+    return x;
+}
+
+NSR_KERNEL void cc_init_kernel(const CcParams P) {
+    const long long i = (long long)bid_x() * nthreads() + tid();
+    if (i < P.n) P.parent[i] = (unsigned)i;
+    if (i == 0) *P.changed = 0u;
+}
+
+NSR_KERNEL void cc_hook_kernel(const CcParams P) {
+    const long long i = (long long)bid_x() * nthreads() + tid();
+    if (i >= P.n_pairs) return;
+    const unsigned ra = cc_find(P.parent, (unsigned)P.pairs[2 * i]), rb = cc_find(P.parent, (unsigned)P.pairs[2 * i + 1]);
+    if (ra == rb) return;
+    const unsigned lo = ra < rb ? ra : rb, hi = ra < rb ? rb : ra;
+    atomic_fetch_max_u32(P.parent + lo, hi);
+    atomic_exchange_u32(P.changed, P.round);
+}
+
+NSR_KERNEL void cc_jump_kernel(const CcParams P) {
+    const long long i = (long long)bid_x() * nthreads() + tid();
+    if (i < P.n) P.parent[i] = cc_find(P.parent, (unsigned)i);
+}
+
+NSR_KERNEL void face_area_kernel(const CcParams P) {
+    const long long f = (long long)bid_x() * nthreads() + tid();
+    if (f >= P.n) return;
+    const double *a = P.verts + 3ll * P.faces[3 * f], *b = P.verts + 3ll * P.faces[3 * f + 1], *c = P.verts + 3ll * P.faces[3 * f + 2];
+    const double ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
+    const double vx = c[0] - a[0], vy = c[1] - a[1], vz = c[2] - a[2];
+    const double cx = uy * vz - uz * vy, cy = uz * vx - ux * vz, cz = ux * vy - uy * vx;
+    P.area[f] = 0.5 * sqrt((cx * cx + cy * cy) + cz * cz);
+}
+
+// segment sums in two fixed-order passes: a run of equal keys inside a tile of kSegTile sorted positions is summed by the
+// thread at its first position (partial[j]); a segment then adds its tile partials in tile order
+constexpr int kSegTile = 256;
+NSR_KERNEL void segment_partial_kernel(const CcParams P) {
+    const long long j = (long long)bid_x() * nthreads() + tid();
+    if (j >= P.n) return;
+    if (j % kSegTile != 0 && P.keys[j] == P.keys[j - 1]) return;
+    const long long end = (j / kSegTile + 1) * kSegTile < P.n ? (j / kSegTile + 1) * kSegTile : P.n;
+    double acc = 0.0;
+    for (long long q = j; q < end && P.keys[q] == P.keys[j]; ++q) acc += P.area[P.order[q]];
+    P.partial[j] = acc;
+}
+
+NSR_KERNEL void segment_area_kernel(const CcParams P) {
+    const long long s = (long long)bid_x() * nthreads() + tid();
+    if (s >= P.n_seg) return;
+    double acc = 0.0;
+    for (long long j = P.seg[s]; j < P.seg[s + 1]; j = (j / kSegTile + 1) * kSegTile) acc += P.partial[j];
+    P.seg_area[s] = acc;
+}
+
 }  // namespace nsr
 
 #include "nsr_bwd2.h"
