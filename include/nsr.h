@@ -24,6 +24,8 @@
  *   nsr_pose_grad        <- autograd of src/common.py:74-88 for that window (local BA, src/Mapper.py:417-419)
  *   nsr_pack_rows        <- (none) gather / scatter of the voxel rows + blobs that travel in the multi-GPU all-reduce
  *   nsr_mc_* / nsr_point_masks / nsr_cc_* <- src/utils/Mesher.py:53-212,349-574  marching cubes, point_masks, mesh.split
+ *   nsr_nn_* / nsr_sample_surface / nsr_dist_stats / nsr_icp_stats / nsr_transform_points / nsr_cull_vertices
+ *                        <- src/tools/eval_recon.py:24-59,91-117, src/tools/cull_mesh.py:45-75  reconstruction evaluation
  *
  * Conventions
  *   - all pointers are DEVICE pointers owned by the caller (PyTorch); the library never frees or
@@ -405,6 +407,59 @@ int nsr_face_areas(const double *verts, const int32_t *faces, int64_t n_faces, d
  * order): deterministic.  partial: [n] doubles of device scratch. */
 int nsr_segment_sums(const double *values, const int64_t *order, const int64_t *keys, int64_t n, const int64_t *seg, int64_t n_seg,
                      double *partial, double *out, void *stream);
+
+/* --- Reconstruction evaluation (src/tools/eval_recon.py, src/tools/cull_mesh.py) ------------------------------------------
+ * Exact nearest neighbour (the cKDTree queries of eval_recon.py:24-43 and of Open3D's ICP, :45-59).  Points are [n][3], fp32
+ * (fp64 = 0) or fp64 (fp64 = 1), computed in fp64: dist = sqrt((dx*dx + dy*dy) + dz*dz), ties -> smallest reference index.
+ *   nsr_nn_bounds           bounding box of the reference set into bounds[0..5] (lo xyz, hi xyz); bounds: NSR_NN_BOUNDS_DOUBLES
+ *                           doubles of device memory (the rest is per-block scratch)
+ *   nsr_nn_plan             HOST: from the box (HOST copy of bounds[0..5]) the grid plan, NSR_NN_PLAN_DOUBLES host doubles;
+ *                           fails for n_ref < 1, n_ref >= 2^31 - 1, or non-finite coordinates.  The cell table is O(n_ref).
+ *   nsr_nn_workspace_bytes  device workspace of nsr_nn_build / nsr_nn_query for that plan (-1: invalid)
+ *   nsr_nn_keys             cell key of every point (queries outside the box are clamped to it); keys [n] int64
+ *   nsr_nn_build            after sorting the reference keys (sorted_keys, and `order`: the permutation that sorts them):
+ *                           fills the workspace (reference points in key order, fine- and coarse-cell tables)
+ *   nsr_nn_query            dist [n] fp64, idx [n] int64, ncand [n] int32 (optional: points examined); qorder [n] (optional):
+ *                           the order in which threads take the queries (the queries sorted by their keys).  plan: HOST. */
+#define NSR_NN_BOUNDS_DOUBLES (6 * 257)
+#define NSR_NN_PLAN_DOUBLES 16
+int nsr_nn_bounds(const void *ref, int64_t n_ref, int32_t fp64, double *bounds, void *stream);
+int nsr_nn_plan(const double *bounds, int64_t n_ref, double *plan);
+int64_t nsr_nn_workspace_bytes(const double *plan, int64_t n_ref);
+int nsr_nn_keys(const void *pts, int64_t n, int32_t fp64, const double *plan, int64_t *keys, void *stream);
+int nsr_nn_build(const void *ref, int64_t n_ref, int32_t fp64, const double *plan, const int64_t *sorted_keys, const int64_t *order,
+                 void *workspace, void *stream);
+int nsr_nn_query(const void *query, int64_t n_query, int32_t fp64, const int64_t *qorder, const double *plan, const void *workspace,
+                 int64_t n_ref, double *dist, int64_t *idx, int32_t *ncand, void *stream);
+
+/* Area-weighted surface sampling (trimesh.sample.sample_surface, called by eval_recon.py:103,106).  verts [nv][3] fp64,
+ * faces [nf][3] int32; areas in fp64 as trimesh's area_faces, their inclusive scan in a fixed order; face = first with
+ * cum >= u0 * total; (a, b) -> |(a, b) - 1| when a + b > 1; point = ((v1 - v0) a + (v2 - v0) b) + v0.  uniforms [n][3]
+ * (u0, a, b) fp64, or NULL: drawn in the kernel by philox(counter = (point, draw), key = seed), 53 bits each.
+ * points [n][3] fp64, face_index [n] int64.  workspace: nsr_sample_workspace_bytes(nf). */
+int64_t nsr_sample_workspace_bytes(int64_t nf);
+int nsr_sample_surface(const double *verts, int64_t nv, const int32_t *faces, int64_t nf, int64_t n, const double *uniforms,
+                       uint64_t seed, void *workspace, double *points, int64_t *face_index, void *stream);
+
+/* Fixed-order fp64 reductions (per-block trees, then the blocks in order: bit-identical run to run).  partial:
+ * nsr_recon_partial_doubles(n) doubles of device scratch.
+ *   nsr_dist_stats   out[0] = sum of dist, out[1] = number of dist < th (eval_recon.py:24-43: mean, completion ratio)
+ *   nsr_icp_stats    over the correspondences with dist < th (idx into tgt [n_tgt][3]; src [n][3]): out[0] count, out[1] sum of
+ *                    |s - t|^2, out[2..4] source centroid, out[5..7] target centroid, out[8..16] sum of (t - mu_t)(s - mu_s)^T
+ *                    row-major (the point-to-point estimate inside Open3D's registration_icp, eval_recon.py:45-59)
+ *   nsr_transform_points  pts [n][3] fp64 <- R pts + t, m: HOST [3][4] row-major [R | t] */
+int64_t nsr_recon_partial_doubles(int64_t n);
+int nsr_dist_stats(const double *dist, int64_t n, double th, double *partial, double *out, void *stream);
+int nsr_icp_stats(const double *src, const double *tgt, const int64_t *idx, const double *dist, int64_t n, int64_t n_tgt, double th,
+                  double *partial, double *out, void *stream);
+int nsr_transform_points(double *pts, int64_t n, const double *m, void *stream);
+
+/* Frustum culling of mesh vertices over a trajectory (cull_mesh.py:45-75), all K poses in one launch.  verts [n][3] fp32 or fp64
+ * (rounded to fp32 as the reference's .float()); w2c [K][12] fp32: rows 0..2 of inv(c2w) as the reference computes it;
+ * seen[v] = 1 iff some pose has 0 <= -z, 0 < u < W, 0 < v < H (fp32, the reference's order, z = K[2] . cam + 1e-5);
+ * keep[f] = 1 unless none of the face's vertices is seen (faces [nf][3] int32; nf = 0: no faces). */
+int nsr_cull_vertices(const void *verts, int64_t n, int32_t fp64, const float *w2c, int32_t K, int32_t H, int32_t W, double fx,
+                      double fy, double cx, double cy, const int32_t *faces, int64_t nf, uint8_t *seen, uint8_t *keep, void *stream);
 
 #ifdef __cplusplus
 }

@@ -138,6 +138,23 @@ SYMBOLS = (
     ("nsr_face_areas", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("nsr_segment_sums", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    ("nsr_nn_bounds", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("nsr_nn_plan", C.c_int, [C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double)]),
+    ("nsr_nn_workspace_bytes", C.c_int64, [C.POINTER(C.c_double), C.c_int64]),
+    ("nsr_nn_keys", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    ("nsr_nn_build", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_nn_query", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int64,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_sample_workspace_bytes", C.c_int64, [C.c_int64]),
+    ("nsr_sample_surface", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_recon_partial_doubles", C.c_int64, [C.c_int64]),
+    ("nsr_dist_stats", C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_icp_stats", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p,
+                                C.c_void_p, C.c_void_p]),
+    ("nsr_transform_points", C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_void_p]),
+    ("nsr_cull_vertices", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                    C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 )
 
 

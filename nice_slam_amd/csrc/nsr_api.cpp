@@ -1,4 +1,5 @@
 // nsr_api.cpp -- the C ABI of libnsr.so (see include/nsr.h).  Compiled as HIP for gfx950.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -9,6 +10,9 @@
 
 #include "nsr_rt.h"
 #include "nsr_kernels.h"
+// (spelled from two levels up: the library build finds it beside this file, the CPU emulator build -- which compiles a copy of
+//  this file elsewhere -- through its include path tests/emu)
+#include "../../nice_slam_amd/csrc/nsr_recon.h"
 
 namespace {
 
@@ -950,6 +954,265 @@ int nsr_segment_sums(const double *values, const int64_t *order, const int64_t *
     if (n > 0) NSR_LAUNCH(nsr::segment_partial_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, P);
     NSR_LAUNCH(nsr::segment_area_kernel, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, stream, P);
     return finish("nsr_segment_sums");
+}
+
+}  // extern "C"
+
+// ---- reconstruction evaluation (include/nsr.h, "Reconstruction evaluation") ----
+namespace {
+
+inline long long align16(long long b) { return (b + 15) & ~15ll; }
+
+struct NnLayout { long long sref, sidx, fstart, fend, cstart, cend, cbox, total; };
+
+NnLayout nn_layout(long long m, long long ncell, long long ncoarse) {
+    NnLayout L;
+    L.sref = 0;
+    L.sidx = L.sref + align16(24 * m);
+    L.fstart = L.sidx + align16(8 * m);
+    L.fend = L.fstart + align16(4 * ncell);
+    L.cstart = L.fend + align16(4 * ncell);
+    L.cend = L.cstart + align16(4 * ncoarse);
+    L.cbox = L.cend + align16(4 * ncoarse);
+    L.total = L.cbox + align16(48 * ncoarse);
+    return L;
+}
+
+// the plan as NnParams; false if it is not one nsr_nn_plan could have written for m points (m < 0: for any number of points)
+bool nn_from_plan(nsr::NnParams &P, const double *plan, long long m) {
+    std::memset(&P, 0, sizeof(P));
+    if (!plan || m == 0) return false;
+    for (int d = 0; d < 3; ++d) {
+        P.lo[d] = plan[nsr::kNnLo + d];
+        P.hi[d] = plan[nsr::kNnHi + d];
+        const double n = plan[nsr::kNnDim + d], c = plan[nsr::kNnCDim + d];
+        if (!(n >= 1 && n <= (1 << 20) && c == std::ceil(n / nsr::kNnLocal))) return false;
+        P.nd[d] = (int)n;
+        P.nc[d] = (int)c;
+        if (!std::isfinite(P.lo[d]) || !std::isfinite(P.hi[d])) return false;
+    }
+    P.h = plan[nsr::kNnH];
+    P.slack = plan[nsr::kNnSlack];
+    P.ncell = (long long)P.nd[0] * P.nd[1] * P.nd[2];
+    P.ncoarse = (long long)P.nc[0] * P.nc[1] * P.nc[2];
+    P.m = m;
+    return P.h > 0 && std::isfinite(P.h) && P.ncell == (long long)plan[nsr::kNnCells] && P.ncoarse == (long long)plan[nsr::kNnCoarse] &&
+           (m < 0 || P.ncell <= 4 * m + 64);
+}
+
+void nn_bind_workspace(nsr::NnParams &P, void *workspace) {
+    const NnLayout L = nn_layout(P.m, P.ncell, P.ncoarse);
+    char *w = static_cast<char *>(workspace);
+    P.sref = reinterpret_cast<double *>(w + L.sref);
+    P.sidx = reinterpret_cast<long long *>(w + L.sidx);
+    P.fstart = reinterpret_cast<int *>(w + L.fstart);
+    P.fend = reinterpret_cast<int *>(w + L.fend);
+    P.cstart = reinterpret_cast<int *>(w + L.cstart);
+    P.cend = reinterpret_cast<int *>(w + L.cend);
+    P.cbox = reinterpret_cast<double *>(w + L.cbox);
+}
+
+inline unsigned nblk(long long n, int tb) { return (unsigned)((n + tb - 1) / tb); }
+
+}  // namespace
+
+extern "C" {
+
+int nsr_nn_bounds(const void *ref, int64_t n_ref, int32_t fp64, double *bounds, void *stream) {
+    if (n_ref < 1) return fail("nsr_nn_bounds: the reference set is empty");
+    if (!ref || !bounds) return fail("nsr_nn_bounds: null pointer");
+    nsr::NnParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.pts = ref; P.n = n_ref; P.fp64 = fp64 ? 1 : 0; P.bounds = bounds;
+    NSR_LAUNCH(nsr::nn_bounds_kernel, dim3(nsr::kNnBoundBlocks), dim3(256), 6 * 256 * 8, stream, P);
+    NSR_LAUNCH(nsr::nn_bounds_final_kernel, dim3(1), dim3(64), 0, stream, P);
+    return finish("nsr_nn_bounds");
+}
+
+int nsr_nn_plan(const double *bounds, int64_t n_ref, double *plan) {
+    if (n_ref < 1 || n_ref >= 2147483647ll) return fail("nsr_nn_plan: the reference set must hold 1 .. 2^31 - 2 points");
+    if (!bounds || !plan) return fail("nsr_nn_plan: null pointer");
+    double ext[3], emax = 0.0, amax = 0.0;
+    for (int d = 0; d < 3; ++d) {
+        if (!std::isfinite(bounds[d]) || !std::isfinite(bounds[3 + d]) || bounds[3 + d] < bounds[d])
+            return fail("nsr_nn_plan: non-finite reference coordinates");
+        ext[d] = bounds[3 + d] - bounds[d];
+        emax = ext[d] > emax ? ext[d] : emax;
+        amax = std::fmax(amax, std::fmax(std::fabs(bounds[d]), std::fabs(bounds[3 + d])));
+    }
+    // about 2 cells per reference point over the extents that are not degenerate (a plane or a line gets a 2-D or 1-D grid)
+    const double target = 2.0 * (double)n_ref, cap = 4.0 * (double)n_ref + 64.0;
+    double prod = 1.0;
+    int k = 0;
+    bool active[3];
+    for (int d = 0; d < 3; ++d) {
+        active[d] = emax > 0.0 && ext[d] > 1e-9 * emax;
+        if (active[d]) { prod *= ext[d]; ++k; }
+    }
+    double h = k ? std::pow(prod / target, 1.0 / k) : 1.0;
+    if (!(h > 0.0) || !std::isfinite(h)) h = emax > 0.0 ? emax : 1.0;
+    double n[3];
+    for (int it = 0;; ++it) {
+        double cells = 1.0;
+        bool fits = true;
+        for (int d = 0; d < 3; ++d) {
+            n[d] = active[d] ? std::fmax(1.0, std::ceil(ext[d] / h)) : 1.0;
+            fits = fits && n[d] <= (double)(1 << 20);
+            cells *= n[d];
+        }
+        if (fits && cells <= cap) break;
+        if (it > 400) return fail("nsr_nn_plan: no grid of O(n_ref) cells covers the reference set");
+        h *= 1.05;
+    }
+    for (int d = 0; d < 3; ++d) {
+        plan[nsr::kNnLo + d] = bounds[d];
+        plan[nsr::kNnHi + d] = bounds[3 + d];
+        plan[nsr::kNnDim + d] = n[d];
+        plan[nsr::kNnCDim + d] = std::ceil(n[d] / nsr::kNnLocal);
+    }
+    plan[nsr::kNnH] = h;
+    plan[nsr::kNnCells] = n[0] * n[1] * n[2];
+    plan[nsr::kNnCoarse] = plan[nsr::kNnCDim] * plan[nsr::kNnCDim + 1] * plan[nsr::kNnCDim + 2];
+    plan[nsr::kNnSlack] = 1e-12 * (amax + emax + h);    // rounding of cell positions and distances, far above the few ulps it covers
+    return 0;
+}
+
+int64_t nsr_nn_workspace_bytes(const double *plan, int64_t n_ref) {
+    nsr::NnParams P;
+    if (!nn_from_plan(P, plan, n_ref)) return -1;
+    return nn_layout(P.m, P.ncell, P.ncoarse).total;
+}
+
+int nsr_nn_keys(const void *pts, int64_t n, int32_t fp64, const double *plan, int64_t *keys, void *stream) {
+    nsr::NnParams P;
+    if (n < 0) return fail("nsr_nn_keys: negative count");
+    if (!nn_from_plan(P, plan, -1)) return fail("nsr_nn_keys: invalid plan");
+    if (n == 0) return 0;
+    if (!pts || !keys) return fail("nsr_nn_keys: null pointer");
+    P.pts = pts; P.n = n; P.fp64 = fp64 ? 1 : 0; P.keys = reinterpret_cast<long long *>(keys);
+    NSR_LAUNCH(nsr::nn_keys_kernel, dim3(nblk(n, 256)), dim3(256), 0, stream, P);
+    return finish("nsr_nn_keys");
+}
+
+int nsr_nn_build(const void *ref, int64_t n_ref, int32_t fp64, const double *plan, const int64_t *sorted_keys, const int64_t *order,
+                 void *workspace, void *stream) {
+    nsr::NnParams P;
+    if (!nn_from_plan(P, plan, n_ref)) return fail("nsr_nn_build: invalid plan for this reference set");
+    if (!ref || !sorted_keys || !order || !workspace) return fail("nsr_nn_build: null pointer");
+    nn_bind_workspace(P, workspace);
+    P.pts = ref; P.n = n_ref; P.fp64 = fp64 ? 1 : 0;
+    P.keys = const_cast<long long *>(reinterpret_cast<const long long *>(sorted_keys));
+    P.order = reinterpret_cast<const long long *>(order);
+    const long long nclear = P.ncell > P.ncoarse ? P.ncell : P.ncoarse;
+    NSR_LAUNCH(nsr::nn_clear_kernel, dim3(nblk(nclear, 256)), dim3(256), 0, stream, P);
+    NSR_LAUNCH(nsr::nn_gather_kernel, dim3(nblk(n_ref, 256)), dim3(256), 0, stream, P);
+    NSR_LAUNCH(nsr::nn_box_kernel, dim3(nblk(P.ncoarse, 64)), dim3(64), 0, stream, P);
+    return finish("nsr_nn_build");
+}
+
+int nsr_nn_query(const void *query, int64_t n_query, int32_t fp64, const int64_t *qorder, const double *plan, const void *workspace,
+                 int64_t n_ref, double *dist, int64_t *idx, int32_t *ncand, void *stream) {
+    nsr::NnParams P;
+    if (n_query < 0) return fail("nsr_nn_query: negative count");
+    if (!nn_from_plan(P, plan, n_ref)) return fail("nsr_nn_query: invalid plan for this reference set");
+    if (n_query == 0) return 0;
+    if (!query || !workspace || !dist || !idx) return fail("nsr_nn_query: null pointer");
+    nn_bind_workspace(P, const_cast<void *>(workspace));
+    P.pts = query; P.n = n_query; P.fp64 = fp64 ? 1 : 0;
+    P.order = reinterpret_cast<const long long *>(qorder);
+    P.dist = dist; P.idx = reinterpret_cast<long long *>(idx); P.ncand = ncand;
+    NSR_LAUNCH(nsr::nn_query_kernel, dim3(nblk(n_query, 64)), dim3(64), 0, stream, P);
+    return finish("nsr_nn_query");
+}
+
+int64_t nsr_sample_workspace_bytes(int64_t nf) {
+    if (nf < 0) return -1;
+    return align16(8 * nf) + 8 * ((nf + nsr::kSurfTile - 1) / nsr::kSurfTile + 1);
+}
+
+int nsr_sample_surface(const double *verts, int64_t nv, const int32_t *faces, int64_t nf, int64_t n, const double *uniforms,
+                       uint64_t seed, void *workspace, double *points, int64_t *face_index, void *stream) {
+    if (nv < 0 || nf < 0 || n < 0) return fail("nsr_sample_surface: negative count");
+    if (nv > 2147483647ll) return fail("nsr_sample_surface: more than 2^31 - 1 vertices");
+    if (n == 0) return 0;
+    if (nf == 0) return fail("nsr_sample_surface: the mesh has no faces");
+    if (!verts || !faces || !workspace || !points || !face_index) return fail("nsr_sample_surface: null pointer");
+    nsr::SurfSampleParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.verts = verts; P.faces = faces; P.nv = nv; P.nf = nf; P.n = n;
+    P.ntiles = (nf + nsr::kSurfTile - 1) / nsr::kSurfTile;
+    P.cum = static_cast<double *>(workspace);
+    P.tile = reinterpret_cast<double *>(static_cast<char *>(workspace) + align16(8 * nf));
+    P.uniforms = uniforms; P.seed = seed; P.points = points; P.face_index = reinterpret_cast<long long *>(face_index);
+    NSR_LAUNCH(nsr::surf_tile_kernel, dim3(nblk(P.ntiles, 64)), dim3(64), 0, stream, P);
+    NSR_LAUNCH(nsr::surf_tile_scan_kernel, dim3(1), dim3(64), 0, stream, P);
+    NSR_LAUNCH(nsr::surf_cum_kernel, dim3(nblk(nf, 256)), dim3(256), 0, stream, P);
+    NSR_LAUNCH(nsr::surf_point_kernel, dim3(nblk(n, 256)), dim3(256), 0, stream, P);
+    return finish("nsr_sample_surface");
+}
+
+int64_t nsr_recon_partial_doubles(int64_t n) {
+    if (n < 0) return -1;
+    return 9 * ((n + nsr::kRedThreads - 1) / nsr::kRedThreads + 1);
+}
+
+int nsr_dist_stats(const double *dist, int64_t n, double th, double *partial, double *out, void *stream) {
+    if (n < 0) return fail("nsr_dist_stats: negative count");
+    if (!partial || !out || (n > 0 && !dist)) return fail("nsr_dist_stats: null pointer");
+    nsr::RedParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.dist = dist; P.n = n; P.th = th; P.partial = partial; P.out = out;
+    P.nblocks = (n + nsr::kRedThreads - 1) / nsr::kRedThreads;
+    if (P.nblocks > 0)
+        NSR_LAUNCH(nsr::reduce_kernel<nsr::kRedDist>, dim3((unsigned)P.nblocks), dim3(nsr::kRedThreads), 2 * nsr::kRedThreads * 8, stream, P);
+    NSR_LAUNCH(nsr::reduce_final_kernel<nsr::kRedDist>, dim3(1), dim3(64), 0, stream, P);
+    return finish("nsr_dist_stats");
+}
+
+int nsr_icp_stats(const double *src, const double *tgt, const int64_t *idx, const double *dist, int64_t n, int64_t n_tgt, double th,
+                  double *partial, double *out, void *stream) {
+    if (n < 0 || n_tgt < 0) return fail("nsr_icp_stats: negative count");
+    if (!partial || !out || (n > 0 && (!src || !tgt || !idx || !dist))) return fail("nsr_icp_stats: null pointer");
+    nsr::RedParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.src = src; P.tgt = tgt; P.idx = reinterpret_cast<const long long *>(idx); P.dist = dist; P.n = n; P.m = n_tgt; P.th = th;
+    P.partial = partial; P.out = out;
+    P.nblocks = (n + nsr::kRedThreads - 1) / nsr::kRedThreads;
+    if (P.nblocks > 0)
+        NSR_LAUNCH(nsr::reduce_kernel<nsr::kRedIcp1>, dim3((unsigned)P.nblocks), dim3(nsr::kRedThreads), 8 * nsr::kRedThreads * 8, stream, P);
+    NSR_LAUNCH(nsr::reduce_final_kernel<nsr::kRedIcp1>, dim3(1), dim3(64), 0, stream, P);
+    if (P.nblocks > 0)
+        NSR_LAUNCH(nsr::reduce_kernel<nsr::kRedIcp2>, dim3((unsigned)P.nblocks), dim3(nsr::kRedThreads), 9 * nsr::kRedThreads * 8, stream, P);
+    NSR_LAUNCH(nsr::reduce_final_kernel<nsr::kRedIcp2>, dim3(1), dim3(64), 0, stream, P);
+    return finish("nsr_icp_stats");
+}
+
+int nsr_transform_points(double *pts, int64_t n, const double *m, void *stream) {
+    if (n < 0) return fail("nsr_transform_points: negative count");
+    if (n == 0) return 0;
+    if (!pts || !m) return fail("nsr_transform_points: null pointer");
+    nsr::XformParams P;
+    P.pts = pts; P.n = n;
+    for (int k = 0; k < 12; ++k) P.m[k] = m[k];
+    NSR_LAUNCH(nsr::transform_points_kernel, dim3(nblk(n, 256)), dim3(256), 0, stream, P);
+    return finish("nsr_transform_points");
+}
+
+int nsr_cull_vertices(const void *verts, int64_t n, int32_t fp64, const float *w2c, int32_t K, int32_t H, int32_t W, double fx,
+                      double fy, double cx, double cy, const int32_t *faces, int64_t nf, uint8_t *seen, uint8_t *keep, void *stream) {
+    if (n < 0 || nf < 0 || K < 0) return fail("nsr_cull_vertices: negative count");
+    if (n > 2147483647ll) return fail("nsr_cull_vertices: more than 2^31 - 1 vertices");
+    if (H < 1 || W < 1) return fail("nsr_cull_vertices: empty image");
+    if ((n > 0 && (!verts || !seen || (K > 0 && !w2c))) || (nf > 0 && (!faces || !keep))) return fail("nsr_cull_vertices: null pointer");
+    nsr::CullParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.verts = verts; P.n = n; P.nf = nf; P.fp64 = fp64 ? 1 : 0; P.K = K; P.w2c = w2c;
+    const double km[9] = {fx, 0.0, cx, 0.0, fy, cy, 0.0, 0.0, 1.0};
+    for (int i = 0; i < 9; ++i) P.kf[i] = (float)km[i];
+    P.W = (float)W; P.H = (float)H; P.faces = faces; P.seen = seen; P.keep = keep;
+    if (n > 0) NSR_LAUNCH(nsr::cull_vertex_kernel, dim3(nblk(n, nsr::kCullThreads)), dim3(nsr::kCullThreads), nsr::kCullChunk * 12 * 4, stream, P);
+    if (nf > 0) NSR_LAUNCH(nsr::cull_face_kernel, dim3(nblk(nf, 256)), dim3(256), 0, stream, P);
+    return finish("nsr_cull_vertices");
 }
 
 }  // extern "C"
