@@ -27,6 +27,45 @@ constexpr int kMaxTiles = 12;            // 12 waves = 768 threads per block
 constexpr int kDefaultBwdBlocks = 256;   // persistent-grid cap of the backward kernels: one block per CU (LDS-bound)
 constexpr int kLdsLimit = 160 * 1024;
 
+// ---- launch policy: one value per choice, each the measured winner (profiles/) ----------------------------------
+// The three NSR_TEST_* hooks let the CPU emulator tests build variants that reach other shapes of the same code
+// (tests/test_emu_parity.py); the library build never defines them.
+#ifndef NSR_TEST_FWD_SMALL
+#define NSR_TEST_FWD_SMALL 1
+#endif
+#ifndef NSR_TEST_HOT_CELLS
+#define NSR_TEST_HOT_CELLS 6
+#endif
+#ifndef NSR_TEST_HOT_SLOTS
+#define NSR_TEST_HOT_SLOTS 512
+#endif
+// Small batches (the tracker's 200 rays): a one-launch forward block runs its decoders one after the other, so with few blocks
+// the launch takes one block's serial chain while most CUs idle.  Fewer rays per block -> one block per CU as long as the batch
+// allows (off: always full 12-tile blocks).
+constexpr bool kFwdSmallBlocks = NSR_TEST_FWD_SMALL != 0;
+// hot-voxel table of a dX block: samples within kHotCells cells of their ray's origin (0: no table), as many slots as the
+// block's LDS has left, at most kHotSlotCap (round 5: 64 slots / 2 cells -> what fits / 6 cells, measured)
+constexpr int kHotCells = NSR_TEST_HOT_CELLS;
+constexpr int kHotSlotCap = NSR_TEST_HOT_SLOTS;
+// dX block deal over the decoder passes by a tile's cost: a pass that owes neither parameter nor ray gradients skips its
+// embedding backward (96 of 240 MFMAs, 24 cosines per lane) -- with equal shares the other passes' blocks set the kernel's length
+// (`--stepped-grads-only`: dX<3> 95 us against 85 with every decoder's gradients); measured 10 / 8 / 7 / 6 / 5 to 10 for a full
+// pass: 92.4 / 85.3 / 82.6 / 79.5 / 80.9 us
+constexpr int kDxFullWeight = 10, kDxLightWeight = 6;
+// dW block deal: the fine decoder's share (the others: 224): its 288 MFMAs per tile against 224 overstate it -- a tile's time has
+// a part that does not scale with the MFMA count (flags, operand reads, sines).  Measured (round 6, log item 22): colour stage
+// 240, fine stage 260.
+constexpr int kDwWeight = 224;
+inline int dw_fine_weight(int stage) { return stage == NSR_STAGE_COLOR ? 240 : 260; }
+// finalize: 512 threads = four resident blocks per CU instead of two was measured: 17.4 vs 15.1 us -- the kernel is a chain of
+// round trips, not a queue of blocks
+constexpr int kFinThreads = 1024;
+// three-launch forward: blocks per decoder pass in proportion to the measured cost of a tile (the fine decoder: 288 MFMAs and two
+// feature gathers against 240 and one), one block per CU over all passes; waves per block from the largest tile share, at most
+// nsr::kDxMaxWaves.  Swept again in round 6: fine stage 12, colour stage 14 against 10 for the others.
+constexpr int kFwdWeight = 10;
+inline int fwd_fine_weight(int stage) { return stage == NSR_STAGE_FINE ? 12 : 14; }
+
 inline int round16(int bytes) { return (bytes + 15) & ~15; }
 
 // forward: up to 12 tiles (768 threads, 3 waves/SIMD, <=168 VGPRs)
@@ -69,12 +108,7 @@ SplitLayout split_layout(int stage, long long n_rays, int S) {
 // fewer waves per block when the batch is small: every CU gets work); the dW kernel `nimg` blocks per pass, each of which
 // leaves one partial image of the gradient blob.
 struct SplitGeo { int nb, waves, nimg; };             // dX: blocks per pass, waves per block; dW: images per pass
-int env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return (e && e[0]) ? atoi(e) : dflt;
-}
 SplitGeo split_geo(int stage, long long n_rays, int S, int max_blocks) {
-    static const int dw_mult = env_int("NSR_DW_BLOCKS_PER_CU", 1);
     SplitGeo G;
     const int passes = bwd_passes(stage);
     const long long tiles = (n_rays * S + nsr::kTile - 1) / nsr::kTile;
@@ -82,12 +116,10 @@ SplitGeo split_geo(int stage, long long n_rays, int S, int max_blocks) {
     int per_pass = cap / passes;
     if (per_pass < 1) per_pass = 1;
     long long w = (tiles + per_pass - 1) / per_pass;
-    static const int wave_cap = env_int("NSR_DX_MAX_WAVES", nsr::kDxMaxWaves);      // (measurement: fewer waves per dX block)
-    const int wcap = wave_cap < 1 ? 1 : (wave_cap > nsr::kDxMaxWaves ? nsr::kDxMaxWaves : wave_cap);
-    G.waves = (int)(w < 1 ? 1 : (w > wcap ? wcap : w));
+    G.waves = (int)(w < 1 ? 1 : (w > nsr::kDxMaxWaves ? nsr::kDxMaxWaves : w));
     const long long nb = (tiles + G.waves - 1) / G.waves;
     G.nb = (int)(nb < 1 ? 1 : (nb > per_pass ? per_pass : nb));
-    long long ni = (long long)per_pass * (dw_mult < 1 ? 1 : dw_mult);
+    long long ni = per_pass;
     if (ni > tiles) ni = tiles;
     G.nimg = (int)(ni < 1 ? 1 : ni);
     return G;
@@ -113,16 +145,10 @@ int build_params(const nsr_render_args *a, nsr::RenderParams &P, bool need_rays,
     }
     P.s_magic = P.S > 1 ? (unsigned)(((1ull << 32) + (unsigned)P.S - 1) / (unsigned)P.S) : 0u;     // (S = 1: nsr_kernels.h::ray_of_point)
     P.rays_per_block = rays_per_block(P.S);
-    if (!bwd) {
-        // Small batches (the tracker's 200 rays): a forward block runs its decoders one after the other, so with few blocks the
-        // launch takes one block's serial chain while most CUs idle.  Fewer rays per block -> one block per CU as long as
-        // the batch allows (NSR_FWD_SMALL=0: always full 12-tile blocks).
-        static const bool small_ok = [] { const char *e = getenv("NSR_FWD_SMALL"); return !(e && e[0] == '0'); }();
-        if (small_ok) {
-            long long want = (P.n_rays + kDefaultBwdBlocks - 1) / kDefaultBwdBlocks;
-            if (want < 1) want = 1;
-            if (want < P.rays_per_block) P.rays_per_block = (int)want;
-        }
+    if (!bwd && kFwdSmallBlocks) {         // (launch policy above)
+        long long want = (P.n_rays + kDefaultBwdBlocks - 1) / kDefaultBwdBlocks;
+        if (want < 1) want = 1;
+        if (want < P.rays_per_block) P.rays_per_block = (int)want;
     }
     P.tiles_per_block = (P.rays_per_block * P.S + nsr::kTile - 1) / nsr::kTile;
     P.n_groups = (P.n_rays + P.rays_per_block - 1) / P.rays_per_block;
@@ -216,8 +242,6 @@ int render_bwd_split(const nsr_render_args *a, const nsr_bwd_args *b, nsr::Rende
     // (the fine decoder's input is [c_fine | c_mid], decoder.py:182-187: its dW reads the middle pass's saved features)
     if (P.dec[NSR_FINE].dparams && (P.acts_masks_only & (1 | 2)))
         return fail("nsr_render_bwd: the forward saved relu masks only for the middle decoder (acts_masks_only), whose features the fine decoder's parameter gradients read");
-    static const int xflags = env_int("NSR_X", 0);
-    P.xflags = xflags;
     if (any_params) {
         const long long need = (long long)passes * ((long long)G.nimg * P.partial_stride + (long long)G.nb * nsr::kDbPart);
         if (!b->workspace || b->workspace_floats < need) return fail("nsr_render_bwd: workspace too small");
@@ -243,42 +267,38 @@ int render_bwd_split(const nsr_render_args *a, const nsr_bwd_args *b, nsr::Rende
             const int need = (nsr::AUX_FLOATS + nsr::packedT_total(kind) + G.waves * nsr::kDxStg + 4) * 4;   // + the tile counter
             lds = need > lds ? need : lds;
         }
-        // hot-voxel table of a dX block: samples within `hot_cells` cells of their ray's origin (NSR_DX_HOT_CELLS, 0: off), as many
-        // slots as the block's LDS has left (NSR_DX_HOT_SLOTS caps it; round 5: 64 slots / 2 cells -> what fits / 6 cells, measured)
-        static const int hot_cells = env_int("NSR_DX_HOT_CELLS", 6), hot_cap = env_int("NSR_DX_HOT_SLOTS", 512);
+        // hot-voxel table of a dX block (launch policy above)
         P.hot_slots = 0;
         if (P.stage != NSR_STAGE_COARSE) {
             int slots = (kLdsLimit - lds) / (nsr::kHotRow * 4);
-            slots = slots > hot_cap ? hot_cap : slots;
+            slots = slots > kHotSlotCap ? kHotSlotCap : slots;
             P.hot_slots = slots < 16 ? 16 : slots;
             lds += P.hot_slots * nsr::kHotRow * 4;
         }
         for (int s = 0; s < 4; ++s) {
             P.hot_z[s] = 0.f;
-            if (s == NSR_COARSE || hot_cells <= 0 || !P.grid[s].dfeat) continue;
+            if (s == NSR_COARSE || kHotCells <= 0 || !P.grid[s].dfeat) continue;
             double cell = 0.0;
             const int nn[3] = {P.grid[s].X, P.grid[s].Y, P.grid[s].Z};
             for (int ax = 0; ax < 3; ++ax) { const double c = nn[ax] > 1 ? P.grid[s].ext[ax] / (nn[ax] - 1) : 0.0; cell = c > cell ? c : cell; }
-            P.hot_z[s] = (float)(hot_cells * cell);
+            P.hot_z[s] = (float)(kHotCells * cell);
         }
         P.lds_grid_floats = 0;
         if (P.stage == NSR_STAGE_COARSE && P.grid[NSR_COARSE].dfeat) {       // a coarse gradient grid that fits next to the rest
             const long long gf = (long long)P.grid[NSR_COARSE].X * P.grid[NSR_COARSE].Y * P.grid[NSR_COARSE].Z * nsr::kC;
             if (lds + gf * 4 <= kLdsLimit) { P.lds_grid_floats = (int)gf; lds += (int)gf * 4; }
         }
-        // the passes * nb blocks dealt over the decoder passes by a tile's cost: a pass that owes neither parameter nor ray gradients skips
-        // its embedding backward (96 of 240 MFMAs, 24 cosines per lane) -- with equal shares the other passes' blocks set the kernel's length
-        // (`--stepped-grads-only`: dX<3> 95 us against 85 with every decoder's gradients); measured 10 / 8 / 7 / 6 / 5 to 10 for a full pass: 92.4 / 85.3 / 82.6 / 79.5 / 80.9 us
-        static const int w_light = env_int("NSR_DX_LIGHT_WEIGHT", 6), w_mid = env_int("NSR_DX_MIDDLE_PCT", 100);
+        // the passes * nb blocks dealt over the decoder passes by a tile's cost (launch policy above)
         {
             const long long tiles = (P.n_points_total + nsr::kTile - 1) / nsr::kTile;
             int wgt[3] = {0, 0, 0}, wsum = 0;
             for (int p = 0; p < passes; ++p) {
                 const int s = P.stage == NSR_STAGE_COARSE ? NSR_COARSE : NSR_MIDDLE + p;
-                wgt[p] = (P.dec[s].dparams || rays || P.stage == NSR_STAGE_COARSE) ? 10 : (w_light < 1 ? 1 : (w_light > 10 ? 10 : w_light));
-                wgt[p] *= (s == NSR_MIDDLE ? w_mid : 100);          // (the middle grid's cells are twice as long: fewer voxel runs per tile)
+                wgt[p] = (P.dec[s].dparams || rays || P.stage == NSR_STAGE_COARSE) ? kDxFullWeight : kDxLightWeight;
                 wsum += wgt[p];
             }
+            // (the blocks sum to at most total = the workspace's d _B partials: a floored share is raised to 1 only where
+            //  total * w / wsum < 1, and with w / wsum <= 10 / 22 for three passes the first two shares never reach total)
             const int total = passes * G.nb;
             int used = 0;
             P.dx_beg[0] = 0;
@@ -309,16 +329,12 @@ int render_bwd_split(const nsr_render_args *a, const nsr_bwd_args *b, nsr::Rende
     if (any_params) {
         const int lds = nsr::dw_lds_bytes(P.stage >= NSR_STAGE_FINE ? NSR_FINE : NSR_MIDDLE);
         // the passes * nimg blocks (= partial images, the workspace's size) dealt over the decoders that want parameter gradients,
-        // in proportion to a tile's measured cost
+        // in proportion to a tile's measured cost (launch policy above)
         const long long tiles = (P.n_points_total + nsr::kTile - 1) / nsr::kTile;
         int wgt[3] = {0, 0, 0}, wsum = 0;
         for (int p = 0; p < passes; ++p) {
             const int s = P.stage == NSR_STAGE_COARSE ? NSR_COARSE : NSR_MIDDLE + p;
-            // the fine decoder's share (the others: 224): its 288 MFMAs per tile against 224 overstate it -- a tile's time has a part that does
-            // not scale with the MFMA count (flags, operand reads, sines).  Measured (round 6, log item 22): colour stage 240, fine stage 260.
-            static const int dw_fine = env_int("NSR_DW_FINE_WEIGHT", 0);
-            const int fine_w = dw_fine > 0 ? dw_fine : (P.stage == NSR_STAGE_COLOR ? 240 : 260);
-            wgt[p] = P.dec[s].dparams ? (s == NSR_FINE ? fine_w : 224) : 0;
+            wgt[p] = P.dec[s].dparams ? (s == NSR_FINE ? dw_fine_weight(P.stage) : kDwWeight) : 0;
             wsum += wgt[p];
         }
         const int total = passes * G.nimg;
@@ -357,9 +373,7 @@ int render_bwd_split(const nsr_render_args *a, const nsr_bwd_args *b, nsr::Rende
             nblocks = nb > nblocks ? nb : nblocks;
         }
         for (int r = rows; r < 3; ++r) R.job[r] = nsr::FinalJob{nullptr, nullptr, nullptr, 0, 0, 0};
-        // (512 threads = four resident blocks per CU instead of two was measured: 17.4 vs 15.1 us -- the kernel is a chain of round trips, not a queue of blocks)
-        static const int fin_threads = env_int("NSR_FIN_THREADS", 1024);
-        NSR_LAUNCH(nsr::bwd_finalize_kernel, dim3(nblocks, rows), dim3(fin_threads), fin_threads * 4, stream, R);
+        NSR_LAUNCH(nsr::bwd_finalize_kernel, dim3(nblocks, rows), dim3(kFinThreads), kFinThreads * 4, stream, R);
     }
     if (b->ev_stop) nsr::rt_record(b->ev_stop, stream);
     return finish("nsr_render_bwd(split)");
@@ -409,29 +423,22 @@ int nsr_render_fwd(const nsr_render_args *a, void *stream) {
 #endif
     if (!a->depth || !a->var || !a->rgb) return fail("nsr_render_fwd: null output pointer");
     if (P.n_rays == 0) return 0;
-    static const int fwd_split = env_int("NSR_FWD_SPLIT", 1);      // 0: always the one-launch kernel (measurement)
     if (a->acts && a->zvals && a->raw) {
-        // a call that hands over an activation buffer (with zvals and raw: without them nsr_render_bwd refuses) will be differentiated: only the three-launch path saves into it, and the
-        // tile / keep arithmetic of the kernels that read it is 32-bit (tile_live, dw_live_mask, split_layout)
-        if (!fwd_split) return fail("nsr_render_fwd: NSR_FWD_SPLIT=0 (the one-launch kernel saves no activations) with an activation buffer: "
-                                    "nsr_render_bwd would read an unwritten buffer");
+        // a call that hands over an activation buffer (with zvals and raw: without them nsr_render_bwd refuses) will be differentiated:
+        // only the three-launch path below saves into it, and the tile / keep arithmetic of the kernels that read it is 32-bit
+        // (tile_live, dw_live_mask, split_layout)
         if (P.n_points_total > (1ll << 25) - 16) return fail("nsr_render_fwd: more than 2^25 sample points in one differentiated call (split the ray batch)");
-    }
-    if (fwd_split && P.acts && P.zvals && P.raw && P.draw) {
-        // a differentiated call with an activation buffer: sample placement -> decoder passes -> compositor (nsr_fwd2.h)
+        // sample placement -> decoder passes -> compositor (nsr_fwd2.h); the block deal: launch policy above
         const int passes = bwd_passes(P.stage), rpb = 4;
-        // blocks per decoder pass in proportion to the measured cost of a tile (the fine decoder: 288 MFMAs and two feature
-        // gathers against 240 and one), one block per CU over all passes; waves per block from the largest tile share
-        static const int w_fine_env = env_int("NSR_FWD_FINE_WEIGHT", 0);
-        const int w_fine = w_fine_env > 0 ? w_fine_env : (P.stage == NSR_STAGE_FINE ? 12 : 14);     // (swept again in round 6: fine stage 12, colour stage 14)
+        const int w_fine = fwd_fine_weight(P.stage);
         const long long tiles = (P.n_points_total + nsr::kTile - 1) / nsr::kTile;
-        const int wsum = passes == 1 ? 10 : (passes == 2 ? 10 + w_fine : 20 + w_fine);
+        const int wsum = passes == 1 ? kFwdWeight : (passes == 2 ? kFwdWeight + w_fine : 2 * kFwdWeight + w_fine);
         long long most = 1;
         P.pass_beg[0] = 0;
         for (int p = 0; p < 3; ++p) {
             int nbp = 0;
             if (p < passes) {
-                nbp = (int)((long long)kDefaultBwdBlocks * (p == 1 ? w_fine : 10) / wsum);
+                nbp = (int)((long long)kDefaultBwdBlocks * (p == 1 ? w_fine : kFwdWeight) / wsum);
                 if (nbp > tiles) nbp = (int)tiles;
                 if (nbp < 1) nbp = 1;
                 const long long share = (tiles + nbp - 1) / nbp;
@@ -439,9 +446,7 @@ int nsr_render_fwd(const nsr_render_args *a, void *stream) {
             }
             P.pass_beg[p + 1] = P.pass_beg[p] + nbp;
         }
-        static const int fwd_cap = env_int("NSR_FWD_MAX_WAVES", nsr::kDxMaxWaves);   // (measurement: fewer waves per pass-kernel block)
-        const int fcap = fwd_cap < 1 ? 1 : (fwd_cap > nsr::kDxMaxWaves ? nsr::kDxMaxWaves : fwd_cap);
-        const int waves = (int)(most > fcap ? fcap : most);
+        const int waves = (int)(most > nsr::kDxMaxWaves ? nsr::kDxMaxWaves : most);
         const dim3 rgrid((unsigned)((P.n_rays + rpb - 1) / rpb)), rblock(64 * rpb);
         NSR_LAUNCH(nsr::fwd_sample_kernel, rgrid, rblock, rpb * 64 * 8, stream, P);
         int lds = 0;
@@ -468,16 +473,16 @@ int nsr_render_fwd(const nsr_render_args *a, void *stream) {
     const int npts = P.rays_per_block * P.S;
     const int lds = fwd_lds_bytes(P.stage, npts);
     const dim3 grid((unsigned)(P.n_groups < (1 << 20) ? P.n_groups : (1 << 20))), block(64 * P.tiles_per_block);
-#define NSR_FWD(ST, SV)                                                                               \
-    if (int rc = launch_cfg(nsr::render_fwd_kernel<ST, SV>, lds, "nsr_render_fwd")) return rc;         \
-    NSR_LAUNCH((nsr::render_fwd_kernel<ST, SV>), grid, block, lds, stream, P);
+#define NSR_FWD(ST)                                                                               \
+    if (int rc = launch_cfg(nsr::render_fwd_kernel<ST>, lds, "nsr_render_fwd")) return rc;         \
+    NSR_LAUNCH((nsr::render_fwd_kernel<ST>), grid, block, lds, stream, P);
     // (the one-launch kernel saves nothing: a call that will be differentiated passes acts + zvals + raw and took the branch above)
     P.acts = nullptr;
     switch (P.stage) {
-        case 0: NSR_FWD(0, false) break;
-        case 1: NSR_FWD(1, false) break;
-        case 2: NSR_FWD(2, false) break;
-        default: NSR_FWD(3, false) break;
+        case 0: NSR_FWD(0) break;
+        case 1: NSR_FWD(1) break;
+        case 2: NSR_FWD(2) break;
+        default: NSR_FWD(3) break;
     }
 #undef NSR_FWD
     return finish("nsr_render_fwd");

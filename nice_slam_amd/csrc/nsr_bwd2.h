@@ -101,7 +101,7 @@ NSR_DEV void gemv_t(f32x4 (&dx)[NTK], const Act<2> &dy, const float *wt, int lan
 #pragma unroll
             for (int Tk = 0; Tk < NTK; ++Tk) dx[Tk] = mfma16(a[Tk][r], dy.t[To][r], dx[Tk]);
     }
-    sched_fence_gemv();
+    sched_fence();
 }
 
 // What a tile's layers need first: d raw and the relu masks.  Requested one tile ahead and handed over RAW -- anything computed on
@@ -146,9 +146,7 @@ NSR_DEV void dx_pass(const RenderParams &P, int bi, int nbp, int gb) {
     const bool use_hot = KIND != NSR_COARSE && P.hot_z[KIND] > 0.f && P.grid[KIND].dfeat != nullptr;
     const HotTab hot{use_hot ? tail_off : -1, P.hot_slots};
     // Tiles: block i of the n of a pass owns the contiguous range [T i / n, T (i + 1) / n) and its waves draw from it through
-    // an LDS counter (a wave whose tile was cheap takes the next one: no rounds); NSR_X bit 7: the static deal tile = block *
-    // waves + wave, + blocks * waves, ... of the first version (measurement).
-    const bool dyn = !(P.xflags & 128);
+    // an LDS counter (a wave whose tile was cheap takes the next one: no rounds).
     int *tcnt = reinterpret_cast<int *>(stg + nw * kDxStg + (KIND == NSR_COARSE ? P.lds_grid_floats : P.hot_slots * kHotRow));
     const GridDev &G = P.grid[KIND];
     const DecDev &D = P.dec[KIND];
@@ -159,20 +157,16 @@ NSR_DEV void dx_pass(const RenderParams &P, int bi, int nbp, int gb) {
     constexpr long long sstride = 256;                       // floats between two slots of a tile
     const float *acts_pass = P.acts + (long long)act_pass(KIND) * P.act_tiles * kActSlots * 256;
     const long long ntiles = (P.n_points_total + kTile - 1) / kTile;
-    const long long t0 = dyn ? ntiles * bi / nbp : 0, tend = dyn ? ntiles * (bi + 1) / nbp : ntiles;
+    const long long t0 = ntiles * bi / nbp, tend = ntiles * (bi + 1) / nbp;
     // A wave's FIRST tile is dealt statically (range start + wave; the counter starts behind them) and its inputs are requested here,
     // in front of the operand staging: they land under the 64 KB copy instead of being waited for behind the barrier (round 6: ~2 us
     // of every launch).  A first tile without a ray of the batch (pre-filter) falls back to the counter.
-    long long tile = dyn ? t0 + wave : (long long)bi * nw + wave;
-    const bool pre = tile < tend && (!dyn || tile_live(P, tile));
+    long long tile = t0 + wave;
+    const bool pre = tile < tend && tile_live(P, tile);
     DxIn cur;
     if (pre) cur = dx_load(P, acts_pass, tile, pt, g);
     copy_f4<AUX_FLOATS / 4>(aux, D.packed);
-#if defined(NSR_X_DX_STAGE_COPY)             // A/B build: the transposed stream through registers (rounds 2-5)
-    copy_f4<packedT_total(KIND) / 4>(wt, D.packed + AUX_FLOATS + packed_total(KIND));
-#else
     copy_f4_dma<packedT_total(KIND) / 4>(wt, D.packed + AUX_FLOATS + packed_total(KIND));
-#endif
     if (gl) for (int i = tid(); i < P.lds_grid_floats; i += nthreads()) gl[i] = 0.f;
     if (use_hot) hot_init(hot);
     if (tid() == 0) tcnt[0] = nw;
@@ -180,7 +174,6 @@ NSR_DEV void dx_pass(const RenderParams &P, int bi, int nbp, int gb) {
     block_sync();
     dbg.stamp(1);
     float *dys = P.dy + (long long)act_pass(KIND) * P.act_tiles * kDySlots * 256;
-    const long long tstep = (long long)nbp * nw;
     const bool need_dc = do_grid || RAYS;
     float aB[kET][3];                                        // d _B partial sums of lane (channel j, point group)
 #pragma unroll
@@ -196,7 +189,7 @@ NSR_DEV void dx_pass(const RenderParams &P, int bi, int nbp, int gb) {
     };
     // d raw written by the forward's loss epilogue: the incoming gradient applies here (one uniform scalar, read once)
     const float dr_scale = (!P.draw_scaled && P.g_scale) ? (float)P.g_scale[0] : 1.f;
-    if (!pre && dyn) {
+    if (!pre) {
         tile = claim();
         if (tile < tend) cur = dx_load(P, acts_pass, tile, pt, g);
     }
@@ -208,7 +201,7 @@ NSR_DEV void dx_pass(const RenderParams &P, int bi, int nbp, int gb) {
         // tile's first inputs (d raw, masks) are requested now and waited for (dx_keep) before this tile's atomics are issued;
         // this tile's positions are requested now as well and first used behind the layers, by when the previous tile's
         // atomics have drained.
-        const long long nxt = dyn ? claim() : tile + tstep;
+        const long long nxt = claim();
         const bool has_next = nxt < tend;
         DxIn nx = cur;
         if (has_next) nx = dx_load(P, acts_pass, nxt, pt, g);
@@ -242,7 +235,7 @@ NSR_DEV void dx_pass(const RenderParams &P, int bi, int nbp, int gb) {
         for (int I = 4; I >= 0; --I) {
             if (XYZ && need_dc) gemv_t<2>(dc.t, dh, wt + xyzT_u(I), lane);         // gradient of (U_i c + v_i) is dh itself
             const Act<2> dY = apply_mask(dh, I < 4 ? mw0 : mw1, I < 4 ? 8 * I : 0);
-            if (PARAMS && active && !(P.xflags & 2)) {
+            if (PARAMS && active) {
                 st4(dyp + (2 * I) * sstride, to_F4(dY.t[0]));
                 st4(dyp + (2 * I + 1) * sstride, to_F4(dY.t[1]));
             }
@@ -264,7 +257,9 @@ NSR_DEV void dx_pass(const RenderParams &P, int bi, int nbp, int gb) {
         dbg.stamp(3);
         const float px = (float)cpx, py = (float)cpy, pz = (float)cpz;       // decoder.py:189
         float dpe[3] = {0.f, 0.f, 0.f};
-        if (XYZ && PARAMS && !(P.xflags & 4)) {
+        // (every tile of the loop holds a point, so the guard is always true: it keeps this block a basic block of its own -- straight-line,
+        //  the compiler hoists its lane-dependent addresses out of the tile loop and spills them, dX<3, false> 155 -> 168 VGPRs + 108 B of scratch)
+        if (XYZ && PARAMS && ballot64(active) != 0ull) {
             // "lane = channel" form: swapping the MFMA operands (A = dY registers, B = transposed stream) yields
             // dE[point 4 g + r][channel 16 Tk + j] in lane (j, g) -- the layout the contraction over points for d _B needs
             if (g == 0) { Sw[kDxP + pt] = px; Sw[kDxP + 16 + pt] = py; Sw[kDxP + 32 + pt] = pz; }
@@ -284,7 +279,7 @@ NSR_DEV void dx_pass(const RenderParams &P, int bi, int nbp, int gb) {
                         e3 = mfma16(dY3.t[To][r], a3[r], e3);
                     }
                 }
-                sched_fence_emb();
+                sched_fence();
                 const F4 b = load_b1(aux, 16 * Tk + pt);
                 const f32x4 darg = (e0 + e3) * cos_dx4(vfma(qz, splat(b.z), vfma(qy, splat(b.y), qx * splat(b.x))));
 #pragma unroll
@@ -318,7 +313,7 @@ NSR_DEV void dx_pass(const RenderParams &P, int bi, int nbp, int gb) {
                 const f32x4 darg = dE[Tk] * cos_dx4(vfma(splat(pz), b.z, vfma(splat(py), b.y, splat(px) * b.x)));
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { ax = fmaf(darg[r], b.x[r], ax); ay = fmaf(darg[r], b.y[r], ay); az = fmaf(darg[r], b.z[r], az); }
-                sched_fence_emb();
+                sched_fence();
             }
             dpe[0] = red_g(ax); dpe[1] = red_g(ay); dpe[2] = red_g(az);
         }
@@ -336,7 +331,7 @@ NSR_DEV void dx_pass(const RenderParams &P, int bi, int nbp, int gb) {
         // loop header costs an `s_waitcnt vmcnt(0)` there, i.e. a wait for the whole tile's atomics)
         keep_alive_d(cpx); keep_alive_d(cpy); keep_alive_d(cpz); keep_alive_d(cz);
         dbg.stamp(5);
-        if (do_grid && !(P.xflags & 1))
+        if (do_grid)
             scatter_merged(G, L, lane, dc, active, Sw + kDxTx, Sw + kDxTab, gl_off, hot, (float)cz < P.hot_z[KIND], live);
         dbg.stamp(6);
         if (RAYS) {
@@ -477,7 +472,6 @@ NSR_DEV DwSrc dw_src(const float *slot) {
 template <int KIND>
 NSR_DEV void dw_issue(const RenderParams &P, long long tile, float *slot, int lane) {
     typedef DwLay<KIND> Y;
-    if (P.xflags & 16) tile &= 3;                                 // measurement: operands from cache-resident tiles
     // a tile's dY (10 KB) and its hidden states + features (12 KB) are contiguous spans in memory: piece n = the n-th KB
     const float *dt = P.dy + ((long long)act_pass(KIND) * P.act_tiles + tile) * (kDySlots * 256);
     const float *at = P.acts + ((long long)act_pass(KIND) * P.act_tiles + tile) * (kActSlots * 256);
@@ -614,11 +608,7 @@ struct DwXyzWave {
             f32x4 qx, qy, qz;
 #pragma unroll
             for (int q = 0; q < 4; ++q) { qx[q] = o.pos[q].x; qy[q] = o.pos[q].y; qz[q] = o.pos[q].z; }
-#if defined(NSR_X_DW_NOSIN)              // A/B build (tools/build_ts.sh): what the sines cost this kernel (wrong numbers, timing only)
-            e = vfma(qz, splat(bz), vfma(qy, splat(by), qx * splat(bx)));
-#else
             e = sin_dw4(vfma(qz, splat(bz), vfma(qy, splat(by), qx * splat(bx))));     // decoder.py:29-30
-#endif
             if (kB0) { vb0[0] += sum4(o.y[0]); vb0[1] += sum4(o.y[1]); }
         }
         if (WJ) vb += sum4(o.a1);
@@ -899,7 +889,6 @@ NSR_DEV void dw_compute(const RenderParams &P, W &Wv, float *ring, int *ctl, flo
     typedef DwLay<KIND> Y;
     Wv.init(P, lane & 15);
     const long long ntiles = (P.n_points_total + kTile - 1) / kTile;
-    const long long ntl = (P.xflags & 64) ? 0 : ntiles;             // measurement: no tiles (prologue + flush only)
     const long long last = ntiles - 1, step = nbp;
     const int ragged = (int)(P.n_points_total & (kTile - 1));
     // (Requesting tile k + 1's operands into a second register set before tile k's MFMAs -- the two waves of a SIMD wait for
@@ -910,7 +899,7 @@ NSR_DEV void dw_compute(const RenderParams &P, W &Wv, float *ring, int *ctl, flo
     unsigned long long lm = ~0ull;
     const Dbg dbg{P.dbg ? P.dbg + kDwDbgOff + ((long long)bid_x() * kDxMaxWaves + wave) * 64 : nullptr};   // (-DNSR_TS builds: tests/perf/ts_dw.py)
     dbg.stamp(0);
-    for (long long t = bi; t < ntl; t += step, ++k) {
+    for (long long t = bi; t < ntiles; t += step, ++k) {
         loop_fence();
         dbg.stamp(1);
         if ((k & 63) == 0) lm = dw_live_mask(P, bi, step, k >> 6, ntiles, lane);
@@ -944,13 +933,13 @@ template <int KIND>
 NSR_DEV void dw_loader(const RenderParams &P, float *ring, int *ctl, int j, int lane, int bi, int nbp) {
     typedef DwLay<KIND> Y;
     const long long ntiles = (P.n_points_total + kTile - 1) / kTile;
-    const long long step = nbp, ntl = (P.xflags & 64) ? 0 : ntiles;
+    const long long step = nbp;
     int m = 0;                                                               // this loader's m-th tile is the block's tile 2 m + j
     unsigned long long lm = ~0ull;
     int chunk = -1;
     const Dbg dbg{P.dbg ? P.dbg + kDwDbgOff + ((long long)bid_x() * kDxMaxWaves + kDwCompute + j) * 64 : nullptr};
     dbg.stamp(0);
-    for (long long t = bi + j * step; t < ntl; t += kDwLoaders * step, ++m) {
+    for (long long t = bi + j * step; t < ntiles; t += kDwLoaders * step, ++m) {
         loop_fence();
         dbg.stamp(1);
         const int k = kDwLoaders * m + j;

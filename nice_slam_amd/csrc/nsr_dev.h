@@ -35,7 +35,6 @@ NSR_DEV int nblk_x() { return (int)gridDim.x; }
 NSR_DEV unsigned long long ballot64(bool p) { return __ballot(p); }            // bit l = lane l's predicate
 NSR_DEV float shfl(float v, int src) { return __shfl(v, src, 64); }
 NSR_DEV int shfl_i(int v, int src) { return __shfl(v, src, 64); }
-NSR_DEV double shfl_d(double v, int src) { return __shfl(v, src, 64); }
 NSR_DEV float shfl_xor(float v, int m) { return __shfl_xor(v, m, 64); }
 NSR_DEV double shfl_xor_d(double v, int m) { return __shfl_xor(v, m, 64); }
 NSR_DEV float shfl_up(float v, int d) { return __shfl_up(v, (unsigned)d, 64); }
@@ -49,17 +48,6 @@ NSR_DEV void wave_fence() {
 }
 // keep the instruction scheduler from hoisting the next operand stream above this point
 NSR_DEV void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
-// the same at sites that A/B builds may switch off (tools/build_ts.sh -DNSR_X_NOFENCE_GEMV / -DNSR_X_NOFENCE_EMB)
-NSR_DEV void sched_fence_gemv() {
-#ifndef NSR_X_NOFENCE_GEMV
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-}
-NSR_DEV void sched_fence_emb() {
-#ifndef NSR_X_NOFENCE_EMB
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-}
 // keep a loaded value (and thereby its load) alive up to this point without doing anything with it
 NSR_DEV void keep_alive(float v) { asm volatile("" ::"v"(v)); }
 NSR_DEV void keep_alive_d(double v) { asm volatile("" ::"v"(v)); }
@@ -102,14 +90,6 @@ struct Dbg {
     }
 };
 
-// Pull the 64-byte line of `p` towards the L2 without a destination register: a global -> LDS load (gfx950
-// global_load_lds_dword) into a sink region nobody reads.  A plain load kept alive in a VGPR gets spilled by the register
-// allocator of the backward kernel -- `s_waitcnt vmcnt(0)` + scratch store right behind every such load, i.e. the full memory
-// latency eight times in a row (measured: 6.7k cycles per tile).
-NSR_DEV void prefetch_line(const float *p, float *lds_sink) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)p,
-                                     (__attribute__((address_space(3))) void *)lds_sink, 4, 0, 0);
-}
 // 16 bytes per lane, global -> LDS without a destination register (gfx950 global_load_lds_dwordx4): lane l's bytes land at
 // lds_base + 16 l, i.e. one wave instruction moves 1 KB; completion is tracked by the vector-memory counter (dma_wait).
 NSR_DEV void dma16(const float *gsrc, float *lds_base, int /*lane*/) {
@@ -167,7 +147,6 @@ NSR_DEV int atomic_cas_lds_i(int *p, int expect, int v) {      // returns the ol
 }
 // plain LDS accesses through a pointer whose provenance the compiler has lost (table pointers handed around in structs)
 NSR_DEV int lds_load_i(const int *p) { return *(const volatile lds_int *)p; }
-NSR_DEV float lds_load_f(const float *p) { return *(const nsr_lfloat *)p; }
 NSR_DEV void atomic_add_global_d(double *p, double v) {
     __hip_atomic_fetch_add((nsr_gdouble *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -203,24 +182,6 @@ NSR_DEV unsigned uniform_load_u8(const unsigned char *p) {
 NSR_DEV char *lds_base() {
     extern __shared__ __attribute__((aligned(16))) char nsr_lds_[];
     return nsr_lds_;
-}
-
-// Operand streams (packed weights / flat parameter blob) are read with buffer loads: the 128-bit
-// descriptor and the per-load offset live in SGPRs, the lane offset is ONE shared VGPR -- the
-// 64-bit per-row address pairs a plain pointer walk needs would otherwise eat >150 VGPRs.
-struct Stream { __amdgpu_buffer_rsrc_t rsrc; };
-NSR_DEV Stream make_stream(const float *base) {
-    Stream s;
-    s.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7fffffff, 0x00020000);
-    return s;
-}
-// value at base[lane_off + const_off]   (offsets in floats; const_off is wave-uniform)
-NSR_DEV float stream_ld(const Stream &s, int lane_off, int const_off) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(s.rsrc, lane_off * 4, const_off * 4, 0));
-}
-
-NSR_DEV void stream_st(const Stream &s, int lane_off, int const_off, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), s.rsrc, lane_off * 4, const_off * 4, 0);
 }
 
 NSR_DEV F4 ld4(const float *p) { float4 v = *reinterpret_cast<const float4 *>(p); return F4{v.x, v.y, v.z, v.w}; }

@@ -135,7 +135,7 @@ NSR_DEV void fwd_pass(const RenderParams &P, int bi, int nbp) {
             const Act<2> c = gather_feat(P.grid[NSR_COARSE], L, g);
             float o[1];
             const ActSink sk = act_sink(P, 0, sp, g);
-            mlp_nox_fwd<false, SAVE>(wl, aux, c, lane, o, nullptr, &sk);
+            mlp_nox_fwd<SAVE>(wl, aux, c, lane, o, &sk);
             if (active && g == 0) scr[0] = o[0];
         } else {
             const float fx = (float)px, fy = (float)py, fz = (float)pz;     // decoder.py:189
@@ -144,7 +144,7 @@ NSR_DEV void fwd_pass(const RenderParams &P, int bi, int nbp) {
                 const Act<2> cm = gather_feat(P.grid[NSR_MIDDLE], Lm, g);
                 float om[1];
                 const ActSink sk = act_sink(P, 0, sp, g);
-                mlp_xyz_fwd<NSR_MIDDLE, false, SAVE>(wl, aux, fx, fy, fz, cm, lane, om, nullptr, &sk);
+                mlp_xyz_fwd<NSR_MIDDLE, SAVE>(wl, aux, fx, fy, fz, cm, lane, om, &sk);
                 if (active && g == 0) scr[0] = om[0];
             } else if (KIND == NSR_FINE) {
                 const Lvl Lf = make_level(P.grid[NSR_FINE], px, py, pz);
@@ -155,14 +155,14 @@ NSR_DEV void fwd_pass(const RenderParams &P, int bi, int nbp) {
                 cc.t[0] = cf.t[0]; cc.t[1] = cf.t[1]; cc.t[2] = cm.t[0]; cc.t[3] = cm.t[1];    // decoder.py:182-187
                 float of[1];
                 const ActSink sk = act_sink(P, 1, sp, g);
-                mlp_xyz_fwd<NSR_FINE, false, SAVE>(wl, aux, fx, fy, fz, cc, lane, of, nullptr, &sk);
+                mlp_xyz_fwd<NSR_FINE, SAVE>(wl, aux, fx, fy, fz, cc, lane, of, &sk);
                 if (active && g == 0) scr[1] = of[0];
             } else {
                 const Lvl Lc = make_level(P.grid[NSR_COLOR], px, py, pz);
                 const Act<2> ccol = gather_feat(P.grid[NSR_COLOR], Lc, g);
                 float oc[4];
                 const ActSink sk = act_sink(P, 2, sp, g);
-                mlp_xyz_fwd<NSR_COLOR, false, SAVE>(wl, aux, fx, fy, fz, ccol, lane, oc, nullptr, &sk);
+                mlp_xyz_fwd<NSR_COLOR, SAVE>(wl, aux, fx, fy, fz, ccol, lane, oc, &sk);
                 if (active && g == 0) { float *rw = P.raw + gp * 4; rw[0] = oc[0]; rw[1] = oc[1]; rw[2] = oc[2]; }
             }
         }

@@ -97,7 +97,6 @@ struct RenderParams {
     int dw_beg[4];            // dW kernel: blocks [dw_beg[p], dw_beg[p + 1]) = partial images of decoder pass p
     int dx_beg[4];            // dX kernel: blocks [dx_beg[p], dx_beg[p + 1]) work on decoder pass p (dealt by the passes' tile cost)
     int draw_scaled;          // 1: `draw` already carries nsr_bwd_args.grad_scale (comp_bwd_kernel ran); 0: the forward wrote it
-    int xflags;               // measurement switches (NSR_X environment variable; 0 in normal operation)
     int skip_masked;          // 1 (with keep): rays with keep == 0 are not part of the batch (nsr_render_args.skip_masked)
     int lds_grid_floats;      // > 0 (coarse stage): the gradient grid (this many floats) is accumulated in the dX block's LDS
     float hot_z[4];           // dX kernel, per grid: samples with z below it use the block's hot-voxel table (0: no table)
@@ -370,32 +369,6 @@ NSR_DEV Act<2> gather_feat(const GridDev &G, const Lvl &L, int g) {
     return c;
 }
 
-// the same in two halves, so that the 16 loads can be issued long before their values are needed
-struct GatherRaw { F4 a[8], b[8]; };
-NSR_DEV void gather_issue(GatherRaw &R, const GridDev &G, const Lvl &L, int g) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float *src = G.feat + (long long)corner_vox(L, k) * kC + 4 * g;
-        R.a[k] = ld4(src);
-        R.b[k] = ld4(src + 16);
-    }
-}
-NSR_DEV Act<2> gather_finish(const GatherRaw &R, const Lvl &L) {
-    Act<2> c;
-    c.t[0] = f4zero();
-    c.t[1] = f4zero();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float w = corner_w(L, k);
-        const F4 a = R.a[k], b = R.b[k];
-        c.t[0][0] = fmaf(a.x, w, c.t[0][0]); c.t[0][1] = fmaf(a.y, w, c.t[0][1]);
-        c.t[0][2] = fmaf(a.z, w, c.t[0][2]); c.t[0][3] = fmaf(a.w, w, c.t[0][3]);
-        c.t[1][0] = fmaf(b.x, w, c.t[1][0]); c.t[1][1] = fmaf(b.y, w, c.t[1][1]);
-        c.t[1][2] = fmaf(b.z, w, c.t[1][2]); c.t[1][3] = fmaf(b.w, w, c.t[1][3]);
-    }
-    return c;
-}
-
 // per-wave transposition buffers: Tx[pt][kTxS]
 NSR_DEV void tx_store(float *Tx, const Act<2> &v, int pt, int g) {
     st4(Tx + pt * kTxS + 4 * g, to_F4(v.t[0]));
@@ -545,13 +518,7 @@ NSR_DEV void scatter_walk(const GridDev &G, int lane, const float *Tx, const flo
                 if (lds_grid >= 0) atomic_add_lds(reinterpret_cast<float *>(lds_base()) + lds_grid + v[p] * kC + ch, s);
                 else if (v[p] & kHotBit) atomic_add_lds(reinterpret_cast<float *>(lds_base()) + hv_off + (v[p] & (kHotBit - 1)), s);
                 else {
-#if defined(NSR_X_SCATTER_STORE)         // A/B build: plain stores to the same addresses (what the vector-memory path costs without the atomic)
-                    G.dfeat[(long long)v[p] * kC + ch] = s;
-#elif defined(NSR_X_SCATTER_HALF)        // A/B build: one of the two 64-byte lines of every voxel row
-                    if (ch < 16) atomic_add_global_off(G.dfeat, ((unsigned)v[p] << 7) + ((unsigned)ch << 2), s);
-#else
                     atomic_add_global_off(G.dfeat, ((unsigned)v[p] << 7) + ((unsigned)ch << 2), s);      // (a grid is < 2^25 voxels = 4 GB: nsr_api.cpp)
-#endif
                 }
                 s = 0.f;                          // the next run of this half's class starts here
             }
@@ -598,7 +565,7 @@ NSR_DEV void gemv_fwd(f32x4 (&acc)[2], const Act<NT> &x, const float *pk, int la
             rb[T % kD] = to_v(ld4(pk + ((T + kD) * 128 + 64 + lane) * 4));
         }
     }
-    sched_fence_gemv();
+    sched_fence();
 }
 
 // cooperative copy of a decoder's packed operand stream into LDS (caller provides the barriers)
@@ -629,15 +596,6 @@ NSR_DEV f32x4 sin_poly4(f32x4 r, u32x4 t) {
 }
 // quotient by the "1.5 * 2^23" trick: t = x/pi + 12582912 has round(x/pi) in its low mantissa bits (|x| < 1e7), so
 // its parity is bit 0 of the float and no float->int conversion / compare / select is needed for the sign
-#if defined(NSR_X_LIBM_SIN)
-// CPU emulator A/B only (tests/perf/parity_causes.py): correctly rounded sines -- how much of a parity miss is the kernels' own sine?
-// NSR_X_LIBM_SIN = 1: every sine / cosine; 2: the forward's embedding only; 3: the dW kernel's re-evaluation only; 4: the dX kernel's cosines only
-}  // namespace nsr
-#include <cmath>
-namespace nsr {
-NSR_DEV f32x4 sin_libm4(f32x4 x) { f32x4 r; for (int i = 0; i < 4; ++i) r[i] = (float)std::sin((double)x[i]); return r; }
-NSR_DEV f32x4 cos_libm4(f32x4 x) { f32x4 r; for (int i = 0; i < 4; ++i) r[i] = (float)std::cos((double)x[i]); return r; }
-#endif
 NSR_DEV f32x4 sin_acc4(f32x4 x) {
     const f32x4 t = vfma(x, splat(0.318309886183790672f), splat(12582912.f));
     const f32x4 k = t - splat(12582912.f);
@@ -655,15 +613,10 @@ NSR_DEV f32x4 cos_acc4(f32x4 x) {
     return sin_poly4(r, ~__builtin_bit_cast(u32x4, t));
 }
 // the three places a Fourier feature is evaluated: the forward's embedding, the dW kernel's re-evaluation of it, the dX kernel's cosines
-#if defined(NSR_X_LIBM_SIN)
-NSR_DEV f32x4 sin_fwd4(f32x4 x) { return (NSR_X_LIBM_SIN == 1 || NSR_X_LIBM_SIN == 2) ? sin_libm4(x) : sin_acc4(x); }
-NSR_DEV f32x4 sin_dw4(f32x4 x) { return (NSR_X_LIBM_SIN == 1 || NSR_X_LIBM_SIN == 3) ? sin_libm4(x) : sin_acc4(x); }
-NSR_DEV f32x4 cos_dx4(f32x4 x) { return (NSR_X_LIBM_SIN == 1 || NSR_X_LIBM_SIN == 4) ? cos_libm4(x) : cos_acc4(x); }
-#else
 // The FORWARD's embedding sine in fp64 (round 6).  At ScanNet-size bounds (|p.B| ~ 1e3 rad) every gradient tensor of the path is a
 // heavily cancelling sum: the fp32 reference itself sits 1e-2 from an fp64 evaluation, and matching IT to 1e-4 means matching the
-// rounding of its per-element values.  Measured with these sources under the CPU emulator (tests/perf/parity_causes.py ->
-// profiles/r06_parity_causes.json, scannet/fine, 5000 rays): with the packed fp32 sine above (abs err 1.5e-7, i.e. one ulp off a
+// rounding of its per-element values.  Measured with these sources under the CPU emulator (profiles/r06_parity_causes.json,
+// scannet/fine, 5000 rays): with the packed fp32 sine above (abs err 1.5e-7, i.e. one ulp off a
 // correctly rounded sine for a good share of the arguments) 31 of 50 gradient tensors miss 1e-4 (max 1.82e-4 -- the GPU's numbers);
 // with a correctly rounded sine in the forward's embedding ALONE none does (max 7.9e-5), and the dW kernel's re-evaluation and the
 // dX kernel's cosines do not matter at all.  fp64 vector operations issue at the unpacked fp32 rate on gfx950: ~16 operations per
@@ -686,18 +639,13 @@ NSR_DEV float sin_f64(float x) {
     return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, s) ^ sign);
 }
 NSR_DEV f32x4 sin_fwd4(f32x4 x) {
-#if defined(NSR_X_FWD_SIN_F32)               // A/B build (tools/build_ts.sh): the packed fp32 sine in the forward, as until round 5 -- what the fp64 one costs
-    return sin_acc4(x);
-#else
     f32x4 r;
 #pragma unroll
     for (int i = 0; i < 4; ++i) r[i] = sin_f64(x[i]);
     return r;
-#endif
 }
 NSR_DEV f32x4 sin_dw4(f32x4 x) { return sin_acc4(x); }
 NSR_DEV f32x4 cos_dx4(f32x4 x) { return cos_acc4(x); }
-#endif
 // Fourier matrix rows of four consecutive channels (group = channel / 4): Bx[4], By[4], Bz[4]
 struct B4 { f32x4 x, y, z; };
 NSR_DEV B4 load_b4(const float *aux, int group) {
@@ -754,18 +702,13 @@ NSR_DEV void embed(Act<kET> &e, const float *aux, float px, float py, float pz, 
         const B4 b = load_b4(aux, 4 * T + g);
         const f32x4 arg = vfma(splat(pz), b.z, vfma(splat(py), b.y, splat(px) * b.x));     // decoder.py:29
         e.t[T] = sin_fwd4(arg);                                                            // decoder.py:30
-        sched_fence_emb();                  // bound the ILP the scheduler extracts from 24 independent sines
+        sched_fence();                  // bound the ILP the scheduler extracts from 24 independent sines
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// decoder forward for one tile.  KEEP keeps what the backward needs (h_i and relu masks).
+// decoder forward for one tile
 // ------------------------------------------------------------------------------------------------
-template <int KIND>
-struct Kept {
-    Act<2> h[5];
-    unsigned mask[5];
-};
 
 // Saved activations (288 GB of HBM buy the backward its forward re-run): per decoder pass p (middle 0, fine 1, colour 2; the
 // coarse decoder uses pass 0) and 16-point tile T of the flat sample-point list, 13 slots of 1 KB:
@@ -792,11 +735,10 @@ NSR_DEV ActSink act_sink(const RenderParams &P, int pass, long long gp, int g) {
 NSR_DEV int act_pass(int kind) { return kind == NSR_COARSE ? 0 : kind - NSR_MIDDLE; }
 
 // MLP (decoder.py:177-203): h_i = relu(W_i x_i + b_i) + (U_i c + v_i), x_3 = [e | h_2]
-// `save` (forward kernel only): non-NULL = write h_i and the relu masks to the lane's activation slots
-template <int KIND, bool KEEP, bool SAVE = false>
+// SAVE (the pass kernels, nsr_fwd2.h): `save` non-NULL = write h_i and the relu masks to the lane's activation slots
+template <int KIND, bool SAVE = false>
 NSR_DEV void mlp_xyz_fwd(const float *pk, const float *aux, float px, float py, float pz,
-                         const Act<cdim_of(KIND) / 16> &c, int lane, float (&out)[nout_of(KIND)], Kept<KIND> *kept,
-                         const ActSink *save = nullptr) {
+                         const Act<cdim_of(KIND) / 16> &c, int lane, float (&out)[nout_of(KIND)], const ActSink *save = nullptr) {
     constexpr int CD = cdim_of(KIND), NOUT = nout_of(KIND), NTC = CD / 16;
     const int g = lane >> 4;
     Act<kET> e;
@@ -818,13 +760,12 @@ NSR_DEV void mlp_xyz_fwd(const float *pk, const float *aux, float px, float py, 
             gemv_fwd<2>(acc, h, pk + xyz_mat(CD, i == 1 ? XW1 : (i == 2 ? XW2 : XW4)).pk, lane);
         }
         unsigned m = 0;
-        if (KEEP || SAVE) m = relu_mask(acc); else relu_plain(acc);
+        if (SAVE) m = relu_mask(acc); else relu_plain(acc);
         acc[0] += to_v(ld4(aux + AUX_V + i * 32 + 4 * g));
         acc[1] += to_v(ld4(aux + AUX_V + i * 32 + 16 + 4 * g));
         gemv_fwd<NTC>(acc, c, pk + xyz_mat(CD, i == 0 ? XU0 : (i == 1 ? XU1 : (i == 2 ? XU2 : (i == 3 ? XU3 : XU4)))).pk, lane);
         h.t[0] = acc[0];
         h.t[1] = acc[1];
-        if (KEEP) { kept->h[i] = h; kept->mask[i] = m; }
         if (SAVE) {
             if (save->p && save->full) { st4(save->p + (2 * i) * save->stride, to_F4(h.t[0])); st4(save->p + (2 * i + 1) * save->stride, to_F4(h.t[1])); }
             if (i < 4) mpack0 |= m << (8 * i); else mpack1 = m;
@@ -848,9 +789,8 @@ NSR_DEV void mlp_xyz_fwd(const float *pk, const float *aux, float px, float py, 
 }
 
 // MLP_no_xyz (decoder.py:262-274): h = c; h = relu(W_i h + b_i); after i == 2: h = [c | h]
-template <bool KEEP, bool SAVE = false>
-NSR_DEV void mlp_nox_fwd(const float *pk, const float *aux, const Act<2> &c, int lane, float (&out)[1], Kept<0> *kept,
-                         const ActSink *save = nullptr) {
+template <bool SAVE = false>
+NSR_DEV void mlp_nox_fwd(const float *pk, const float *aux, const Act<2> &c, int lane, float (&out)[1], const ActSink *save = nullptr) {
     const int g = lane >> 4;
     Act<2> h = c;
     unsigned mpack0 = 0, mpack1 = 0;
@@ -866,10 +806,9 @@ NSR_DEV void mlp_nox_fwd(const float *pk, const float *aux, const Act<2> &c, int
             gemv_fwd<2>(acc, h, pk + nox_mat(i == 0 ? NW0 : (i == 1 ? NW1 : (i == 2 ? NW2 : NW4))).pk, lane);
         }
         unsigned m = 0;
-        if (KEEP || SAVE) m = relu_mask(acc); else relu_plain(acc);
+        if (SAVE) m = relu_mask(acc); else relu_plain(acc);
         h.t[0] = acc[0];
         h.t[1] = acc[1];
-        if (KEEP) { kept->h[i] = h; kept->mask[i] = m; }
         if (SAVE) {
             if (save->p && save->full) { st4(save->p + (2 * i) * save->stride, to_F4(h.t[0])); st4(save->p + (2 * i + 1) * save->stride, to_F4(h.t[1])); }
             if (i < 4) mpack0 |= m << (8 * i); else mpack1 = m;
@@ -936,27 +875,24 @@ NSR_DEV double wave_sum_d(double v) {
 // NICE.forward for the tile of this wave with the packed weights staged in LDS, one decoder after the other
 // (block-wide barriers inside: EVERY wave of the block must call it).  On entry `wl` holds the first decoder of the
 // stage (coarse or middle); on exit the last one.  Returns (r,g,b,occ) before the out-of-bound override.
-template <int STAGE, bool SAVE = false>
-NSR_DEV F4 decode_tile_lds(const RenderParams &P, const float *aux, float *wl, double px, double py, double pz, int lane,
-                           long long gp = -1) {      // gp: global index of the lane's sample point (saved activations), -1: none
+template <int STAGE>
+NSR_DEV F4 decode_tile_lds(const RenderParams &P, const float *aux, float *wl, double px, double py, double pz, int lane) {
     const int g = lane >> 4;
     F4 raw = F4{0.f, 0.f, 0.f, 0.f};
     if (STAGE == NSR_STAGE_COARSE) {
         const Lvl L = make_level(P.grid[NSR_COARSE], px, py, pz);
         const Act<2> c = gather_feat(P.grid[NSR_COARSE], L, g);
         float o[1];
-        const ActSink sc = act_sink(P, 0, gp, g);
-        mlp_nox_fwd<false, SAVE>(wl, aux, c, lane, o, nullptr, &sc);
+        mlp_nox_fwd(wl, aux, c, lane, o);
         raw.w = o[0];
     } else {
         const float fx = (float)px, fy = (float)py, fz = (float)pz;     // decoder.py:189
         const Lvl Lm = make_level(P.grid[NSR_MIDDLE], px, py, pz);
         const Act<2> cm = gather_feat(P.grid[NSR_MIDDLE], Lm, g);
         float om[1];
-        const ActSink sm = act_sink(P, 0, gp, g);
         const Dbg dbg{P.dbg ? P.dbg + ((long long)bid_x() * 12 + (tid() >> 6)) * 64 : nullptr};
         dbg.stamp(10);                                                  // features gathered (issued), before the middle decoder
-        mlp_xyz_fwd<NSR_MIDDLE, false, SAVE>(wl, aux, fx, fy, fz, cm, lane, om, nullptr, &sm);
+        mlp_xyz_fwd<NSR_MIDDLE>(wl, aux, fx, fy, fz, cm, lane, om);
         dbg.stamp(3);
         float occ = om[0];
         if (STAGE >= NSR_STAGE_FINE) {
@@ -969,8 +905,7 @@ NSR_DEV F4 decode_tile_lds(const RenderParams &P, const float *aux, float *wl, d
             Act<4> cc;
             cc.t[0] = cf.t[0]; cc.t[1] = cf.t[1]; cc.t[2] = cm.t[0]; cc.t[3] = cm.t[1];    // decoder.py:182-187
             float of[1];
-            const ActSink sf = act_sink(P, 1, gp, g);
-            mlp_xyz_fwd<NSR_FINE, false, SAVE>(wl, aux + AUX_FLOATS, fx, fy, fz, cc, lane, of, nullptr, &sf);
+            mlp_xyz_fwd<NSR_FINE>(wl, aux + AUX_FLOATS, fx, fy, fz, cc, lane, of);
             occ = of[0] + om[0];                                                            // decoder.py:333,341
             dbg.stamp(5);
         }
@@ -982,8 +917,7 @@ NSR_DEV F4 decode_tile_lds(const RenderParams &P, const float *aux, float *wl, d
             block_sync();
             dbg.stamp(11);
             float oc[4];
-            const ActSink sc = act_sink(P, 2, gp, g);
-            mlp_xyz_fwd<NSR_COLOR, false, SAVE>(wl, aux + 2 * AUX_FLOATS, fx, fy, fz, ccol, lane, oc, nullptr, &sc);
+            mlp_xyz_fwd<NSR_COLOR>(wl, aux + 2 * AUX_FLOATS, fx, fy, fz, ccol, lane, oc);
             raw.x = oc[0]; raw.y = oc[1]; raw.z = oc[2];
         }
         raw.w = occ;
@@ -998,7 +932,7 @@ NSR_DEV F4 decode_tile_lds(const RenderParams &P, const float *aux, float *wl, d
 // decoder's packed operand stream (61-82 KB) in LDS so that every MFMA operand is an LDS read (~100 cycles)
 // instead of an L2 round trip.  The gathers of the next decoder's features are issued before the barrier.
 // ------------------------------------------------------------------------------------------------
-template <int STAGE, bool SAVE = false>
+template <int STAGE>
 NSR_KERNEL NSR_BOUNDS(768) void render_fwd_kernel(const RenderParams P) {
     char *lds = lds_base();
     const int npts = P.rays_per_block * P.S;
@@ -1035,7 +969,7 @@ NSR_KERNEL NSR_BOUNDS(768) void render_fwd_kernel(const RenderParams P) {
         const double pz = (double)P.rays_o[rr * 3 + 2] + (double)P.rays_d[rr * 3 + 2] * z;
         const bool inside = (px > P.blo[0]) && (px < P.bhi[0]) && (py > P.blo[1]) && (py < P.bhi[1]) &&
                             (pz > P.blo[2]) && (pz < P.bhi[2]);
-        F4 raw = decode_tile_lds<STAGE, SAVE>(P, aux, wl, px, py, pz, lane, active ? ray * S + k : -1);
+        F4 raw = decode_tile_lds<STAGE>(P, aux, wl, px, py, pz, lane);
         dbg.stamp(6);
         if (!inside) raw.w = 100.f;                                         // Renderer.py:57
         if (active && g == 0) {

@@ -53,14 +53,14 @@ def _bound_arrays(bound):
 
 
 # Where the pixel indices of a window come from when the caller passes none (src/common.py:99: `torch.randint(h * w, (n,))`
-# per keyframe): "kernel" -- drawn inside the window kernel (philox4x32-10 keyed by torch's seed, nsr_get_samples_window_draw):
-# no launch of its own and, under graph capture, none of the fills with which torch keeps a captured generator's offset -- or
-# "torch" -- one `torch.randint` call for the window.  Same distribution either way; neither is the reference's stream (it
-# draws once per keyframe).  `get_samples` (the drop-in of common.py:91-106) always uses torch.randint like the reference.
-PIXEL_DRAW = os.environ.get("NSR_PIXEL_DRAW", "kernel")
-# The fused iterations' one zero fill (loss accumulator, kept max, every gradient buffer of the backward) inside the window
-# kernel's launch (nsr_get_samples_window_fused) instead of a `torch.zeros` launch in front of it; "0": the separate fill (A/B).
-FUSED_FILL = os.environ.get("NSR_FUSED_FILL", "1") != "0"
+# per keyframe): on the GPU they are drawn inside the window kernel (philox4x32-10 keyed by torch's seed,
+# nsr_get_samples_window_draw): no launch of its own and, under graph capture, none of the fills with which torch keeps a
+# captured generator's offset; elsewhere one `torch.randint` call for the window.  Same distribution either way; neither is the
+# reference's stream (it draws once per keyframe).  `get_samples` (the drop-in of common.py:91-106) always uses torch.randint
+# like the reference.  PIXEL_DRAW names that draw for callers and tests that ask; it is fixed, not a setting.
+PIXEL_DRAW = "kernel"
+# The fused iterations' one zero fill (loss accumulator, kept max, every gradient buffer of the backward) runs inside the window
+# kernel's launch (nsr_get_samples_window_fused) instead of a `torch.zeros` launch in front of it.
 _DRAW_STATE = {}
 
 
@@ -205,11 +205,11 @@ def pose_grads(indices, K, n, crop, intr, g_o, g_d, shapes, out=None) -> List[to
 def _window_meta(H0, H1, W0, W1, n, W, fx, fy, cx, cy, c2ws, depths, colors, bound, device, indices, draw_state=None, peer_seeds=None):
     K = len(depths)
     dev = torch.device(device)
-    if indices is None and (PIXEL_DRAW == "kernel" or draw_state is not None) and dev.type == "cuda":
-        indices = torch.empty((K * n,), dtype=torch.int64, device=dev)            # filled by the window kernel (see PIXEL_DRAW)
+    if indices is None and dev.type == "cuda":
+        indices = torch.empty((K * n,), dtype=torch.int64, device=dev)            # filled by the window kernel (in-kernel draw, above)
         indices._nsr_draw = True
         indices._nsr_state = draw_state                                           # None: the device's default state
-        indices._nsr_peers = list(peer_seeds) if (peer_seeds and FUSED_FILL) else None   # (ShardedMapping: the other ranks' seeds)
+        indices._nsr_peers = list(peer_seeds) if peer_seeds else None              # (ShardedMapping: the other ranks' seeds)
     elif indices is None:
         indices = torch.randint((H1 - H0) * (W1 - W0), (K * n,), device=dev)      # one draw for the window (common.py:99 per frame)
     else:
@@ -227,7 +227,7 @@ def get_samples_window(H0, H1, W0, W1, n, H, W, fx, fy, cx, cy, c2ws: Sequence[t
     ``colors[k]`` [H,W,3] on the device), concatenated in frame order -- the sampling loop of Mapper.py:437-468 -- plus the
     bounding-box pre-filter of :471-481 as ``keep`` (bool per ray) and ``kept_max`` (1-element tensor: maximum depth over
     the kept rays, to be passed as ``render_batch_ray(..., gt_max=kept_max)``).  ``indices``: optional [K*n] flat crop
-    indices (default: drawn inside the kernel, see ``PIXEL_DRAW``)."""
+    indices (default: drawn inside the kernel, see the in-kernel draw at the top of this module)."""
     meta, c2ws = _window_meta(H0, H1, W0, W1, n, W, fx, fy, cx, cy, c2ws, depths, colors, bound, device, indices)
     _require_cuda(depths[0] if depths[0].is_cuda else torch.empty(0, device=meta[-1]), "get_samples_window: frames")
     ro, rd, gd, gc, keep, kmax = _WindowFn.apply(meta, *c2ws)
@@ -270,7 +270,7 @@ class _MappingLossFn(torch.autograd.Function):
                 sum(param_count(s) for s, nd in zip(slots, need_par) if nd)
         n_pose = 16 * K if need_pose else 0                     # d c2w of the window (pose_grads), behind the gradients
         # (round 5: not a fill launch -- the window kernel zero-fills it beside its sampling blocks and writes the header)
-        fuse_fill = FUSED_FILL and N > 0
+        fuse_fill = N > 0
         if fuse_fill and not getattr(indices, "_nsr_draw", False) and getattr(indices, "_nsr_state", None) is None and _capturing() \
                 and (dev.type, dev.index if dev.index is not None else torch.cuda.current_device()) not in _DRAW_STATE:
             # explicit indices, nothing is drawn -- but the fused launch borrows the device's draw state for its hand-off words, and that

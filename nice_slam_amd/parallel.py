@@ -283,7 +283,7 @@ class ShardedMapping:
         return torch.randint(n_pixels_crop, (n_total,), device=dev, generator=self.generator(dev))
 
     def draw_state(self, dev) -> torch.Tensor:
-        """This rank's state of the in-kernel pixel draw (mapping.PIXEL_DRAW = "kernel"): seeded per rank like ``generator``,
+        """This rank's state of the in-kernel pixel draw (nice_slam_amd.mapping, on the GPU): seeded per rank like ``generator``,
         advanced by the window kernel itself -- nothing to register with a capturing graph."""
         dev = torch.device(dev)
         if self._draw_state is None:
@@ -440,7 +440,7 @@ class ShardedMapping:
         state, peers = None, None
         if indices is None:                  # this rank's own draw (see __init__): never the global generator / the device's state
             dev = frames[0][1].device
-            if mapping.PIXEL_DRAW == "kernel" and dev.type == "cuda":
+            if dev.type == "cuda":
                 state = self.draw_state(dev)
                 peers = self.peer_seeds()
             else:

@@ -7,7 +7,7 @@ ROOT="$(cd "$HERE/../.." && pwd)"
 CXX="${NSR_EMU_CXX:-/opt/rocm/lib/llvm/bin/clang++}"
 [ -x "$CXX" ] || CXX=clang++
 BUILD="${NSR_EMU_BUILD:-$HERE/_build}"
-OUT="${NSR_EMU_OUT:-$HERE/libnsr_emu.so}"      # (A/B builds of the emulator: tests/perf/parity_causes.py)
+OUT="${NSR_EMU_OUT:-$HERE/libnsr_emu.so}"      # (variant builds with NSR_EMU_DEFS: tests/test_emu_parity.py)
 mkdir -p "$BUILD"
 # the shim directory comes first on the include path so that its nsr_dev.h / nsr_rt.h shadow the HIP ones
 cp "$ROOT/nice_slam_amd/csrc/nsr_api.cpp" "$ROOT/nice_slam_amd/csrc/nsr_kernels.h" "$ROOT/nice_slam_amd/csrc/nsr_bwd2.h" "$ROOT/nice_slam_amd/csrc/nsr_fwd2.h" "$ROOT/nice_slam_amd/csrc/nsr_layout.h" "$BUILD/"

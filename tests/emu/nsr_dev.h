@@ -152,7 +152,6 @@ NSR_DEV unsigned long long ballot64(bool p) {
 NSR_DEV int flag_load(const int *p) { return shfl_any(*p, 0); }
 NSR_DEV float shfl(float v, int src) { return shfl_any(v, src); }
 NSR_DEV int shfl_i(int v, int src) { return shfl_any(v, src); }
-NSR_DEV double shfl_d(double v, int src) { return shfl_any(v, src); }
 NSR_DEV float shfl_xor(float v, int m) { return shfl_any(v, (emu::B->cur->tid & 63) ^ m); }
 NSR_DEV double shfl_xor_d(double v, int m) { return shfl_any(v, (emu::B->cur->tid & 63) ^ m); }
 NSR_DEV float shfl_up(float v, int d) {
@@ -167,15 +166,12 @@ NSR_DEV float shfl_down(float v, int d) {
 struct Dbg { long long *p; NSR_DEV void stamp(int) const {} NSR_DEV void note(int, long long) const {} };
 NSR_DEV void wave_fence() { emu::wave_sync(); }
 NSR_DEV void sched_fence() {}
-NSR_DEV void sched_fence_gemv() {}
-NSR_DEV void sched_fence_emb() {}
 NSR_DEV void keep_alive(float) {}
 NSR_DEV void keep_alive_d(double) {}
 NSR_DEV void loop_fence() {}
 NSR_DEV int opaque_i(int v) { return v; }
 NSR_DEV void block_sync() { emu::block_sync_impl(); }
 
-NSR_DEV void prefetch_line(const float *, float *) {}
 NSR_DEV void dma16(const float *gsrc, float *lds_base, int lane) { std::memcpy(lds_base + lane * 4, gsrc, 16); }
 template <int N> NSR_DEV void dma_wait() {}
 // (a wave's lanes run in lock step on the device: everything the wave did before the flag store has been done by ALL its lanes --
@@ -199,7 +195,6 @@ NSR_DEV void atomic_add_lds_i(int *p, int v) { *p += v; }
 NSR_DEV int atomic_fetch_add_lds_i(int *p, int v) { const int o = *p; *p += v; return o; }
 NSR_DEV int atomic_cas_lds_i(int *p, int expect, int v) { const int o = *p; if (o == expect) *p = v; return o; }
 NSR_DEV int lds_load_i(const int *p) { return *p; }
-NSR_DEV float lds_load_f(const float *p) { return *p; }
 NSR_DEV void atomic_add_global_d(double *p, double v) { *p += v; }
 NSR_DEV void atomic_add_global_off(float *base, unsigned byte_off, float v) { atomic_add_global(reinterpret_cast<float *>(reinterpret_cast<char *>(base) + byte_off), v); }
 NSR_DEV unsigned long long atomic_fetch_add_global_u64(unsigned long long *p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_ACQ_REL); }
@@ -220,11 +215,6 @@ NSR_DEV void keep_alive_u(unsigned) {}
 
 NSR_DEV unsigned uniform_load_u8(const unsigned char *p) { return *p; }
 NSR_DEV char *lds_base() { return emu::B->lds; }
-
-struct Stream { const float *base; };
-NSR_DEV void stream_st(const Stream &s, int lane_off, int const_off, float v) { const_cast<float *>(s.base)[lane_off + const_off] = v; }
-NSR_DEV Stream make_stream(const float *base) { return Stream{base}; }
-NSR_DEV float stream_ld(const Stream &s, int lane_off, int const_off) { return s.base[lane_off + const_off]; }
 
 NSR_DEV F4 ld4(const float *p) { return F4{p[0], p[1], p[2], p[3]}; }
 NSR_DEV void st4(float *p, F4 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w; }

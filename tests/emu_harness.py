@@ -19,23 +19,31 @@ EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU_LIB = os.path.join(EMU_DIR, "libnsr_emu.so")
 
 
-def build_emu(force=False):
+def build_emu(force=False, variant=None, defs=""):
+    """The emulator library; `variant` (a name) with `defs` (-D flags, e.g. the NSR_TEST_* hooks of nsr_api.cpp): a variant build
+    of its own under tests/emu/_build_<variant>/."""
     srcs = [os.path.join(ROOT, "nice_slam_amd", "csrc", f) for f in ("nsr_api.cpp", "nsr_kernels.h", "nsr_bwd2.h", "nsr_fwd2.h", "nsr_layout.h")]
     srcs += [os.path.join(EMU_DIR, f) for f in ("nsr_dev.h", "nsr_rt.h", "emu_runtime.cpp", "build_emu.sh")]
     srcs += [os.path.join(ROOT, "include", "nsr.h")]
-    if not force and os.path.exists(EMU_LIB) and all(os.path.getmtime(EMU_LIB) >= os.path.getmtime(s) for s in srcs):
-        return EMU_LIB
-    subprocess.run([os.path.join(EMU_DIR, "build_emu.sh")], check=True, capture_output=True)
-    return EMU_LIB
+    env, out = None, EMU_LIB
+    if variant is not None:
+        bdir = os.path.join(EMU_DIR, "_build_" + variant)
+        out = os.path.join(bdir, "libnsr_emu.so")
+        env = dict(os.environ, NSR_EMU_DEFS=defs, NSR_EMU_OUT=out, NSR_EMU_BUILD=bdir)
+    if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
+        return out
+    subprocess.run([os.path.join(EMU_DIR, "build_emu.sh")], check=True, capture_output=True, env=env)
+    return out
 
 
 _emu = None
 
 
 def emu_lib():
+    """NSR_EMU_LIB: the path of a variant build to load instead (tests/test_emu_parity.py runs part of itself against one)"""
     global _emu
     if _emu is None:
-        _emu = _capi.Lib(build_emu())
+        _emu = _capi.Lib(os.environ.get("NSR_EMU_LIB") or build_emu())
     return _emu
 
 
@@ -150,8 +158,9 @@ class HostScene:
         return out
 
     def backward(self, stage, fwd, d_depth, d_var, d_rgb, want_grid=True, want_params=True, want_rays=True, max_blocks=0,
-                 overwrite_dparams=False, grad_scale=None, from_forward=False, in_place=False, grad_voxel_masks=None):
-        """grad_voxel_masks: None or {slot: uint8 [Z][Y][X]} -- nsr_render_args.grad_voxel_mask (consumed-gradient masks)"""
+                 overwrite_dparams=False, grad_scale=None, from_forward=False, in_place=False, grad_voxel_masks=None, ws_tail=0):
+        """grad_voxel_masks: None or {slot: uint8 [Z][Y][X]} -- nsr_render_args.grad_voxel_mask (consumed-gradient masks);
+        ws_tail: NaN floats behind the workspace nsr_bwd_workspace_floats sizes (self.last_ws[self.last_nws:], nobody may write them)"""
         if "acts" not in fwd:                              # forward without an activation buffer: run the saving forward now
             assert not from_forward and not in_place
             was, self.save_acts = self.save_acts, True
@@ -197,8 +206,8 @@ class HostScene:
             res["d_rays_d"] = np.zeros((n, 3), dtype=np.float32)
             b.d_rays_o, b.d_rays_d = ptr(res["d_rays_o"]), ptr(res["d_rays_d"])
         nws = self.lib.nsr_bwd_workspace_floats(_capi.STAGE_ID[stage], n, S, max_blocks)
-        ws = np.full(max(nws, 1), np.nan, dtype=np.float32)
-        self.last_ws = ws
+        ws = np.full(max(nws, 1) + ws_tail, np.nan, dtype=np.float32)
+        self.last_ws, self.last_nws = ws, nws
         b.workspace, b.workspace_floats, b.max_blocks = ptr(ws), nws, max_blocks
         b.overwrite_dparams = 1 if overwrite_dparams else 0
         gs = None if grad_scale is None else np.array([grad_scale], dtype=np.float64)

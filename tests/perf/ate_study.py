@@ -1,8 +1,7 @@
 """TEST INFRASTRUCTURE (measurement script): the ATE distribution of the tiny synthetic SLAM run of tests/test_hip_slam_ate.py over
-many seeds, one process per variant (the measurement switches of libnsr.so are read once per process).
+many seeds, one process per variant.
 
     python tests/perf/ate_study.py --kind fused --seeds 0:100 --out gpurun_out/ate/fused.json
-    NSR_PIXEL_DRAW=torch python tests/perf/ate_study.py --kind fused --seeds 0:60 --out gpurun_out/ate/fused_torchdraw.json
     python tests/perf/ate_study.py --kind aten --seeds 0:30 --out gpurun_out/ate/aten.json
     python tests/perf/ate_study.py --kind fused --seeds 0:1 --repeat 30 --out ...      # run-to-run spread of ONE seed
     python tests/perf/ate_study.py --summarize gpurun_out/ate/*.json                     # table + CI of the mean differences

@@ -2,7 +2,9 @@
 Per-phase breakdown of the forward kernel from s_memtime stamps (Dbg::stamp in nsr_kernels.h).
 
 Needs the instrumented build (tools/build_ts.sh -> nice_slam_amd/_ab/libnsr_ts.so, not part of the product):
-    sh tools/build_ts.sh && NSR_LIB_PATH=$PWD/nice_slam_amd/_ab/libnsr_ts.so python tests/perf/ts_fwd.py [n_rays] [stage]"""
+    sh tools/build_ts.sh && NSR_LIB_PATH=$PWD/nice_slam_amd/_ab/libnsr_ts.so python tests/perf/ts_fwd.py [n_rays] [stage] [--one-launch]
+--one-launch: a forward without gradients, i.e. without an activation buffer -- the one-launch kernel (nsr_kernels.h) instead of
+the three-launch forward (nsr_fwd2.h)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -10,21 +12,24 @@ import torch, numpy as np
 from scene_util import make_scene, build_product
 import nice_slam_amd as nsa
 dev = torch.device("cuda", 0)
-n_rays = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
-stage = sys.argv[2] if len(sys.argv) > 2 else "color"
+SPLIT = "--one-launch" not in sys.argv                   # the three-launch forward (nsr_fwd2.h): stamps of its pass kernel
+argv = [a for a in sys.argv if a != "--one-launch"]
+n_rays = int(argv[1]) if len(argv) > 1 else 1000
+stage = argv[2] if len(argv) > 2 else "color"
 sc = make_scene(seed=0, n_rays=n_rays, scene="replica_room0", fine_scale=1.0, zero_frac=0.01, depth_range=(1.0, 4.0))
 renderer, dec, grids = build_product(sc, dev)
 grids = {k: v.requires_grad_(True) for k, v in grids.items()}
 for p in dec.parameters(): p.requires_grad_(True)
 NB, NW, NS = 1024, 12, 64
-SPLIT = os.environ.get("NSR_FWD_SPLIT", "1") != "0"         # the three-launch forward (nsr_fwd2.h): stamps of its pass kernel
 buf = torch.zeros((NB * NW * NS,), dtype=torch.int64, device=dev)
 frames = [(sc["c2w"].to(dev), sc["depth_img"].to(dev), sc["color_img"].to(dev)) for _ in range(5)]
 for it in range(3):
     if it == 2: os.environ["NSR_DBG_FWD_PTR"] = hex(buf.data_ptr())
     for g in grids.values(): g.grad = None
     for p in dec.parameters(): p.grad = None
-    nsa.mapping_loss(renderer, grids, dec, frames, n_rays // 5, stage).backward()
+    with torch.set_grad_enabled(SPLIT):
+        loss = nsa.mapping_loss(renderer, grids, dec, frames, n_rays // 5, stage)
+    if SPLIT: loss.backward()
     torch.cuda.synchronize()
 t = buf.cpu().numpy().reshape(NB, NW, NS).astype(np.float64) / 2100.0           # microseconds at ~2.1 GHz
 ok = (t[:, :, 0] > 0) & (t[:, :, 9] > 0)

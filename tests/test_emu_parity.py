@@ -718,38 +718,62 @@ def test_camera_from_tensor_forward_and_backward(emu):
     assert np.allclose(d, t.grad.numpy(), rtol=1e-5, atol=1e-5 * float(t.grad.abs().max()))
 
 
-def test_full_size_forward_blocks_in_a_subprocess():
-    """nsr_render_fwd shrinks its blocks for small batches (one block per CU); NSR_FWD_SMALL=0 keeps the 12-tile blocks the
-    large batches use, so that the small CPU scenes cover that shape too (the switch is read once per process)."""
+def _run_against_variant(variant, defs, selection, extra_env=None):
+    """run the `selection` of this file in a child process against an emulator built with `defs` (the NSR_TEST_* launch-policy
+    hooks of nsr_api.cpp, which the library build never defines)"""
     import subprocess, sys
-    if os.environ.get("NSR_FWD_SMALL") == "0":
+    if not (os.path.exists("/opt/rocm/lib/llvm/bin/clang++") or shutil.which("clang++")):
+        pytest.skip("no host clang++ for the emulator build")
+    if os.environ.get("NSR_EMU_LIB"):
         pytest.skip("already the inner run")
-    env = dict(os.environ, NSR_FWD_SMALL="0", NSR_EMU_SAVE_ACTS="0")      # ... through the one-launch forward kernel (no activation buffer)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-k",
-                        "golden_forward or random_scene or fused_mapping_loss or other_sample_counts"],
+    from emu_harness import build_emu
+    env = dict(os.environ, NSR_EMU_LIB=build_emu(variant=variant, defs=defs), **(extra_env or {}))
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-k", selection],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
+
+
+def test_full_size_forward_blocks_in_a_subprocess():
+    """nsr_render_fwd shrinks its blocks for small batches (one block per CU); NSR_TEST_FWD_SMALL=0 keeps the 12-tile blocks the
+    large batches use, so that the small CPU scenes cover that shape too."""
+    _run_against_variant("fwd_full_blocks", "-DNSR_TEST_FWD_SMALL=0",
+                         "golden_forward or random_scene or fused_mapping_loss or other_sample_counts",
+                         {"NSR_EMU_SAVE_ACTS": "0"})      # ... through the one-launch forward kernel (no activation buffer)
 
 
 @pytest.mark.parametrize("cells,slots", [("0", None), ("64", None), ("64", "16")])
 def test_hot_voxel_table_extremes_in_a_subprocess(cells, slots):
     """The dX kernel's hot-voxel table (LDS rows for the samples next to their ray's origin, claimed with a compare-and-swap,
-    flushed once per block; since round 5 as many slots as the block's LDS has left): NSR_DX_HOT_CELLS=0 switches it off, 64 sends
-    EVERY sample of these small scenes through it, and with NSR_DX_HOT_SLOTS=16 most of them find their slot taken by another voxel
-    (the fall-back to memory atomics).  All against the oracle, like the default of six cells in the rest of this file (the
-    switches are read once per process)."""
-    import subprocess, sys
-    if os.environ.get("NSR_DX_HOT_CELLS") is not None:
-        pytest.skip("already the inner run")
-    env = dict(os.environ, NSR_DX_HOT_CELLS=cells)
-    if slots is not None:
-        env["NSR_DX_HOT_SLOTS"] = slots
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-k",
-                        "golden_forward or random_scene or saved_activations_equal"],
-                       env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout
+    flushed once per block; since round 5 as many slots as the block's LDS has left): NSR_TEST_HOT_CELLS=0 switches it off, 64 sends
+    EVERY sample of these small scenes through it, and with NSR_TEST_HOT_SLOTS=16 most of them find their slot taken by another voxel
+    (the fall-back to memory atomics).  All against the oracle, like the default of six cells in the rest of this file."""
+    defs = "-DNSR_TEST_HOT_CELLS=%s" % cells + ("" if slots is None else " -DNSR_TEST_HOT_SLOTS=%s" % slots)
+    _run_against_variant("hot_%s_%s" % (cells, slots or "dflt"), defs, "golden_forward or random_scene or saved_activations_equal")
+
+
+@pytest.mark.parametrize("stage", STAGES)
+def test_backward_stays_inside_the_sized_workspace(emu, stage):
+    """nsr_bwd_workspace_floats sizes the backward's workspace for passes * nb dX blocks (d _B partials) and passes * nimg dW
+    partial images; the dX block deal over the decoder passes (light passes get fewer blocks, every pass at least one) must not
+    launch more blocks than that.  A NaN tail behind the sized workspace stays untouched for every persistent-grid cap, small
+    and ragged ray counts, and the parameter / ray gradient subsets that make passes light."""
+    s = make_scene(seed=41, n_rays=37, small=True)
+    sc = _host_scene(emu, s["grids"], s["params"], s["bound"].numpy())
+    w = s["w"]
+    slots = {"coarse": ["coarse"], "middle": ["middle"], "fine": ["middle", "fine"], "color": ["middle", "fine", "color"]}[stage]
+    subsets = [True] + [[sl] for sl in slots[:-1]] + ([slots[-1:]] if len(slots) > 1 else [])
+    tail = 4096
+    for n in (1, 2, 5, 37):
+        sl = slice(0, n)
+        fwd = sc.forward(stage, s["rays_o"].numpy()[sl], s["rays_d"].numpy()[sl], s["gt_depth"].numpy()[sl])
+        for max_blocks in (1, 2, 3, 0):
+            for params in subsets:
+                for rays in (True, False):
+                    sc.backward(stage, fwd, w["depth"].numpy()[sl], w["var"].numpy()[sl], w["rgb"].numpy()[sl], want_params=params,
+                                want_rays=rays, max_blocks=max_blocks, ws_tail=tail)
+                    assert sc.last_nws > 0
+                    assert np.isnan(sc.last_ws[sc.last_nws:]).all(), (stage, n, max_blocks, params, rays)
 
 
 @pytest.mark.parametrize("stage", ["coarse", "middle", "fine", "color"])

@@ -1,7 +1,7 @@
 #!/bin/sh
 # Measurement tooling: which unit is busy while the dX kernel's matrix pipe idles?  rocprofv3 --pmc passes (one counter group per run, no
-# trace domain next to --pmc) over ONE bench configuration under a list of environment settings (NSR_X measurement switches, NSR_LIB_PATH
-# of an A/B build), summarised per nsr kernel and variant.
+# trace domain next to --pmc) over ONE bench configuration under a list of environment settings (NSR_LIB_PATH of an A/B build),
+# summarised per nsr kernel and variant.
 #   sh tools/pmc_dx.sh <tag> "<bench flags>" "ENV1=.. ENV2=.." "ENV.." ...   ->  gpurun_out/<tag>/<tag>_pmc_table.txt
 # (rocprofv3 --att, the thread trace the round-5 verdict asked for first, needs librocprof-trace-decoder, which this image does not ship.)
 TAG="$1"; FLAGS="$2"; shift 2

@@ -1,6 +1,6 @@
 #!/bin/sh
 # Measurement tooling: per-kernel average times (rocprofv3 --kernel-trace --stats) of one bench configuration under a list of
-# NSR_X measurement switches / environment settings.   sh tools/xsweep.sh <tag> "<bench flags>" "ENV1=.. ENV2=.." "ENV.." ...
+# environment settings, e.g. NSR_LIB_PATH of an A/B build (tools/build_ts.sh).   sh tools/xsweep.sh <tag> "<bench flags>" "ENV1=.. ENV2=.." "ENV.." ...
 TAG="$1"; FLAGS="$2"; shift 2
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$ROOT/gpurun_out/$TAG"
