@@ -461,6 +461,53 @@ int nsr_transform_points(double *pts, int64_t n, const double *m, void *stream);
 int nsr_cull_vertices(const void *verts, int64_t n, int32_t fp64, const float *w2c, int32_t K, int32_t H, int32_t W, double fx,
                       double fy, double cx, double cy, const int32_t *faces, int64_t nf, uint8_t *seen, uint8_t *keep, void *stream);
 
+/* --- Mesh bound from keyframes (src/utils/Mesher.py:214-279, get_bound_from_frames) -------------------------------------
+ * TSDF fusion restating Open3D's legacy ScalableTSDFVolume (units of 16^3 voxels, depth_sampling_stride 4, depth_scale 1,
+ * depth_trunc 1000; the caller passes voxel_length = 4 scale / 512 and sdf_trunc = 0.04 scale), geometry only.  The rules are
+ * written out in nice_slam_amd/csrc/nsr_bound.h.  depth [K][H][W] fp32; c2w [K][12] fp64: rows 0..2 of the FLIPPED c2w
+ * (columns 1 and 2 negated); w2c [K][12] fp32: rows 0..2 of inv(flipped c2w) taken in fp64.  box: [6] int32 (unit index lo xyz,
+ * hi xyz, inclusive): device for nsr_tsdf_unit_box, a HOST copy everywhere else.
+ *   nsr_tsdf_unit_box        the box of every unit some frame touches
+ *   nsr_tsdf_workspace_bytes device workspace for that box (-1: empty, or more than 2^31 units)
+ *   nsr_tsdf_touch_count     dense unit bitmap + its rank into the workspace; n_units [1] int64 (device) out
+ *   nsr_tsdf_touch_emit      units [n_units][3] int32 in linear-index order, touch [n_units][(K + 31) / 32] uint32: bit k of
+ *                            unit u = frame k touches u
+ *   nsr_tsdf_integrate       tsdf, weight [n_units][16][16][16] fp32 (x slowest), frames in order, bit-identical run to run
+ *   nsr_tsdf_surface_count   counts [n_units + 1] int64: surface points before each unit; counts[n_units] = the total
+ *   nsr_tsdf_surface_emit    points [n_points][3] fp64 (the vertex set of extract_triangle_mesh, fixed order)
+ * Hull:
+ *   nsr_hull_extremes        ext [26] int64: the extreme point along each direction of {-1, 0, 1}^3 \ 0 (code 0..26 without
+ *                            13, x slowest); partial: nsr_hull_partial_doubles() doubles of device scratch
+ *   nsr_hull_prefilter       keep [n] uint8 = 0 iff the point is more than `margin` inside every plane (HOST [n_planes][4],
+ *                            at most 64): planes of the hull of those extremes
+ *   nsr_convex_hull          HOST, all pointers host memory: fp64 quickhull with distance tolerance tol of pts [n][3], scaled
+ *                            by bound_scale about the mean of its vertices.  counts [2] = (nv, nf); verts [nv][3] (capacity n),
+ *                            vert_index [nv] (the input point of each vertex, ascending), faces [nf][3] int32 outward (capacity
+ *                            2 n), planes [nf][4] (unit normal, offset) of the scaled faces
+ *   nsr_hull_contains        inside [n] uint8: 1 iff ((nx x + ny y) + nz z) + off <= 0 in fp64 for every plane (device
+ *                            [n_planes][4]); pts fp32 (fp64 = 0) or fp64 */
+int nsr_tsdf_unit_box(const float *depth, int32_t K, int32_t H, int32_t W, const double *c2w, double fx, double fy, double cx, double cy,
+                      double voxel_length, double sdf_trunc, int32_t *box, void *stream);
+int64_t nsr_tsdf_workspace_bytes(const int32_t *box);
+int nsr_tsdf_touch_count(const float *depth, int32_t K, int32_t H, int32_t W, const double *c2w, double fx, double fy, double cx, double cy,
+                         double voxel_length, double sdf_trunc, const int32_t *box, void *workspace, int64_t *n_units, void *stream);
+int nsr_tsdf_touch_emit(const float *depth, int32_t K, int32_t H, int32_t W, const double *c2w, double fx, double fy, double cx, double cy,
+                        double voxel_length, double sdf_trunc, const int32_t *box, const void *workspace, int64_t n_units, int32_t *units,
+                        uint32_t *touch, void *stream);
+int nsr_tsdf_integrate(const float *depth, int32_t K, int32_t H, int32_t W, const float *w2c, double fx, double fy, double cx, double cy,
+                       double voxel_length, double sdf_trunc, const int32_t *units, const uint32_t *touch, int64_t n_units, float *tsdf,
+                       float *weight, void *stream);
+int nsr_tsdf_surface_count(const int32_t *box, const void *workspace, const int32_t *units, int64_t n_units, const float *tsdf,
+                           const float *weight, int64_t *counts, void *stream);
+int nsr_tsdf_surface_emit(const int32_t *box, const void *workspace, const int32_t *units, int64_t n_units, const float *tsdf,
+                          const float *weight, double voxel_length, const int64_t *counts, int64_t n_points, double *points, void *stream);
+int64_t nsr_hull_partial_doubles(void);
+int nsr_hull_extremes(const double *pts, int64_t n, double *partial, int64_t *ext, void *stream);
+int nsr_hull_prefilter(const double *pts, int64_t n, const double *planes, int32_t n_planes, double margin, uint8_t *keep, void *stream);
+int nsr_convex_hull(const double *pts, int64_t n, double tol, double bound_scale, int64_t *counts, double *verts, int64_t *vert_index,
+                    int32_t *faces, double *planes);
+int nsr_hull_contains(const void *pts, int64_t n, int32_t fp64, const double *planes, int32_t n_planes, uint8_t *inside, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@ path, drop-in behind the reference's Renderer / decoder / get_samples call surfa
     from nice_slam_amd import Renderer, NICE, get_samples, grid_init, load_bound
     from nice_slam_amd import Mesher, marching_cubes
     from nice_slam_amd import recon        # eval_recon.py -3d / cull_mesh.py: calc_3d_metric, cull_mesh, nearest, ...
+    from nice_slam_amd import bound_from_frames, ConvexBound     # Mesher.get_bound_from_frames: TSDF fusion + convex hull
 
 No CPU / PyTorch fallback exists: every arithmetic entry point goes through libnsr.so.
 """
@@ -17,8 +18,11 @@ from . import graphs  # noqa: F401
 from .mesher import Mesher, marching_cubes  # noqa: F401
 from . import recon  # noqa: F401
 from .recon import align_icp, calc_3d_metric, cull_mesh, nearest, sample_surface  # noqa: F401
+from . import bound  # noqa: F401
+from .bound import ConvexBound, bound_from_frames, surface_points, tsdf_fuse  # noqa: F401
 
 __all__ = ["Renderer", "NICE", "MLP", "MLP_no_xyz", "get_samples", "get_rays", "grid_init", "load_bound",
            "to_channels_last", "MaskedGridAdam", "FlatAdam", "FrustumSelector", "aabb_keep", "get_samples_window", "mapping_loss", "tracking_loss", "seed_pixel_draws", "get_camera_from_tensor", "backward",
            "Mesher", "marching_cubes",
-           "recon", "nearest", "sample_surface", "align_icp", "calc_3d_metric", "cull_mesh"]
+           "recon", "nearest", "sample_surface", "align_icp", "calc_3d_metric", "cull_mesh",
+           "bound", "bound_from_frames", "ConvexBound", "tsdf_fuse", "surface_points"]

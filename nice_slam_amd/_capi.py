@@ -155,6 +155,27 @@ SYMBOLS = (
     ("nsr_transform_points", C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_void_p]),
     ("nsr_cull_vertices", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                     C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_tsdf_unit_box", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                    C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    ("nsr_tsdf_workspace_bytes", C.c_int64, [C.POINTER(C.c_int32)]),
+    ("nsr_tsdf_touch_count", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_tsdf_touch_emit", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                      C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    ("nsr_tsdf_integrate", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                     C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    ("nsr_tsdf_surface_count", C.c_int, [C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    ("nsr_tsdf_surface_emit", C.c_int, [C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("nsr_hull_partial_doubles", C.c_int64, []),
+    ("nsr_hull_extremes", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_hull_prefilter", C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    ("nsr_convex_hull", C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    ("nsr_hull_contains", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
 )
 
 

@@ -13,6 +13,7 @@
 // (spelled from two levels up: the library build finds it beside this file, the CPU emulator build -- which compiles a copy of
 //  this file elsewhere -- through its include path tests/emu)
 #include "../../nice_slam_amd/csrc/nsr_recon.h"
+#include "../../nice_slam_amd/csrc/nsr_bound.h"
 
 namespace {
 
@@ -1218,6 +1219,235 @@ int nsr_cull_vertices(const void *verts, int64_t n, int32_t fp64, const float *w
     if (n > 0) NSR_LAUNCH(nsr::cull_vertex_kernel, dim3(nblk(n, nsr::kCullThreads)), dim3(nsr::kCullThreads), nsr::kCullChunk * 12 * 4, stream, P);
     if (nf > 0) NSR_LAUNCH(nsr::cull_face_kernel, dim3(nblk(nf, 256)), dim3(256), 0, stream, P);
     return finish("nsr_cull_vertices");
+}
+
+}  // extern "C"
+
+// ---- mesh bound from keyframes (include/nsr.h, "Mesh bound from keyframes") ----
+namespace {
+
+constexpr long long kTsdfMaxBits = 1ll << 31;        // dense unit bitmap: at most 2^31 units (256 MB)
+
+int tsdf_setup(nsr::TsdfParams &P, const float *depth, int32_t K, int32_t H, int32_t W, const double *c2w, const float *w2c, double fx,
+               double fy, double cx, double cy, double voxel_length, double sdf_trunc, const char *what) {
+    std::memset(&P, 0, sizeof(P));
+    if (K < 1 || H < 1 || W < 1) return fail(std::string(what) + ": need at least one frame of at least 1 x 1 pixels");
+    if (!(voxel_length > 0.0) || !(sdf_trunc > 0.0) || !std::isfinite(voxel_length) || !std::isfinite(sdf_trunc))
+        return fail(std::string(what) + ": voxel_length and sdf_trunc must be positive");
+    if (!(fx != 0.0) || !(fy != 0.0)) return fail(std::string(what) + ": zero focal length");
+    P.depth = depth; P.K = K; P.H = H; P.W = W; P.c2w = c2w; P.w2c = w2c;
+    P.su = (W + nsr::kTsdfStride - 1) / nsr::kTsdfStride; P.sv = (H + nsr::kTsdfStride - 1) / nsr::kTsdfStride;
+    P.npts = (long long)K * P.su * P.sv;
+    P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.vl = voxel_length; P.ul = voxel_length * nsr::kTsdfUnit; P.trunc = sdf_trunc;
+    P.fxf = (float)fx; P.fyf = (float)fy; P.cxf = (float)cx; P.cyf = (float)cy; P.truncf = (float)sdf_trunc;
+    P.tw = (K + 31) / 32;
+    return 0;
+}
+
+// the bitmap layout for a HOST copy of the unit box; false if the box is empty or too large
+bool tsdf_box(nsr::TsdfParams &P, const int32_t *box) {
+    if (!box) return false;
+    long long bits = 1;
+    for (int d = 0; d < 3; ++d) {
+        const long long n = (long long)box[3 + d] - box[d] + 1;
+        if (n < 1 || n > (1 << 21)) return false;
+        P.lo[d] = box[d];
+        P.dim[d] = (int)n;
+        bits *= n;
+        if (bits > kTsdfMaxBits) return false;
+    }
+    P.nbits = bits;
+    P.nwords = (bits + 31) / 32;
+    P.nwblocks = (P.nwords + nsr::kBitsPerBlock - 1) / nsr::kBitsPerBlock;
+    return true;
+}
+
+long long tsdf_ws_bytes(const nsr::TsdfParams &P) { return align16(4 * P.nwords) + align16(4 * P.nwords) + align16(8 * P.nwblocks) + 16; }
+
+void tsdf_bind(nsr::TsdfParams &P, void *workspace) {
+    char *w = static_cast<char *>(workspace);
+    P.bitmap = reinterpret_cast<unsigned *>(w);
+    P.wprefix = reinterpret_cast<int *>(w + align16(4 * P.nwords));
+    P.bsum = reinterpret_cast<long long *>(w + 2 * align16(4 * P.nwords));
+    P.nunits = reinterpret_cast<long long *>(w + 2 * align16(4 * P.nwords) + align16(8 * P.nwblocks));
+}
+
+}  // namespace
+
+extern "C" {
+
+int nsr_tsdf_unit_box(const float *depth, int32_t K, int32_t H, int32_t W, const double *c2w, double fx, double fy, double cx, double cy,
+                      double voxel_length, double sdf_trunc, int32_t *box, void *stream) {
+    nsr::TsdfParams P;
+    if (int rc = tsdf_setup(P, depth, K, H, W, c2w, nullptr, fx, fy, cx, cy, voxel_length, sdf_trunc, "nsr_tsdf_unit_box")) return rc;
+    if (!depth || !c2w || !box) return fail("nsr_tsdf_unit_box: null pointer");
+    P.box = box;
+    NSR_LAUNCH(nsr::tsdf_box_init_kernel, dim3(1), dim3(64), 0, stream, P);
+    const long long nb = (P.npts + 255) / 256;
+    NSR_LAUNCH(nsr::tsdf_box_kernel, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, stream, P);
+    return finish("nsr_tsdf_unit_box");
+}
+
+int64_t nsr_tsdf_workspace_bytes(const int32_t *box) {
+    nsr::TsdfParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (!tsdf_box(P, box)) return -1;
+    return tsdf_ws_bytes(P);
+}
+
+int nsr_tsdf_touch_count(const float *depth, int32_t K, int32_t H, int32_t W, const double *c2w, double fx, double fy, double cx, double cy,
+                         double voxel_length, double sdf_trunc, const int32_t *box, void *workspace, int64_t *n_units, void *stream) {
+    nsr::TsdfParams P;
+    if (int rc = tsdf_setup(P, depth, K, H, W, c2w, nullptr, fx, fy, cx, cy, voxel_length, sdf_trunc, "nsr_tsdf_touch_count")) return rc;
+    if (!tsdf_box(P, box)) return fail("nsr_tsdf_touch_count: empty unit box, or more than 2^31 units in it");
+    if (!depth || !c2w || !workspace || !n_units) return fail("nsr_tsdf_touch_count: null pointer");
+    tsdf_bind(P, workspace);
+    P.nunits = reinterpret_cast<long long *>(n_units);
+    NSR_LAUNCH(nsr::tsdf_clear_kernel, dim3(nblk(P.nwords, 256)), dim3(256), 0, stream, P);
+    NSR_LAUNCH(nsr::tsdf_mark_kernel, dim3(nblk(P.npts, 256)), dim3(256), 0, stream, P);
+    NSR_LAUNCH(nsr::tsdf_wscan_kernel, dim3((unsigned)P.nwblocks), dim3(nsr::kBitsPerBlock), 4 * nsr::kBitsPerBlock, stream, P);
+    NSR_LAUNCH(nsr::tsdf_bscan_kernel, dim3(1), dim3(64), 0, stream, P);
+    NSR_LAUNCH(nsr::tsdf_wfix_kernel, dim3(nblk(P.nwords, 256)), dim3(256), 0, stream, P);
+    return finish("nsr_tsdf_touch_count");
+}
+
+int nsr_tsdf_touch_emit(const float *depth, int32_t K, int32_t H, int32_t W, const double *c2w, double fx, double fy, double cx, double cy,
+                        double voxel_length, double sdf_trunc, const int32_t *box, const void *workspace, int64_t n_units, int32_t *units,
+                        uint32_t *touch, void *stream) {
+    nsr::TsdfParams P;
+    if (int rc = tsdf_setup(P, depth, K, H, W, c2w, nullptr, fx, fy, cx, cy, voxel_length, sdf_trunc, "nsr_tsdf_touch_emit")) return rc;
+    if (!tsdf_box(P, box)) return fail("nsr_tsdf_touch_emit: empty unit box, or more than 2^31 units in it");
+    if (n_units < 0 || n_units > P.nbits) return fail("nsr_tsdf_touch_emit: unit count out of range");
+    if (n_units == 0) return 0;
+    if (!depth || !c2w || !workspace || !units || !touch) return fail("nsr_tsdf_touch_emit: null pointer");
+    tsdf_bind(P, const_cast<void *>(workspace));
+    P.n_units = n_units; P.units = units; P.touch = touch;
+    NSR_LAUNCH(nsr::tsdf_units_kernel, dim3(nblk(P.nwords, 256)), dim3(256), 0, stream, P);
+    NSR_LAUNCH(nsr::tsdf_touch_kernel, dim3(nblk(P.npts, 256)), dim3(256), 0, stream, P);
+    return finish("nsr_tsdf_touch_emit");
+}
+
+int nsr_tsdf_integrate(const float *depth, int32_t K, int32_t H, int32_t W, const float *w2c, double fx, double fy, double cx, double cy,
+                       double voxel_length, double sdf_trunc, const int32_t *units, const uint32_t *touch, int64_t n_units, float *tsdf,
+                       float *weight, void *stream) {
+    nsr::TsdfParams P;
+    if (int rc = tsdf_setup(P, depth, K, H, W, nullptr, w2c, fx, fy, cx, cy, voxel_length, sdf_trunc, "nsr_tsdf_integrate")) return rc;
+    if (n_units < 0 || n_units > 2147483647ll) return fail("nsr_tsdf_integrate: unit count out of range");
+    if (n_units == 0) return 0;
+    if (!depth || !w2c || !units || !touch || !tsdf || !weight) return fail("nsr_tsdf_integrate: null pointer");
+    P.units = const_cast<int *>(units); P.touch = const_cast<unsigned *>(touch); P.n_units = n_units; P.tsdf = tsdf; P.weight = weight;
+    NSR_LAUNCH(nsr::tsdf_integrate_kernel, dim3((unsigned)n_units), dim3(nsr::kTsdfThreads), 0, stream, P);
+    return finish("nsr_tsdf_integrate");
+}
+
+int nsr_tsdf_surface_count(const int32_t *box, const void *workspace, const int32_t *units, int64_t n_units, const float *tsdf,
+                           const float *weight, int64_t *counts, void *stream) {
+    nsr::TsdfParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (!tsdf_box(P, box)) return fail("nsr_tsdf_surface_count: empty unit box, or more than 2^31 units in it");
+    if (n_units < 0 || n_units > P.nbits) return fail("nsr_tsdf_surface_count: unit count out of range");
+    if (!counts) return fail("nsr_tsdf_surface_count: null pointer");
+    if (n_units > 0 && (!workspace || !units || !tsdf || !weight)) return fail("nsr_tsdf_surface_count: null pointer");
+    tsdf_bind(P, const_cast<void *>(workspace));
+    P.units = const_cast<int *>(units); P.n_units = n_units;
+    P.tsdf = const_cast<float *>(tsdf); P.weight = const_cast<float *>(weight); P.counts = reinterpret_cast<long long *>(counts);
+    if (n_units > 0)
+        NSR_LAUNCH(nsr::tsdf_surface_kernel<false>, dim3((unsigned)n_units), dim3(nsr::kTsdfThreads), 4 * (nsr::kTsdfThreads + 1), stream, P);
+    NSR_LAUNCH(nsr::tsdf_count_scan_kernel, dim3(1), dim3(64), 0, stream, P);
+    return finish("nsr_tsdf_surface_count");
+}
+
+int nsr_tsdf_surface_emit(const int32_t *box, const void *workspace, const int32_t *units, int64_t n_units, const float *tsdf,
+                          const float *weight, double voxel_length, const int64_t *counts, int64_t n_points, double *points, void *stream) {
+    nsr::TsdfParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (!tsdf_box(P, box)) return fail("nsr_tsdf_surface_emit: empty unit box, or more than 2^31 units in it");
+    if (n_units < 0 || n_units > P.nbits || n_points < 0) return fail("nsr_tsdf_surface_emit: count out of range");
+    if (!(voxel_length > 0.0) || !std::isfinite(voxel_length)) return fail("nsr_tsdf_surface_emit: voxel_length must be positive");
+    if (n_points == 0 || n_units == 0) return 0;
+    if (!workspace || !units || !tsdf || !weight || !counts || !points) return fail("nsr_tsdf_surface_emit: null pointer");
+    tsdf_bind(P, const_cast<void *>(workspace));
+    P.units = const_cast<int *>(units); P.n_units = n_units;
+    P.tsdf = const_cast<float *>(tsdf); P.weight = const_cast<float *>(weight);
+    P.counts = const_cast<long long *>(reinterpret_cast<const long long *>(counts)); P.points = points;
+    P.vl = voxel_length; P.ul = voxel_length * nsr::kTsdfUnit;
+    NSR_LAUNCH(nsr::tsdf_surface_kernel<true>, dim3((unsigned)n_units), dim3(nsr::kTsdfThreads), 4 * (nsr::kTsdfThreads + 1), stream, P);
+    return finish("nsr_tsdf_surface_emit");
+}
+
+int64_t nsr_hull_partial_doubles(void) { return 2ll * nsr::kHullBlocks * nsr::kHullDirs; }
+
+int nsr_hull_extremes(const double *pts, int64_t n, double *partial, int64_t *ext, void *stream) {
+    if (n < 1) return fail("nsr_hull_extremes: no points");
+    if (!pts || !partial || !ext) return fail("nsr_hull_extremes: null pointer");
+    nsr::HullParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.pts = pts; P.n = n; P.fp64 = 1; P.partial = partial; P.ext = reinterpret_cast<long long *>(ext);
+    NSR_LAUNCH(nsr::hull_extreme_kernel, dim3(nsr::kHullBlocks), dim3(256), 256 * 16, stream, P);
+    NSR_LAUNCH(nsr::hull_extreme_final_kernel, dim3(1), dim3(64), 0, stream, P);
+    return finish("nsr_hull_extremes");
+}
+
+int nsr_hull_prefilter(const double *pts, int64_t n, const double *planes, int32_t n_planes, double margin, uint8_t *keep, void *stream) {
+    if (n < 0 || n_planes < 0 || n_planes > nsr::kHullMaxPlanes) return fail("nsr_hull_prefilter: count out of range (at most 64 planes)");
+    if (!(margin >= 0.0)) return fail("nsr_hull_prefilter: negative margin");
+    if (n == 0) return 0;
+    if (!pts || !keep || (n_planes > 0 && !planes)) return fail("nsr_hull_prefilter: null pointer");
+    nsr::HullParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.pts = pts; P.n = n; P.fp64 = 1; P.n_planes = n_planes; P.margin = margin; P.out = keep;
+    for (int j = 0; j < n_planes; ++j)
+        for (int e = 0; e < 4; ++e) P.planes[j][e] = planes[4 * j + e];
+    NSR_LAUNCH(nsr::hull_prefilter_kernel, dim3(nblk(n, 256)), dim3(256), 0, stream, P);
+    return finish("nsr_hull_prefilter");
+}
+
+int nsr_convex_hull(const double *pts, int64_t n, double tol, double bound_scale, int64_t *counts, double *verts, int64_t *vert_index,
+                    int32_t *faces, double *planes) {
+    if (n < 0 || n > 2147483647ll) return fail("nsr_convex_hull: point count out of range");
+    if (!(tol >= 0.0) || !(bound_scale > 0.0) || !std::isfinite(bound_scale)) return fail("nsr_convex_hull: tol must be >= 0, bound_scale > 0");
+    if (!pts || !counts || !verts || !vert_index || !faces || !planes) return fail("nsr_convex_hull: null pointer");
+    for (long long i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(pts[i])) return fail("nsr_convex_hull: non-finite coordinates");
+    std::vector<nsr::HullFace> F;
+    const int rc = nsr::hull_build(pts, n, tol, F);
+    if (rc == -1) return fail("nsr_convex_hull: the points span no volume (fewer than 4, or all within tol of a plane)");
+    if (rc != 0) return fail("nsr_convex_hull: the hull surface did not close (numerical breakdown)");
+    std::vector<int> remap((size_t)n, -1);
+    for (const auto &f : F)
+        if (f.alive)
+            for (int e = 0; e < 3; ++e) remap[f.v[e]] = 0;
+    long long nv = 0, nf = 0;
+    for (long long i = 0; i < n; ++i)
+        if (remap[i] == 0) { remap[i] = (int)nv; vert_index[nv] = i; ++nv; }
+    double c[3] = {0.0, 0.0, 0.0};
+    for (long long v = 0; v < nv; ++v)
+        for (int d = 0; d < 3; ++d) c[d] += pts[3 * vert_index[v] + d];
+    for (int d = 0; d < 3; ++d) c[d] /= (double)nv;
+    for (long long v = 0; v < nv; ++v)
+        for (int d = 0; d < 3; ++d) verts[3 * v + d] = (pts[3 * vert_index[v] + d] - c[d]) * bound_scale + c[d];
+    for (const auto &f : F) {
+        if (!f.alive) continue;
+        nsr::HullFace g;
+        for (int e = 0; e < 3; ++e) { faces[3 * nf + e] = remap[f.v[e]]; g.v[e] = remap[f.v[e]]; }
+        nsr::hull_plane(verts, g);
+        for (int e = 0; e < 3; ++e) planes[4 * nf + e] = g.n[e];
+        planes[4 * nf + 3] = g.off;
+        ++nf;
+    }
+    counts[0] = nv; counts[1] = nf;
+    return 0;
+}
+
+int nsr_hull_contains(const void *pts, int64_t n, int32_t fp64, const double *planes, int32_t n_planes, uint8_t *inside, void *stream) {
+    if (n < 0 || n_planes < 0) return fail("nsr_hull_contains: negative count");
+    if (n == 0) return 0;
+    if (!pts || !inside || (n_planes > 0 && !planes)) return fail("nsr_hull_contains: null pointer");
+    nsr::HullParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.pts = pts; P.n = n; P.fp64 = fp64 ? 1 : 0; P.dplanes = planes; P.n_planes = n_planes; P.out = inside;
+    NSR_LAUNCH(nsr::hull_contains_kernel, dim3(nblk(n, 256)), dim3(256), nsr::kContainsChunk * 4 * 8, stream, P);
+    return finish("nsr_hull_contains");
 }
 
 }  // extern "C"

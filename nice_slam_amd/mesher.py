@@ -8,9 +8,10 @@ nsr_mc_emit), face areas and the union-find over faces that share an edge (nsr_f
 torch does the plumbing: lattice coordinates, boolean indexing, sorting edge keys, compaction.
 
 Deviations from the reference (also in INTEGRATION.md):
-  * ``get_bound_from_frames`` (:214-279) needs Open3D's TSDF fusion and a convex hull: it raises NotImplementedError.
-    ``get_mesh(..., mesh_bound=...)`` takes its place: None (everything is inside) or a callable
-    ``contains(np.ndarray [N,3]) -> bool [N]``, e.g. the ``contains`` of a user's trimesh hull.
+  * ``get_bound_from_frames`` (:214-279) raises NotImplementedError; ``bound_from_frames`` (nice_slam_amd/bound.py) builds the
+    same hull on the GPU and returns a ``ConvexBound``.  ``get_mesh(..., mesh_bound=...)`` takes: None (everything is
+    inside), "frames" (the bound of ``keyframe_dict``, built on the GPU: the reference's default), a ``ConvexBound`` (tested on
+    the device), or a callable ``contains(np.ndarray [N,3]) -> bool [N]``, e.g. the ``contains`` of a user's trimesh hull.
   * ``color_mesh_extraction_method == 'render_ray_along_normal'`` is iMAP* only and raises NotImplementedError.
   * The marching-cubes table is this project's own (crack-free, tests/mesh_reference.py); vertex and face order follow the
     lattice, not skimage's, and the kept faces keep their order (trimesh regroups them by component).  No vertices are
@@ -26,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from .bound import ConvexBound, bound_from_frames
 from .common import _require_cuda, _stream
 from .renderer import eval_points_raw
 
@@ -238,8 +240,20 @@ class Mesher:
 
     # ---- the reference's methods ----
     def get_bound_from_frames(self, keyframe_dict, scale=1):
-        raise NotImplementedError("Mesher.get_bound_from_frames needs Open3D's TSDF fusion and convex hull; pass "
-                                  "get_mesh(..., mesh_bound=<callable contains(points) -> bool>) instead")
+        raise NotImplementedError("Mesher.get_bound_from_frames needs Open3D's TSDF fusion and convex hull; use "
+                                  "Mesher.bound_from_frames (the same bound, built on the GPU) or get_mesh(..., mesh_bound=\"frames\")")
+
+    def bound_from_frames(self, keyframe_dict, scale=1):
+        """Mesher.py:214-279 on the GPU (nice_slam_amd/bound.py) -> ConvexBound: the hull of the camera centres and the TSDF mesh
+        vertices of the keyframes, scaled by meshing.clean_mesh_bound_scale about the mean of its vertices."""
+        return bound_from_frames(keyframe_dict, self.H, self.W, self.fx, self.fy, self.cx, self.cy, scale, self.clean_mesh_bound_scale)
+
+    @staticmethod
+    def _inside(mesh_bound, points: torch.Tensor) -> torch.Tensor:
+        """bool [N] on points' device: a ConvexBound runs on the device, a plain callable gets numpy slabs"""
+        if isinstance(mesh_bound, ConvexBound):
+            return mesh_bound.contains(points)
+        return torch.from_numpy(np.asarray(mesh_bound(points.cpu().numpy()), dtype=bool)).to(points.device)
 
     def get_grid_uniform(self, resolution, device="cpu"):
         """Mesher.py:322-347: {"grid_points": fp32 [R^3,3] in np.meshgrid order (y slowest, then x, then z), "xyz": [x, y, z]}"""
@@ -282,10 +296,18 @@ class Mesher:
                  timer=None):
         """Mesher.py:349-574.  Writes a binary PLY and returns (vertices / scale fp64 [V,3], faces int32 [F,3], colours uint8
         [V,3] or None) on the device; None (and no file) when the level set has no surface.  ``mesh_bound`` replaces
-        get_bound_from_frames (see the module docstring).  ``timer``: optional callable(phase_name) invoked after each phase
-        (tools/mesh_timing.py)."""
+        get_bound_from_frames (see the module docstring; "frames" builds it from keyframe_dict when a branch needs it).
+        ``timer``: optional callable(phase_name) invoked after each phase (tools/mesh_timing.py)."""
         tick = timer or (lambda name: None)
         dev = torch.device(device)
+        if isinstance(mesh_bound, str):
+            if mesh_bound != "frames":
+                raise ValueError(f"get_mesh: mesh_bound must be None, \"frames\", a ConvexBound or a callable (got {mesh_bound!r})")
+            if show_forecast and not clean_mesh:
+                mesh_bound = None                                          # no branch reads it
+            else:
+                mesh_bound = self.bound_from_frames(keyframe_dict, self.scale)
+                tick("bound")
         with torch.no_grad():
             grid = self.get_grid_uniform(self.resolution, device=dev)
             points = grid["grid_points"]
@@ -300,9 +322,8 @@ class Mesher:
             else:
                 z = torch.cat([self.eval_points(pi, decoders, c, "fine", dev)[:, -1] for pi in torch.split(points, self.points_batch_size)])
                 if mesh_bound is not None:
-                    inside = np.concatenate([np.asarray(mesh_bound(pi.cpu().numpy()), dtype=bool)
-                                             for pi in torch.split(points, self.points_batch_size)])
-                    z[~torch.from_numpy(inside).to(dev)] = 100.0
+                    inside = torch.cat([self._inside(mesh_bound, pi) for pi in torch.split(points, self.points_batch_size)])
+                    z[~inside] = 100.0
             tick("query")
             vol = z.reshape(R[1], R[0], R[2]).permute(1, 0, 2).contiguous()          # :440-441
             spacing = [a[2] - a[1] for a in grid["xyz"]]
@@ -315,7 +336,7 @@ class Mesher:
             if clean_mesh:
                 if show_forecast:
                     if mesh_bound is not None:
-                        inside = torch.from_numpy(np.asarray(mesh_bound(verts.cpu().numpy()), dtype=bool)).to(dev)
+                        inside = self._inside(mesh_bound, verts)
                         faces = faces[~(~inside)[faces.long()].all(1)]
                 else:
                     code = self._mask_codes(verts, keyframe_dict, estimate_c2w_list, idx, dev, get_mask_use_all_frames)
