@@ -26,6 +26,8 @@
  *   nsr_mc_* / nsr_point_masks / nsr_cc_* <- src/utils/Mesher.py:53-212,349-574  marching cubes, point_masks, mesh.split
  *   nsr_nn_* / nsr_sample_surface / nsr_dist_stats / nsr_icp_stats / nsr_transform_points / nsr_cull_vertices
  *                        <- src/tools/eval_recon.py:24-59,91-117, src/tools/cull_mesh.py:45-75  reconstruction evaluation
+ *   nsr_raster_* / nsr_depth_error / nsr_view_unseen
+ *                        <- src/tools/eval_recon.py:131-211  depth rendering and the 2-D depth metric
  *
  * Conventions
  *   - all pointers are DEVICE pointers owned by the caller (PyTorch); the library never frees or
@@ -507,6 +509,33 @@ int nsr_hull_prefilter(const double *pts, int64_t n, const double *planes, int32
 int nsr_convex_hull(const double *pts, int64_t n, double tol, double bound_scale, int64_t *counts, double *verts, int64_t *vert_index,
                     int32_t *faces, double *planes);
 int nsr_hull_contains(const void *pts, int64_t n, int32_t fp64, const double *planes, int32_t n_planes, uint8_t *inside, void *stream);
+
+/* --- Depth rasterization and the 2-D depth metric (src/tools/eval_recon.py:131-211, calc_2d_metric and check_proj) ----------
+ * A tiled z-buffer rasterizer for triangle meshes; the numerical contract is written out in nice_slam_amd/csrc/nsr_raster.h.
+ * verts [n_verts][3] fp32, faces [n_faces][3] int32 (a face with an index outside [0, n_verts) draws nothing), w2c [K][12] fp32:
+ * rows 0..2 of inv(c2w) taken in fp64, c2w in the OpenCV convention (x right, y down, z forward).  Intrinsics fx, fy, cx, cy;
+ * images H x W, at most 1024 x 1024; 0 < near < far.  Two calls per batch of views:
+ *   nsr_raster_workspace_bytes  device workspace of both calls (-1: invalid sizes)
+ *   nsr_raster_bin              camera-space vertices, pixel boxes and the per-tile entry counts into the workspace; n_entries
+ *                               [1] int64 (device) out: the number of (tile, triangle) entries of all K views
+ *   nsr_raster_depth            with bins [n_entries] int32 of device scratch: the entries in (view, tile, triangle) order, then
+ *                               depth [K][H][W] fp32 (0 where nothing is drawn).  Bit-identical run to run.
+ *   nsr_depth_error                per view k: the mean over n_pixels of |a - b| (fp64, fixed order) into out [K] fp64; partial:
+ *                               nsr_depth_error_partial_doubles(K, n_pixels) doubles of device scratch
+ *   nsr_view_unseen             check_proj for K candidate poses: sees [K] uint8 = 1 iff some point of pts [n][3] (fp32 / fp64)
+ *                               projects into the image; w2c [K][12] fp32: rows 0..2 of inv of the FLIPPED c2w (y, z columns
+ *                               negated), as nsr_cull_vertices. */
+int64_t nsr_raster_workspace_bytes(int64_t n_verts, int64_t n_faces, int32_t K, int32_t H, int32_t W);
+int nsr_raster_bin(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *w2c, int32_t K, int32_t H,
+                   int32_t W, double fx, double fy, double cx, double cy, double near, double far, void *workspace, int64_t *n_entries,
+                   void *stream);
+int nsr_raster_depth(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *w2c, int32_t K, int32_t H,
+                     int32_t W, double fx, double fy, double cx, double cy, double near, double far, void *workspace, int32_t *bins,
+                     int64_t n_entries, float *depth, void *stream);
+int64_t nsr_depth_error_partial_doubles(int32_t K, int64_t n_pixels);
+int nsr_depth_error(const float *a, const float *b, int32_t K, int64_t n_pixels, double *partial, double *out, void *stream);
+int nsr_view_unseen(const void *pts, int64_t n, int32_t fp64, const float *w2c, int32_t K, int32_t H, int32_t W, double fx, double fy,
+                    double cx, double cy, uint8_t *sees, void *stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@ path, drop-in behind the reference's Renderer / decoder / get_samples call surfa
 
     from nice_slam_amd import Renderer, NICE, get_samples, grid_init, load_bound
     from nice_slam_amd import Mesher, marching_cubes
-    from nice_slam_amd import recon        # eval_recon.py -3d / cull_mesh.py: calc_3d_metric, cull_mesh, nearest, ...
+    from nice_slam_amd import recon        # eval_recon.py / cull_mesh.py: calc_3d_metric, calc_2d_metric, render_depth, cull_mesh, ...
     from nice_slam_amd import bound_from_frames, ConvexBound     # Mesher.get_bound_from_frames: TSDF fusion + convex hull
 
 No CPU / PyTorch fallback exists: every arithmetic entry point goes through libnsr.so.

@@ -176,6 +176,17 @@ SYMBOLS = (
     ("nsr_convex_hull", C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
     ("nsr_hull_contains", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("nsr_raster_workspace_bytes", C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    ("nsr_raster_bin", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                 C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
+    ("nsr_raster_depth", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                   C.c_int64, C.c_void_p, C.c_void_p]),
+    ("nsr_depth_error_partial_doubles", C.c_int64, [C.c_int32, C.c_int64]),
+    ("nsr_depth_error", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_view_unseen", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                  C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
 )
 
 

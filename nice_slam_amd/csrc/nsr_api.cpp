@@ -14,6 +14,7 @@
 //  this file elsewhere -- through its include path tests/emu)
 #include "../../nice_slam_amd/csrc/nsr_recon.h"
 #include "../../nice_slam_amd/csrc/nsr_bound.h"
+#include "../../nice_slam_amd/csrc/nsr_raster.h"
 
 namespace {
 
@@ -1448,6 +1449,135 @@ int nsr_hull_contains(const void *pts, int64_t n, int32_t fp64, const double *pl
     P.pts = pts; P.n = n; P.fp64 = fp64 ? 1 : 0; P.dplanes = planes; P.n_planes = n_planes; P.out = inside;
     NSR_LAUNCH(nsr::hull_contains_kernel, dim3(nblk(n, 256)), dim3(256), nsr::kContainsChunk * 4 * 8, stream, P);
     return finish("nsr_hull_contains");
+}
+
+}  // extern "C"
+
+// ---- depth rasterization and the 2-D depth metric (include/nsr.h, "Depth rasterization") ----
+namespace {
+
+struct RasterLayout { long long cam, rect, counts, start, total; };
+
+bool raster_sizes(nsr::RasterParams &P, int64_t nv, int64_t nf, int32_t K, int32_t H, int32_t W) {
+    if (nv < 1 || nf < 1 || K < 1 || H < 1 || W < 1 || H > nsr::kRasterMaxTiles || W > nsr::kRasterMaxTiles) return false;
+    if (nv > 2147483647ll || nf > 2147483647ll) return false;
+    P.nv = nv; P.nf = nf; P.K = K; P.H = H; P.W = W;
+    P.tx = (W + nsr::kRasterTile - 1) / nsr::kRasterTile;
+    P.ty = (H + nsr::kRasterTile - 1) / nsr::kRasterTile;
+    P.ntiles = P.tx * P.ty;
+    P.nchunks = (nf + nsr::kRasterChunk - 1) / nsr::kRasterChunk;
+    return true;
+}
+
+RasterLayout raster_layout(const nsr::RasterParams &P) {
+    RasterLayout L;
+    L.cam = 0;
+    L.rect = L.cam + align16(16ll * P.K * P.nv);
+    L.counts = L.rect + align16(8ll * P.K * P.nf);
+    L.start = L.counts + align16(4ll * P.K * P.ntiles * P.nchunks);
+    L.total = L.start + align16(8ll * ((long long)P.K * P.ntiles + 1));
+    return L;
+}
+
+int raster_setup(nsr::RasterParams &P, const float *verts, int64_t nv, const int32_t *faces, int64_t nf, const float *w2c, int32_t K,
+                 int32_t H, int32_t W, double fx, double fy, double cx, double cy, double near, double far, void *workspace,
+                 const char *what) {
+    std::memset(&P, 0, sizeof(P));
+    if (nv < 1 || nf < 1) return fail(std::string(what) + ": empty mesh");
+    if (K < 1) return fail(std::string(what) + ": no views");
+    if (!raster_sizes(P, nv, nf, K, H, W)) return fail(std::string(what) + ": image sizes must be 1..1024, at most 2^31 - 1 vertices and faces");
+    if (!(near > 0.0) || !(far > near) || !std::isfinite(far) || far > 1e30) return fail(std::string(what) + ": need 0 < near < far (finite)");
+    if (!(fx != 0.0) || !(fy != 0.0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail(std::string(what) + ": focal lengths must be finite and non-zero");
+    if (!verts || !faces || !w2c || !workspace) return fail(std::string(what) + ": null pointer");
+    P.verts = verts; P.faces = faces; P.w2c = w2c;
+    P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.near = near; P.far = far;
+    P.fxf = (float)fx; P.fyf = (float)fy; P.cxf = (float)cx; P.cyf = (float)cy; P.nearf = (float)near; P.farf = (float)far;
+    const RasterLayout L = raster_layout(P);
+    char *w = static_cast<char *>(workspace);
+    P.cam = reinterpret_cast<float *>(w + L.cam);
+    P.rect = reinterpret_cast<int *>(w + L.rect);
+    P.counts = reinterpret_cast<int *>(w + L.counts);
+    P.tile_start = reinterpret_cast<long long *>(w + L.start);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nsr_raster_workspace_bytes(int64_t n_verts, int64_t n_faces, int32_t K, int32_t H, int32_t W) {
+    nsr::RasterParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (!raster_sizes(P, n_verts, n_faces, K, H, W)) return -1;
+    return raster_layout(P).total;
+}
+
+int nsr_raster_bin(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *w2c, int32_t K, int32_t H,
+                   int32_t W, double fx, double fy, double cx, double cy, double near, double far, void *workspace, int64_t *n_entries,
+                   void *stream) {
+    nsr::RasterParams P;
+    if (int rc = raster_setup(P, verts, n_verts, faces, n_faces, w2c, K, H, W, fx, fy, cx, cy, near, far, workspace, "nsr_raster_bin")) return rc;
+    if (!n_entries) return fail("nsr_raster_bin: null pointer");
+    P.n_entries = reinterpret_cast<long long *>(n_entries);
+    const int T = nsr::kRasterThreads;
+    NSR_LAUNCH(nsr::raster_vertex_kernel, dim3(nblk(P.nv, T), K), dim3(T), 0, stream, P);
+    NSR_LAUNCH(nsr::raster_setup_kernel, dim3(nblk(P.nf, T), K), dim3(T), 0, stream, P);
+    NSR_LAUNCH(nsr::raster_count_kernel, dim3((unsigned)P.nchunks, K), dim3(T), 4 * 4 * P.ntiles, stream, P);
+    NSR_LAUNCH(nsr::raster_scan_tile_kernel, dim3(P.ntiles, K), dim3(T), 2 * 4 * T, stream, P);
+    NSR_LAUNCH(nsr::raster_scan_view_kernel, dim3(1), dim3(T), 8 * T, stream, P);
+    return finish("nsr_raster_bin");
+}
+
+int nsr_raster_depth(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *w2c, int32_t K, int32_t H,
+                     int32_t W, double fx, double fy, double cx, double cy, double near, double far, void *workspace, int32_t *bins,
+                     int64_t n_entries, float *depth, void *stream) {
+    nsr::RasterParams P;
+    if (int rc = raster_setup(P, verts, n_verts, faces, n_faces, w2c, K, H, W, fx, fy, cx, cy, near, far, workspace, "nsr_raster_depth")) return rc;
+    if (n_entries < 0) return fail("nsr_raster_depth: negative entry count");
+    if (!depth || (n_entries > 0 && !bins)) return fail("nsr_raster_depth: null pointer");
+    P.bins = bins; P.depth = depth; P.cap = n_entries;
+    const int T = nsr::kRasterThreads;
+    // (n_entries is what nsr_raster_bin counted into the same workspace: the emit writes exactly that many)
+    if (n_entries > 0) NSR_LAUNCH(nsr::raster_emit_kernel, dim3((unsigned)P.nchunks, K), dim3(T), 4 * 4 * P.ntiles, stream, P);
+    NSR_LAUNCH(nsr::raster_resolve_kernel, dim3(P.ntiles, K), dim3(T), nsr::kRasterResolveLds, stream, P);
+    return finish("nsr_raster_depth");
+}
+
+int64_t nsr_depth_error_partial_doubles(int32_t K, int64_t n_pixels) {
+    if (K < 1 || n_pixels < 1) return -1;
+    return (long long)K * ((n_pixels + nsr::kRasterThreads - 1) / nsr::kRasterThreads);
+}
+
+int nsr_depth_error(const float *a, const float *b, int32_t K, int64_t n_pixels, double *partial, double *out, void *stream) {
+    if (K < 1 || n_pixels < 1) return fail("nsr_depth_error: need at least one view of at least one pixel");
+    if (!a || !b || !partial || !out) return fail("nsr_depth_error: null pointer");
+    nsr::L1Params P;
+    std::memset(&P, 0, sizeof(P));
+    P.a = a; P.b = b; P.n = n_pixels; P.K = K; P.partial = partial; P.out = out;
+    P.nblocks = (n_pixels + nsr::kRasterThreads - 1) / nsr::kRasterThreads;
+    const int T = nsr::kRasterThreads;
+    NSR_LAUNCH(nsr::raster_l1_kernel, dim3((unsigned)P.nblocks, K), dim3(T), 8 * T, stream, P);
+    NSR_LAUNCH(nsr::raster_l1_final_kernel, dim3(nblk(K, T)), dim3(T), 0, stream, P);
+    return finish("nsr_depth_error");
+}
+
+int nsr_view_unseen(const void *pts, int64_t n, int32_t fp64, const float *w2c, int32_t K, int32_t H, int32_t W, double fx, double fy,
+                    double cx, double cy, uint8_t *sees, void *stream) {
+    if (n < 0 || K < 1) return fail("nsr_view_unseen: need at least one candidate and a non-negative point count");
+    if (n > 2147483647ll) return fail("nsr_view_unseen: more than 2^31 - 1 points");
+    if (H < 1 || W < 1) return fail("nsr_view_unseen: empty image");
+    if (!w2c || !sees || (n > 0 && !pts)) return fail("nsr_view_unseen: null pointer");
+    nsr::ViewParams V;
+    std::memset(&V, 0, sizeof(V));
+    V.C.verts = pts; V.C.n = n; V.C.fp64 = fp64 ? 1 : 0; V.C.K = K; V.C.w2c = w2c;
+    const double km[9] = {fx, 0.0, cx, 0.0, fy, cy, 0.0, 0.0, 1.0};
+    for (int i = 0; i < 9; ++i) V.C.kf[i] = (float)km[i];
+    V.C.W = (float)W; V.C.H = (float)H; V.sees = sees;
+    const int T = nsr::kRasterThreads;
+    NSR_LAUNCH(nsr::raster_view_clear_kernel, dim3(nblk(K, T)), dim3(T), 0, stream, V);
+    if (n > 0) NSR_LAUNCH(nsr::raster_view_kernel, dim3(nblk(n, T)), dim3(T), nsr::kRasterViewChunk * 12 * 4, stream, V);
+    return finish("nsr_view_unseen");
 }
 
 }  // extern "C"

@@ -1,0 +1,368 @@
+"""Depth rendering of triangle meshes on the GPU and the 2-D depth metric of the reference's ``src/tools/eval_recon.py``
+(``calc_2d_metric``, :131-211, with ``get_cam_position``, ``viewmatrix`` and ``check_proj``).  Re-exported by
+``nice_slam_amd.recon``.
+
+    from nice_slam_amd import recon
+    depth = recon.render_depth(vertices, faces, c2w)              # [K, 500, 500] fp32 device tensor, 0 = background
+    recon.calc_2d_metric("rec.ply", "gt.ply")                      # {"depth_l1_cm": ..., "per_view": ...}
+
+    python -m nice_slam_amd.recon depth --rec_mesh R --gt_mesh G
+
+Every per-pixel and per-point loop runs in libnsr.so (include/nsr.h, "Depth rasterization"; the rules are written out in
+csrc/nsr_raster.h): a tiled z-buffer rasterizer (nsr_raster_bin, nsr_raster_depth), the per-view depth L1 (nsr_depth_error) and
+the candidate-view test (nsr_view_unseen).  The oriented box of the camera positions is the library's fp64 convex hull plus
+a minimum-area rectangle per hull-face normal on the host.
+
+Deviations from the reference (also in INTEGRATION.md):
+  * not Open3D's OpenGL depth buffer: depth is the exact ray-plane depth rounded once to fp32 (no 24-bit depth quantization),
+    coverage is a ray-triangle test that counts boundary pixels as covered (no GL fill rule);
+  * near plane 0.01 x the largest axis-aligned extent of the mesh being rendered (Open3D's ViewControl rule for a camera
+    inside the bounding box, recalled from its source), far plane 20;
+  * the view stream is a seeded numpy Generator (the reference draws from the unseeded ``random`` / numpy streams);
+  * the oriented box orders its axes by ascending extent (trimesh's ``oriented_bounds(ordered=True)`` as recalled; trimesh
+    is not used) with each of the two shorter axes pointing to the positive side of its largest component.
+"""
+from __future__ import annotations
+
+import os
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _capi
+from . import bound as _bound
+from .recon import Engine, _faces, _gpu, _transform, align_icp, read_mesh
+
+__all__ = ["render_depth", "depth_l1", "oriented_bounds", "cam_position", "viewmatrix", "view_draws", "views_from_draws",
+           "views_unseen", "sample_views", "calc_2d_metric"]
+
+H_REF, W_REF, FOCAL_REF = 500, 500, 300.0          # eval_recon.py:135-142
+FAR_REF = 20.0                                     # ctr.set_constant_z_far(20)
+NEAR_REL = 0.01                                    # near = 0.01 x the mesh's largest extent
+MAX_VIEWS_PER_LAUNCH = 64
+
+
+def _c2w_stack(c2w) -> np.ndarray:
+    m = c2w.detach().cpu().numpy() if isinstance(c2w, torch.Tensor) else np.asarray(c2w)
+    m = np.asarray(m, np.float64)
+    if m.shape == (4, 4):
+        m = m[None]
+    if m.ndim != 3 or m.shape[1:] != (4, 4):
+        raise ValueError(f"c2w must be [4, 4] or [K, 4, 4] (got {m.shape})")
+    return m
+
+
+def _w2c_rows(c2w: np.ndarray) -> np.ndarray:
+    """[K, 12] fp32: rows 0..2 of inv(c2w) taken in fp64"""
+    return np.ascontiguousarray(np.linalg.inv(c2w)[:, :3].reshape(len(c2w), 12).astype(np.float32))
+
+
+def max_extent(vertices) -> float:
+    """the largest axis-aligned extent of a vertex set (fp64)"""
+    v = vertices if isinstance(vertices, torch.Tensor) else torch.from_numpy(np.asarray(vertices))
+    v = v.detach().to(torch.float64)
+    if v.numel() == 0:
+        return 0.0
+    return float((v.amax(0) - v.amin(0)).max())
+
+
+def _views_per_launch(E: Engine, nv: int, nf: int, H: int, W: int) -> int:
+    ntiles = ((W + 31) // 32) * ((H + 31) // 32)
+    per_view = 16 * nv + 8 * nf + 4 * ntiles * ((nf + 255) // 256) + 8 * ntiles + 16 * nf + 4 * H * W
+    if E.device.type != "cuda":
+        return 8
+    free = torch.cuda.mem_get_info(E.device)[0]
+    return int(max(1, min(MAX_VIEWS_PER_LAUNCH, free // 4 // per_view)))
+
+
+def render_depth(vertices, faces, c2w, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_REF, cx=249.5, cy=249.5, near=None, far=FAR_REF,
+                 engine: Optional[Engine] = None) -> torch.Tensor:
+    """Depth images [K, H, W] fp32 on the engine's device of the mesh (vertices [V, 3], faces [F, 3]) seen from each c2w
+    ([4, 4] or [K, 4, 4], OpenCV convention: x right, y down, z forward).  Depth is camera-space z, 0 where nothing is drawn;
+    fragments outside [near, far] are discarded; near defaults to 0.01 x the mesh's largest axis-aligned extent."""
+    E = engine or _gpu()
+    lib = E.lib
+    v = E.tensor(vertices, torch.float32, "render_depth: vertices")
+    f = _faces(E, faces)
+    c2w = _c2w_stack(c2w)
+    K = len(c2w)
+    if v.shape[0] == 0 or f.shape[0] == 0:
+        raise _capi.NsrError("render_depth: empty mesh")
+    if K == 0:
+        raise _capi.NsrError("render_depth: no views")
+    lo, hi = int(f.min()), int(f.max())
+    if lo < 0 or hi >= v.shape[0]:
+        raise _capi.NsrError(f"render_depth: face indices out of range [0, {v.shape[0]}) (found {lo}..{hi})")
+    if near is None:
+        near = NEAR_REL * max_extent(vertices)
+    if not near > 0.0:
+        raise _capi.NsrError(f"render_depth: near must be positive (got {near})")
+    w2c = torch.from_numpy(_w2c_rows(c2w)).to(E.device)
+    out = torch.empty((K, int(H), int(W)), dtype=torch.float32, device=E.device)
+    nv, nf = v.shape[0], f.shape[0]
+    step = _views_per_launch(E, nv, nf, int(H), int(W))
+    args = (int(H), int(W), float(fx), float(fy), float(cx), float(cy), float(near), float(far))
+    with torch.no_grad(), E.guard():
+        for k0 in range(0, K, step):
+            kb = min(step, K - k0)
+            nbytes = int(lib.nsr_raster_workspace_bytes(nv, nf, kb, int(H), int(W)))
+            if nbytes < 0:
+                raise _capi.NsrError(f"render_depth: unsupported sizes ({nv} vertices, {nf} faces, {H} x {W})")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)
+            n_ent = torch.zeros(1, dtype=torch.int64, device=E.device)
+            wk = w2c[k0:k0 + kb]
+            lib.check(lib.nsr_raster_bin(v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), n_ent.data_ptr(),
+                                         E.stream()), "nsr_raster_bin")
+            n = int(n_ent.item())
+            bins = torch.empty(max(n, 1), dtype=torch.int32, device=E.device)
+            lib.check(lib.nsr_raster_depth(v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), bins.data_ptr(), n,
+                                           out[k0:k0 + kb].data_ptr(), E.stream()), "nsr_raster_depth")
+    return out
+
+
+def depth_l1(a: torch.Tensor, b: torch.Tensor, engine: Optional[Engine] = None) -> torch.Tensor:
+    """per-view mean |a - b| [K] fp64 of two depth stacks [K, H, W] fp32 (fixed-order fp64 sums: bit-identical run to run)"""
+    E = engine or _gpu()
+    lib = E.lib
+    a = a.detach().to(E.device, torch.float32).contiguous()
+    b = b.detach().to(E.device, torch.float32).contiguous()
+    if a.shape != b.shape or a.dim() != 3:
+        raise ValueError(f"depth_l1: two stacks [K, H, W] of one shape (got {tuple(a.shape)}, {tuple(b.shape)})")
+    K, n = a.shape[0], a.shape[1] * a.shape[2]
+    if K == 0 or n == 0:
+        raise _capi.NsrError("depth_l1: no views or empty images")
+    out = torch.empty(K, dtype=torch.float64, device=E.device)
+    partial = torch.empty(int(lib.nsr_depth_error_partial_doubles(K, n)), dtype=torch.float64, device=E.device)
+    with torch.no_grad(), E.guard():
+        lib.check(lib.nsr_depth_error(a.data_ptr(), b.data_ptr(), K, n, partial.data_ptr(), out.data_ptr(), E.stream()), "nsr_depth_error")
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
+# the box the cameras are drawn in (get_cam_position, eval_recon.py:120-128)
+# --------------------------------------------------------------------------------------------------
+def _hull2d(p: np.ndarray) -> np.ndarray:
+    """indices of the 2-D convex hull of p [n, 2], counter-clockwise (monotone chain, collinear points dropped)"""
+    order = np.lexsort((p[:, 1], p[:, 0]))
+
+    def half(idx):
+        h = []
+        for i in idx:
+            while len(h) >= 2:
+                a, b = p[h[-2]], p[h[-1]]
+                if (b[0] - a[0]) * (p[i][1] - a[1]) - (b[1] - a[1]) * (p[i][0] - a[0]) <= 0:
+                    h.pop()
+                else:
+                    break
+            h.append(i)
+        return h
+
+    lower, upper = half(order), half(order[::-1])
+    return np.array(lower[:-1] + upper[:-1], dtype=np.int64)
+
+
+def _min_rect(q: np.ndarray):
+    """(area, (e, e_perp) unit directions, (lo, hi) along them) of the minimum-area rectangle around the 2-D points q:
+    rotating calipers' candidates, one rectangle side on each hull edge"""
+    h = q[_hull2d(q)]
+    if len(h) < 3:
+        h = q
+    e = np.roll(h, -1, axis=0) - h
+    L = np.linalg.norm(e, axis=1)
+    e, L = e[L > 0], L[L > 0]
+    e = e / L[:, None]
+    p = np.stack([-e[:, 1], e[:, 0]], 1)
+    a = h @ e.T                                    # [n_pts, n_edges]
+    b = h @ p.T
+    wa, wb = a.max(0) - a.min(0), b.max(0) - b.min(0)
+    area = wa * wb
+    j = int(np.argmin(area))
+    return area[j], (e[j], p[j]), ((a[:, j].min(), a[:, j].max()), (b[:, j].min(), b[:, j].max()))
+
+
+def _hull_points(vertices, lib, device) -> np.ndarray:
+    v = vertices if isinstance(vertices, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(vertices, dtype=np.float64))
+    v = v.detach().to(device, torch.float64).contiguous()
+    pts = _bound.prefilter(v, _bound.Engine(lib, device)).cpu().numpy()
+    hv = _bound.convex_hull(pts, 1.0, lib=lib)
+    return hv[0], hv[3]
+
+
+def oriented_bounds(vertices, engine: Optional[Engine] = None):
+    """(to_origin 4x4 fp64, extents [3] ascending): the smallest-volume box with one face parallel to a face of the convex
+    hull (trimesh.bounds.oriented_bounds).  Box axes in the order of their extents, right-handed; to_origin maps the box's
+    centre to the origin and its axes onto x, y, z."""
+    E = engine or _gpu()
+    hv, planes = _hull_points(vertices, E.lib, E.device)
+    normals = np.unique(np.round(planes[:, :3], 12), axis=0)
+    best = None
+    for n in normals:
+        n = n / np.linalg.norm(n)
+        t = np.eye(3)[int(np.argmin(np.abs(n)))]
+        u = np.cross(n, t)
+        u /= np.linalg.norm(u)
+        w = np.cross(n, u)
+        q = np.stack([hv @ u, hv @ w], 1)
+        hn = hv @ n
+        area, (e, p), ((a0, a1), (b0, b1)) = _min_rect(q)
+        vol = area * (hn.max() - hn.min())
+        if best is None or vol < best[0]:
+            ax = [e[0] * u + e[1] * w, p[0] * u + p[1] * w, n]
+            ext = [a1 - a0, b1 - b0, hn.max() - hn.min()]
+            mid = [(a0 + a1) / 2, (b0 + b1) / 2, (hn.max() + hn.min()) / 2]
+            best = (vol, ax, ext, mid)
+    _, ax, ext, mid = best
+    centre = sum(m * a for m, a in zip(mid, ax))
+    order = np.argsort(ext, kind="stable")
+    R = np.stack([ax[i] for i in order], 1)
+    for c in range(2):
+        if R[int(np.argmax(np.abs(R[:, c]))), c] < 0:
+            R[:, c] = -R[:, c]
+    R[:, 2] = np.cross(R[:, 0], R[:, 1])
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, centre
+    return np.linalg.inv(T), np.asarray(ext, np.float64)[order]
+
+
+def cam_position(vertices, faces=None, engine: Optional[Engine] = None):
+    """(extents [3], transform 4x4) of the box camera origins are drawn in, as get_cam_position: the oriented bounds of the
+    ground-truth mesh, extents scaled by (0.3, 0.7, 0.7) (the shortest axis: the room's height), the centre raised by 0.4
+    on world z.  ``faces`` is accepted for symmetry with the reference's mesh argument; the box reads only the vertices."""
+    to_origin, extents = oriented_bounds(vertices, engine)
+    extents = extents.copy()
+    extents[2] *= 0.7
+    extents[1] *= 0.7
+    extents[0] *= 0.3
+    transform = np.linalg.inv(to_origin)
+    transform[2, 3] += 0.4
+    return extents, transform
+
+
+# --------------------------------------------------------------------------------------------------
+# candidate views (calc_2d_metric's rejection loop, :162-180)
+# --------------------------------------------------------------------------------------------------
+def _normalize(x):
+    return x / np.linalg.norm(x)
+
+
+def viewmatrix(z, up, pos) -> np.ndarray:
+    """3x4 [x | y | z | pos] of a camera at pos looking along z: x = normalize(up x z), y = normalize(z x x)"""
+    v2 = _normalize(z)
+    v0 = _normalize(np.cross(up, v2))
+    v1 = _normalize(np.cross(v2, v0))
+    return np.stack([v0, v1, v2, pos], 1)
+
+
+def view_draws(n: int, rng: np.random.Generator) -> np.ndarray:
+    """[n, 6] uniforms in [0, 1) per candidate: three for the origin in the box, three for the target"""
+    return rng.random((n, 6))
+
+
+def views_from_draws(extents, transform, draws) -> np.ndarray:
+    """[M, 4, 4] fp64 candidate c2w from draws [M, 6]: origin = transform (u - 0.5) extents (trimesh's volume_rectangular),
+    target = round(uniform(-1e4, 1e4), 2) - origin per axis, up = (0, 0, -1)"""
+    draws = np.asarray(draws, np.float64).reshape(-1, 6)
+    extents = np.asarray(extents, np.float64)
+    transform = np.asarray(transform, np.float64)
+    out = np.zeros((len(draws), 4, 4))
+    for i, d in enumerate(draws):
+        p = (d[:3] - 0.5) * extents
+        origin = np.dot(transform, np.append(p, 1.0))[:3]
+        tgt = np.array([round(-10000.0 + 20000.0 * float(x), 2) for x in d[3:]])
+        m = np.eye(4)
+        m[:3, :] = viewmatrix(tgt - origin, [0, 0, -1], origin)
+        out[i] = m
+    return out
+
+
+def views_unseen(c2w, unseen, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_REF, cx=249.5, cy=249.5,
+                 engine: Optional[Engine] = None) -> np.ndarray:
+    """bool [M]: check_proj of each candidate c2w against the unseen cloud: True iff the candidate sees some point of it"""
+    E = engine or _gpu()
+    c2w = _c2w_stack(c2w).copy()
+    c2w[:, :3, 1] *= -1.0
+    c2w[:, :3, 2] *= -1.0
+    w2c = torch.from_numpy(_w2c_rows(c2w)).to(E.device)
+    pts = E.tensor(unseen, what="unseen points")
+    sees = torch.empty(len(c2w), dtype=torch.uint8, device=E.device)
+    with torch.no_grad(), E.guard():
+        E.lib.check(E.lib.nsr_view_unseen(pts.data_ptr(), pts.shape[0], int(pts.dtype == torch.float64), w2c.data_ptr(), len(c2w), int(H),
+                                          int(W), float(fx), float(fy), float(cx), float(cy), sees.data_ptr(), E.stream()),
+                    "nsr_view_unseen")
+    return sees.cpu().numpy().astype(bool)
+
+
+def sample_views(extents, transform, n, unseen=None, seed=0, draws=None, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_REF, cx=249.5,
+                 cy=249.5, engine: Optional[Engine] = None, max_candidates=10_000_000) -> np.ndarray:
+    """[n, 4, 4] fp64 c2w: the first n candidates, in draw order, that see no point of ``unseen`` (None: every candidate is
+    accepted) -- the reference's sequential rejection loop fed by numpy.random.default_rng(seed), or by ``draws`` [M, 6]."""
+    E = engine or _gpu()
+    n = int(n)
+    rng = np.random.default_rng(seed)
+    out, used = [], 0
+    while len(out) < n:
+        if draws is not None:
+            if used >= len(draws):
+                raise ValueError(f"sample_views: the {len(draws)} draws give only {len(out)} accepted views of {n}")
+            d = np.asarray(draws)[used:used + max(64, 2 * (n - len(out)))]
+        else:
+            if used >= max_candidates:
+                raise RuntimeError(f"sample_views: {used} candidates drawn, {len(out)} of {n} accepted: the unseen cloud is in "
+                                   "almost every view")
+            d = view_draws(min(4096, max(64, 2 * (n - len(out)))), rng)
+        used += len(d)
+        c2w = views_from_draws(extents, transform, d)
+        ok = np.ones(len(c2w), bool) if unseen is None else ~views_unseen(c2w, unseen, H, W, fx, fy, cx, cy, E)
+        out.extend(c2w[ok][: n - len(out)])
+    return np.asarray(out, np.float64).reshape(n, 4, 4)
+
+
+# --------------------------------------------------------------------------------------------------
+# the 2-D metric (calc_2d_metric, eval_recon.py:131-211)
+# --------------------------------------------------------------------------------------------------
+def _load_mesh(E: Engine, mesh):
+    v, f = read_mesh(mesh) if isinstance(mesh, str) else (mesh[0], mesh[1])
+    return E.tensor(v, torch.float64, "mesh vertices"), _faces(E, f)
+
+
+def calc_2d_metric(rec_mesh, gt_mesh, align=True, n_imgs=1000, unseen=None, seed=0, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_REF,
+                   cx=249.5, cy=249.5, views_per_batch=100, engine: Optional[Engine] = None):
+    """Depth L1 [cm] of a reconstructed mesh against the ground truth, as calc_2d_metric: (optionally) ICP-align the
+    reconstruction, draw ``n_imgs`` views in the box of cam_position that see no point of the unseen cloud, render both
+    meshes at 500 x 500 (f = 300) and average the per-view mean |gt - rec|.  Meshes: PLY paths or (vertices, faces) pairs.
+    ``unseen``: None = the ground truth's ``_pc_unseen.npy`` beside it (required), a path or [N, 3] array, or False (accept
+    every candidate).  The intrinsics default to the reference's.  Returns {"depth_l1_cm": float, "per_view": fp64 [n_imgs]
+    (m), "c2w": fp64 [n_imgs, 4, 4]}."""
+    E = engine or _gpu()
+    if unseen is None:
+        if not isinstance(gt_mesh, str):
+            raise ValueError("calc_2d_metric: pass unseen= (a path, an array or False) with an in-memory ground truth")
+        unseen = gt_mesh.replace(".ply", "_pc_unseen.npy")
+        if not os.path.exists(unseen):
+            raise FileNotFoundError(f"calc_2d_metric: the unseen point cloud {unseen} is missing (pass unseen=False to accept every view)")
+    if isinstance(unseen, str):
+        unseen = np.load(unseen)
+    if unseen is False:
+        unseen = None
+    rv, rf = _load_mesh(E, rec_mesh)
+    gv, gf = _load_mesh(E, gt_mesh)
+    if align:
+        T = align_icp(rv, gv, 0.1, engine=E)[0]
+        rv = rv.clone()
+        _transform(E, rv, T)
+    extents, transform = cam_position(gv, gf, E)
+    poses = sample_views(extents, transform, n_imgs, unseen, seed, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, engine=E)
+    near_gt, near_rec = NEAR_REL * max_extent(gv), NEAR_REL * max_extent(rv)
+    per_view = []
+    for k0 in range(0, len(poses), views_per_batch):
+        c2w = poses[k0:k0 + views_per_batch]
+        gt_d = render_depth(gv, gf, c2w, H, W, fx, fy, cx, cy, near=near_gt, engine=E)
+        rec_d = render_depth(rv, rf, c2w, H, W, fx, fy, cx, cy, near=near_rec, engine=E)
+        per_view.append(depth_l1(gt_d, rec_d, E).cpu().numpy())
+        del gt_d, rec_d
+    per_view = np.concatenate(per_view) if per_view else np.zeros(0)
+    total = 0.0
+    for x in per_view:                              # in view order
+        total += float(x)
+    return {"depth_l1_cm": total / max(len(per_view), 1) * 100, "per_view": per_view, "c2w": poses}

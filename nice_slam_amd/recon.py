@@ -3,8 +3,10 @@
 
     from nice_slam_amd import recon
     recon.calc_3d_metric("rec.ply", "gt.ply")      # {accuracy_cm, completion_cm, completion_ratio_pct}
+    recon.calc_2d_metric("rec.ply", "gt.ply")      # {depth_l1_cm, per_view}  (nice_slam_amd/raster.py)
 
     python -m nice_slam_amd.recon eval --rec_mesh R --gt_mesh G -3d
+    python -m nice_slam_amd.recon depth --rec_mesh R --gt_mesh G
     python -m nice_slam_amd.recon cull --input_mesh M --traj traj.txt --output_mesh OUT
 
 Every per-point loop runs in libnsr.so (include/nsr.h, "Reconstruction evaluation"): exact nearest neighbour over a cell grid
@@ -18,7 +20,8 @@ Deviations from the reference (also in INTEGRATION.md):
     own random stream cannot be matched, only its algorithm;
   * ICP is Open3D's point-to-point ``registration_icp`` loop restated (the same correspondences, update and stopping rule),
     not Open3D itself: the transform agrees to rounding;
-  * the 2-D depth metric (``calc_2d_metric``) is not available: it needs a rasterizer matching Open3D's OpenGL depth buffer.
+  * the 2-D depth metric (``calc_2d_metric``, ``render_depth``: nice_slam_amd/raster.py) renders with this library's tiled
+    rasterizer, not Open3D's OpenGL depth buffer; its own deviations are listed in raster.py.
 """
 from __future__ import annotations
 
@@ -35,7 +38,8 @@ from .common import _stream
 from .mesher import write_ply
 
 __all__ = ["nearest", "accuracy", "completion", "completion_ratio", "recon_metrics", "sample_surface", "align_icp",
-           "calc_3d_metric", "cull_mesh", "load_poses", "read_mesh", "NNIndex"]
+           "calc_3d_metric", "cull_mesh", "load_poses", "read_mesh", "NNIndex",
+           "render_depth", "depth_l1", "cam_position", "sample_views", "calc_2d_metric"]
 
 
 # --------------------------------------------------------------------------------------------------
@@ -477,8 +481,12 @@ def read_mesh(path: str):
     return verts, faces
 
 
+# the 2-D metric and the rasterizer live in raster.py (which imports this module's engine and ICP)
+from .raster import calc_2d_metric, cam_position, depth_l1, render_depth, sample_views  # noqa: E402
+
+
 # --------------------------------------------------------------------------------------------------
-# command line: eval_recon.py -3d and cull_mesh.py
+# command line: eval_recon.py -3d / calc_2d_metric and cull_mesh.py
 # --------------------------------------------------------------------------------------------------
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m nice_slam_amd.recon", description="Reconstruction evaluation on the GPU.")
@@ -489,6 +497,15 @@ def main(argv=None):
     ev.add_argument("-2d", "--metric_2d", action="store_true", help="enable 2D metric (not available)")
     ev.add_argument("-3d", "--metric_3d", action="store_true", help="enable 3D metric")
     ev.add_argument("--seed", type=int, default=0, help="seed of the surface samplers")
+    de = sub.add_parser("depth", help="eval_recon.py calc_2d_metric: Depth L1 of a reconstructed mesh")
+    de.add_argument("--rec_mesh", type=str, required=True, help="reconstructed mesh file path")
+    de.add_argument("--gt_mesh", type=str, required=True, help="ground truth mesh file path")
+    un = de.add_mutually_exclusive_group()
+    un.add_argument("--unseen", type=str, default=None, help="unseen point cloud (.npy; default: <gt_mesh>_pc_unseen.npy)")
+    un.add_argument("--no_unseen", action="store_true", help="accept every candidate view")
+    de.add_argument("--n_imgs", type=int, default=1000, help="number of views")
+    de.add_argument("--seed", type=int, default=0, help="seed of the view stream")
+    de.add_argument("--no_align", action="store_true", help="skip the ICP alignment of the reconstruction")
     cu = sub.add_parser("cull", help="cull_mesh.py: remove faces no camera of a trajectory sees")
     cu.add_argument("--input_mesh", type=str, help="path to the mesh to be culled")
     cu.add_argument("--traj", type=str, help="path to the trajectory")
@@ -496,13 +513,17 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.cmd == "eval":
         if args.metric_2d:
-            raise NotImplementedError("the 2-D depth metric (eval_recon.py calc_2d_metric) needs a triangle rasterizer matching "
-                                      "Open3D's OpenGL depth buffer and the scene's _pc_unseen.npy view samples; it is not available")
+            raise NotImplementedError("eval -2d is not wired to the rasterizer: the 2-D depth metric (eval_recon.py calc_2d_metric) "
+                                      "is `python -m nice_slam_amd.recon depth --rec_mesh R --gt_mesh G`")
         if args.metric_3d:
             m = calc_3d_metric(args.rec_mesh, args.gt_mesh, seed=args.seed)
             print("accuracy: ", m["accuracy_cm"])
             print("completion: ", m["completion_cm"])
             print("completion ratio: ", m["completion_ratio_pct"])
+    elif args.cmd == "depth":
+        unseen = False if args.no_unseen else args.unseen
+        m = calc_2d_metric(args.rec_mesh, args.gt_mesh, align=not args.no_align, n_imgs=args.n_imgs, unseen=unseen, seed=args.seed)
+        print("Depth L1: ", m["depth_l1_cm"])
     else:
         v, f = read_mesh(args.input_mesh)
         poses = load_poses(args.traj)
