@@ -17,66 +17,25 @@ Deviations from the reference (also in INTEGRATION.md):
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _capi
-from .common import _stream
+from .engine import Engine, c_doubles, c_int32s, gpu, pose_stack, w2c_rows
+from .ply import write_ply
 
 UNIT = 16                        # voxels per unit edge (Open3D's volume_unit_resolution)
 HULL_TOL_REL = 1e-14             # quickhull distance tolerance, relative to the sum over axes of the largest |coordinate|
 PREFILTER_MARGIN_REL = 1e-9      # a point is dropped only if it lies this far inside every plane of the extremes' hull
 
 
-class Engine:
-    """Drives the bound entry points of a loaded library on tensors of one device.  The product uses the GPU engine
-    (``_gpu()``); the CPU tests build one on the emulator library, which takes host pointers."""
-
-    def __init__(self, lib, device):
-        self.lib = lib
-        self.device = torch.device(device)
-
-    def stream(self):
-        return _stream(self.device) if self.device.type == "cuda" else None
-
-    def guard(self):
-        return _capi.on_device(self.device if self.device.type == "cuda" else None)
-
-
-_gpu_engine = None
-
-
-def _gpu() -> Engine:
-    global _gpu_engine
-    if _gpu_engine is None:
-        if not torch.cuda.is_available():
-            raise _capi.NsrError("nice_slam_amd.bound needs the AMD GPU; there is no CPU path")
-        _gpu_engine = Engine(_capi.get_lib(), torch.device("cuda", torch.cuda.current_device()))
-    return _gpu_engine
-
-
-def _np(x) -> np.ndarray:
-    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-
-
 def frame_poses(c2ws):
     """(c2w fp64 [K,12], w2c fp32 [K,12], camera centres fp64 [K,3]) from the keyframes' est_c2w, flipped to Open3D's
     convention as Mesher.py:240-243 does; w2c = inv(c2w) in fp64, then rounded to fp32."""
-    K = len(c2ws)
-    c2w = np.zeros((K, 12), np.float64)
-    w2c = np.zeros((K, 12), np.float32)
-    cams = np.zeros((K, 3), np.float64)
-    for k, m in enumerate(c2ws):
-        m = _np(m).astype(np.float64).reshape(4, 4).copy()
-        m[:3, 1] *= -1.0
-        m[:3, 2] *= -1.0
-        c2w[k] = m[:3].reshape(-1)
-        w2c[k] = np.linalg.inv(m)[:3].reshape(-1).astype(np.float32)
-        cams[k] = m[:3, 3]
-    return c2w, w2c, cams
+    c2w = pose_stack(c2ws, flip_yz=True)
+    return np.ascontiguousarray(c2w[:, :3]).reshape(len(c2w), 12), w2c_rows(c2w, np.float64), c2w[:, :3, 3].copy()
 
 
 class TSDFVolume:
@@ -90,14 +49,10 @@ class TSDFVolume:
         self.voxel_length, self.sdf_trunc, self.cams = voxel_length, sdf_trunc, cams
 
 
-def _box_arg(box):
-    return (C.c_int32 * 6)(*[int(x) for x in box])
-
-
 def tsdf_fuse(keyframes, H, W, fx, fy, cx, cy, scale=1.0, engine: Optional[Engine] = None, timer=None) -> TSDFVolume:
     """Fuse every keyframe's depth (``keyframe['depth']`` [H,W], ``keyframe['est_c2w']`` 4x4) into a sparse TSDF volume with
     voxel_length 4 scale / 512 and sdf_trunc 0.04 scale (Mesher.py:227-236).  ``timer``: optional callable(phase)."""
-    E = engine or _gpu()
+    E = engine or gpu()
     lib, dev = E.lib, E.device
     tick = timer or (lambda name: None)
     K = len(keyframes)
@@ -118,16 +73,16 @@ def tsdf_fuse(keyframes, H, W, fx, fy, cx, cy, scale=1.0, engine: Optional[Engin
             z = torch.zeros((0, UNIT, UNIT, UNIT), dtype=torch.float32, device=dev)
             return TSDFVolume(E, box, None, torch.zeros((0, 3), dtype=torch.int32, device=dev),
                               torch.zeros((0, tw), dtype=torch.int32, device=dev), z, z.clone(), vl, trunc, cams)
-        nbytes = lib.nsr_tsdf_workspace_bytes(_box_arg(box))
+        nbytes = lib.nsr_tsdf_workspace_bytes(c_int32s(box))
         if nbytes < 0:
             raise _capi.NsrError(f"tsdf_fuse: the touched units span {box[3:] - box[:3] + 1} units: more than 2^31")
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
         nu_d = torch.empty(1, dtype=torch.int64, device=dev)
-        lib.check(lib.nsr_tsdf_touch_count(*args, _box_arg(box), ws.data_ptr(), nu_d.data_ptr(), E.stream()), "nsr_tsdf_touch_count")
+        lib.check(lib.nsr_tsdf_touch_count(*args, c_int32s(box), ws.data_ptr(), nu_d.data_ptr(), E.stream()), "nsr_tsdf_touch_count")
         nu = int(nu_d.cpu()[0])
         units = torch.empty((nu, 3), dtype=torch.int32, device=dev)
         touch = torch.empty((nu, tw), dtype=torch.int32, device=dev)     # uint32 bits (torch has no uint32 arithmetic)
-        lib.check(lib.nsr_tsdf_touch_emit(*args, _box_arg(box), ws.data_ptr(), nu, units.data_ptr(), touch.data_ptr(), E.stream()),
+        lib.check(lib.nsr_tsdf_touch_emit(*args, c_int32s(box), ws.data_ptr(), nu, units.data_ptr(), touch.data_ptr(), E.stream()),
                   "nsr_tsdf_touch_emit")
         tick("touch")
         tsdf = torch.empty((nu, UNIT, UNIT, UNIT), dtype=torch.float32, device=dev)
@@ -150,11 +105,11 @@ def surface_points(vol: TSDFVolume) -> torch.Tensor:
         return torch.zeros((0, 3), dtype=torch.float64, device=dev)
     with torch.no_grad(), E.guard():
         counts = torch.empty(nu + 1, dtype=torch.int64, device=dev)
-        lib.check(lib.nsr_tsdf_surface_count(_box_arg(vol.box), vol.workspace.data_ptr(), vol.units.data_ptr(), nu, vol.tsdf.data_ptr(),
+        lib.check(lib.nsr_tsdf_surface_count(c_int32s(vol.box), vol.workspace.data_ptr(), vol.units.data_ptr(), nu, vol.tsdf.data_ptr(),
                                              vol.weight.data_ptr(), counts.data_ptr(), E.stream()), "nsr_tsdf_surface_count")
         n = int(counts[nu].cpu())
         pts = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        lib.check(lib.nsr_tsdf_surface_emit(_box_arg(vol.box), vol.workspace.data_ptr(), vol.units.data_ptr(), nu, vol.tsdf.data_ptr(),
+        lib.check(lib.nsr_tsdf_surface_emit(c_int32s(vol.box), vol.workspace.data_ptr(), vol.units.data_ptr(), nu, vol.tsdf.data_ptr(),
                                             vol.weight.data_ptr(), float(vol.voxel_length), counts.data_ptr(), n, pts.data_ptr(),
                                             E.stream()), "nsr_tsdf_surface_emit")
     return pts
@@ -178,9 +133,8 @@ def convex_hull(points, bound_scale=1.0, tol=None, lib=None):
     vidx = np.zeros(max(n, 1), np.int64)
     faces = np.zeros((max(2 * n, 1), 3), np.int32)
     planes = np.zeros((max(2 * n, 1), 4), np.float64)
-    P = lambda a: a.ctypes.data_as(C.c_void_p)
-    lib.check(lib.nsr_convex_hull(P(p), n, float(tol), float(bound_scale), P(counts), P(verts), P(vidx), P(faces), P(planes)),
-              "nsr_convex_hull")
+    lib.check(lib.nsr_convex_hull(p.ctypes, n, float(tol), float(bound_scale), counts.ctypes, verts.ctypes, vidx.ctypes, faces.ctypes,
+                                  planes.ctypes), "nsr_convex_hull")
     nv, nf = int(counts[0]), int(counts[1])
     return verts[:nv].copy(), vidx[:nv].copy(), faces[:nf].copy(), planes[:nf].copy()
 
@@ -188,7 +142,7 @@ def convex_hull(points, bound_scale=1.0, tol=None, lib=None):
 def prefilter(points: torch.Tensor, engine: Optional[Engine] = None) -> torch.Tensor:
     """The points that may be vertices of the convex hull of ``points`` (fp64 [N,3] on the engine's device), in their
     order: every point strictly inside the hull of the 26 extremes (csrc/nsr_bound.h) is dropped."""
-    E = engine or _gpu()
+    E = engine or gpu()
     lib, dev = E.lib, E.device
     pts = points.detach().to(dev, torch.float64).contiguous()
     n = pts.shape[0]
@@ -206,9 +160,8 @@ def prefilter(points: torch.Tensor, engine: Optional[Engine] = None) -> torch.Te
             return pts
         margin = PREFILTER_MARGIN_REL * _tol_scale(ep)
         keep = torch.empty(n, dtype=torch.uint8, device=dev)
-        pl = np.ascontiguousarray(planes.reshape(-1))
-        lib.check(lib.nsr_hull_prefilter(pts.data_ptr(), n, (C.c_double * len(pl))(*pl), planes.shape[0], margin, keep.data_ptr(),
-                                         E.stream()), "nsr_hull_prefilter")
+        lib.check(lib.nsr_hull_prefilter(pts.data_ptr(), n, c_doubles(planes), planes.shape[0], margin, keep.data_ptr(), E.stream()),
+                  "nsr_hull_prefilter")
     return pts[keep.bool()]
 
 
@@ -234,29 +187,23 @@ class ConvexBound:
     def contains(self, points):
         """bool [N]: numpy in -> numpy out; a tensor in -> a tensor on its device out (fp32 or fp64 points, [N,3])."""
         as_np = not isinstance(points, torch.Tensor)
-        E = self.engine
-        if E is None:
-            E = _gpu()
-        t = torch.from_numpy(np.ascontiguousarray(points)) if as_np else points
-        if t.dtype not in (torch.float32, torch.float64):
-            t = t.to(torch.float64)
-        dev = E.device if (as_np or t.device.type != E.device.type) else t.device
-        t = t.detach().to(dev).reshape(-1, 3).contiguous()
+        E = self.engine or gpu()
+        if not as_np and points.device.type == E.device.type and points.device != E.device:
+            E = Engine(E.lib, points.device)                          # a tensor on another GPU is tested there
+        t = E.tensor(np.reshape(points, (-1, 3)) if as_np else points.reshape(-1, 3), what="contains: points")
         n = t.shape[0]
-        out = torch.empty(n, dtype=torch.uint8, device=dev)
+        out = torch.empty(n, dtype=torch.uint8, device=E.device)
         if n:
-            pl = self._planes_on(dev)
-            lib = E.lib
-            with torch.no_grad(), _capi.on_device(dev if dev.type == "cuda" else None):
-                lib.check(lib.nsr_hull_contains(t.data_ptr(), n, 1 if t.dtype == torch.float64 else 0, pl.data_ptr(), pl.shape[0],
-                                                out.data_ptr(), _stream(dev) if dev.type == "cuda" else None), "nsr_hull_contains")
+            pl = self._planes_on(E.device)
+            with torch.no_grad(), E.guard():
+                E.lib.check(E.lib.nsr_hull_contains(t.data_ptr(), n, int(t.dtype == torch.float64), pl.data_ptr(), pl.shape[0],
+                                                    out.data_ptr(), E.stream()), "nsr_hull_contains")
         res = out.bool()
         return res.cpu().numpy() if as_np else res
 
     __call__ = contains
 
     def to_ply(self, path: str):
-        from .mesher import write_ply
         write_ply(path, self.vertices, self.faces)
 
 
@@ -264,7 +211,7 @@ def bound_from_frames(keyframe_dict, H, W, fx, fy, cx, cy, scale=1.0, bound_scal
                       timer=None) -> ConvexBound:
     """Mesher.get_bound_from_frames: the convex hull of the camera centres and the TSDF mesh vertices of the keyframes,
     scaled by ``bound_scale`` about the mean of its vertices.  ``stats`` of the result: the point counts of each stage."""
-    E = engine or _gpu()
+    E = engine or gpu()
     tick = timer or (lambda name: None)
     vol = tsdf_fuse(keyframe_dict, H, W, fx, fy, cx, cy, scale, engine=E, timer=tick)
     surf = surface_points(vol)

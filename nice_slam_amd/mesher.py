@@ -20,7 +20,6 @@ Deviations from the reference (also in INTEGRATION.md):
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Callable, Optional
 
 import numpy as np
@@ -28,67 +27,70 @@ import torch
 
 from . import _capi
 from .bound import ConvexBound, bound_from_frames
-from .common import _require_cuda, _stream
+from .common import _require_cuda
+from .engine import Engine, c_doubles, compact, w2c_rows
+from .ply import read_mesh, write_ply
 from .renderer import eval_points_raw
 
-def _dbl3(v):
-    return (C.c_double * 3)(*[float(x) for x in v])
+
+def _engine(engine: Optional[Engine], t: torch.Tensor, what: str) -> Engine:
+    """the caller's engine, else the product library on the GPU ``t`` lives on"""
+    if engine is not None:
+        return engine
+    _require_cuda(t, what)
+    return Engine(_capi.get_lib(), t.device)
 
 
-def marching_cubes(volume: torch.Tensor, level: float = 0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+def marching_cubes(volume: torch.Tensor, level: float = 0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0),
+                   engine: Optional[Engine] = None):
     """Welded marching cubes of a device fp32 lattice ``volume[nx, ny, nz]`` (x slowest) -> (verts fp64 [V,3], faces int32
     [F,3]) on the device.  Vertex = origin + (i + t) * spacing; face normals point toward decreasing field (skimage's
     ``gradient_direction='descent'``).  One host read (the two counts) sizes the outputs."""
-    _require_cuda(volume, "marching_cubes: volume")
+    E = _engine(engine, volume, "marching_cubes: volume")
     if volume.dim() != 3:
         raise ValueError("marching_cubes: volume must be [nx, ny, nz]")
-    lib = _capi.get_lib()
-    dev = volume.device
-    vol = volume.detach().to(torch.float32).contiguous()
+    lib, dev = E.lib, E.device
+    vol = volume.detach().to(dev, torch.float32).contiguous()
     nx, ny, nz = (int(s) for s in vol.shape)
-    with torch.no_grad(), _capi.on_device(dev):
+    with torch.no_grad(), E.guard():
         nbytes = lib.nsr_mc_workspace_bytes(nx, ny, nz)
         if nbytes < 0:
             raise _capi.NsrError(f"marching_cubes: lattice {tuple(vol.shape)} not supported (every dimension >= 2, <= 2^31 points)")
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
-        lib.check(lib.nsr_mc_count(vol.data_ptr(), nx, ny, nz, float(level), ws.data_ptr(), counts.data_ptr(), _stream(dev)), "nsr_mc_count")
+        lib.check(lib.nsr_mc_count(vol.data_ptr(), nx, ny, nz, float(level), ws.data_ptr(), counts.data_ptr(), E.stream()), "nsr_mc_count")
         n_v, n_f = (int(x) for x in counts.cpu())
         verts = torch.empty((n_v, 3), dtype=torch.float64, device=dev)
         faces = torch.empty((n_f, 3), dtype=torch.int32, device=dev)
-        lib.check(lib.nsr_mc_emit(vol.data_ptr(), nx, ny, nz, float(level), _dbl3(origin), _dbl3(spacing), ws.data_ptr(), n_v, n_f,
-                                  verts.data_ptr(), faces.data_ptr(), _stream(dev)), "nsr_mc_emit")
+        lib.check(lib.nsr_mc_emit(vol.data_ptr(), nx, ny, nz, float(level), c_doubles(origin, 3), c_doubles(spacing, 3), ws.data_ptr(),
+                                  n_v, n_f, verts.data_ptr(), faces.data_ptr(), E.stream()), "nsr_mc_emit")
     return verts, faces
 
 
-def point_masks_raw(points: torch.Tensor, c2ws, depths, H, W, fx, fy, cx, cy, mode: int, chunk: int) -> torch.Tensor:
+def point_masks_raw(points: torch.Tensor, c2ws, depths, H, W, fx, fy, cx, cy, mode: int, chunk: int,
+                    engine: Optional[Engine] = None) -> torch.Tensor:
     """uint8 [N] on the device: 0 unseen, 1 seen, 2 forecast (nsr_point_masks).  ``c2ws``: list of 4x4 poses (tensors or
     arrays); ``depths``: list of [H,W] depth tensors (modes 1, 2)."""
-    _require_cuda(points, "point_masks: points")
-    lib = _capi.get_lib()
-    dev = points.device
-    pts = points.detach().to(torch.float32).contiguous()
+    E = _engine(engine, points, "point_masks: points")
+    lib, dev = E.lib, E.device
+    pts = points.detach().to(dev, torch.float32).contiguous()
     n = pts.shape[0]
     K = len(c2ws)
     out = torch.empty(n, dtype=torch.uint8, device=dev)
     if n == 0:
         return out
-    w2c = np.zeros((max(K, 1), 12), dtype=np.float32)
-    for k, c2w in enumerate(c2ws):
-        c = c2w.detach().cpu().numpy() if isinstance(c2w, torch.Tensor) else np.asarray(c2w)
-        w2c[k] = np.linalg.inv(c).astype(np.float32)[:3].reshape(-1)       # as Mesher.py:130-132
-    w2c_d = torch.from_numpy(w2c).to(dev)
+    w2c_d = torch.from_numpy(w2c_rows(c2ws, None)).to(dev)
     depth = limit = ws = None
     if mode == 2 and K:
         depth = torch.stack([d.detach().to(dev, torch.float32).reshape(H, W) for d in depths]).contiguous()
         ws = torch.empty(int(lib.nsr_point_masks_workspace_floats(n, chunk, K)), dtype=torch.float32, device=dev)
     elif mode == 1 and K:
         limit = torch.stack([torch.max(d.detach().to(dev, torch.float32)) * 1.1 for d in depths]).contiguous()   # :179
-    with _capi.on_device(dev):
+    with E.guard():
         lib.check(lib.nsr_point_masks(pts.data_ptr(), n, int(chunk), int(mode), K, w2c_d.data_ptr(),
                                       None if depth is None else depth.data_ptr(), None if limit is None else limit.data_ptr(),
                                       int(H), int(W), float(fx), float(fy), float(cx), float(cy),
-                                      None if ws is None else ws.data_ptr(), out.data_ptr(), _stream(dev)), "nsr_point_masks")
+                                      None if ws is None else ws.data_ptr(), out.data_ptr(), E.stream()), "nsr_point_masks")
     return out
 
 
@@ -106,31 +108,31 @@ def face_adjacency(faces: torch.Tensor, n_verts: int) -> torch.Tensor:
     return torch.stack([fs[:-1][same], fs[1:][same]], 1).to(torch.int32).contiguous()
 
 
-def face_components(verts: torch.Tensor, faces: torch.Tensor):
+def face_components(verts: torch.Tensor, faces: torch.Tensor, engine: Optional[Engine] = None):
     """(label int64 [F] = the largest face index of the face's component, component areas fp64 [C], first (smallest) face of
     each component int64 [C], component index of each face int64 [F]); components in order of their label."""
-    lib = _capi.get_lib()
-    dev = faces.device
     F = faces.shape[0]
     if F == 0:
-        z = torch.zeros(0, dtype=torch.int64, device=dev)
-        return z, torch.zeros(0, dtype=torch.float64, device=dev), z, z
-    pairs = face_adjacency(faces, verts.shape[0])
+        z = torch.zeros(0, dtype=torch.int64, device=faces.device)
+        return z, torch.zeros(0, dtype=torch.float64, device=faces.device), z, z
+    E = _engine(engine, faces, "face_components: faces")
+    lib, dev = E.lib, E.device
+    vv = verts.detach().to(dev, torch.float64).contiguous()
+    ff = faces.to(dev, torch.int32).contiguous()
+    pairs = face_adjacency(ff, vv.shape[0])
     parent = torch.empty(F, dtype=torch.int32, device=dev)
     changed = torch.empty(1, dtype=torch.int32, device=dev)
-    vv = verts.detach().to(torch.float64).contiguous()
-    ff = faces.to(torch.int32).contiguous()
-    with _capi.on_device(dev):
-        lib.check(lib.nsr_cc_init(F, parent.data_ptr(), changed.data_ptr(), _stream(dev)), "nsr_cc_init")
+    with E.guard():
+        lib.check(lib.nsr_cc_init(F, parent.data_ptr(), changed.data_ptr(), E.stream()), "nsr_cc_init")
         r = 0
         while True:
-            lib.check(lib.nsr_cc_round(pairs.data_ptr(), pairs.shape[0], F, parent.data_ptr(), changed.data_ptr(), r, _stream(dev)),
+            lib.check(lib.nsr_cc_round(pairs.data_ptr(), pairs.shape[0], F, parent.data_ptr(), changed.data_ptr(), r, E.stream()),
                       "nsr_cc_round")
             if int(changed.item()) != r + 1:
                 break
             r += 1
         area = torch.empty(F, dtype=torch.float64, device=dev)
-        lib.check(lib.nsr_face_areas(vv.data_ptr(), ff.data_ptr(), F, area.data_ptr(), _stream(dev)), "nsr_face_areas")
+        lib.check(lib.nsr_face_areas(vv.data_ptr(), ff.data_ptr(), F, area.data_ptr(), E.stream()), "nsr_face_areas")
         label = parent.long()
         ls, order = torch.sort(label, stable=True)
         start = torch.ones(F, dtype=torch.bool, device=dev)
@@ -141,17 +143,17 @@ def face_components(verts: torch.Tensor, faces: torch.Tensor):
         order, ls = order.contiguous(), ls.contiguous()
         partial = torch.empty(F, dtype=torch.float64, device=dev)
         lib.check(lib.nsr_segment_sums(area.data_ptr(), order.data_ptr(), ls.data_ptr(), F, seg.data_ptr(), n_seg, partial.data_ptr(),
-                                       comp_area.data_ptr(), _stream(dev)), "nsr_segment_sums")
+                                       comp_area.data_ptr(), E.stream()), "nsr_segment_sums")
     comp_of = torch.empty(F, dtype=torch.int64, device=dev)
     comp_of[order] = torch.cumsum(start.long(), 0) - 1
     first = order[seg[:-1]]
     return label, comp_area, first, comp_of
 
 
-def keep_components(verts: torch.Tensor, faces: torch.Tensor, largest: bool, min_area: float):
+def keep_components(verts: torch.Tensor, faces: torch.Tensor, largest: bool, min_area: float, engine: Optional[Engine] = None):
     """Mesher.py:487-498: keep the component of largest area (ties: the one whose first face comes first), or every component
     of area > min_area; then drop unreferenced vertices.  Faces and vertices keep their order."""
-    _, comp_area, first, comp_of = face_components(verts, faces)
+    _, comp_area, first, comp_of = face_components(verts, faces, engine)
     if faces.shape[0] == 0:
         return verts[:0], faces
     if largest:
@@ -164,53 +166,11 @@ def keep_components(verts: torch.Tensor, faces: torch.Tensor, largest: bool, min
     return compact(verts, faces[keep_comp[comp_of]])
 
 
-def compact(verts: torch.Tensor, faces: torch.Tensor):
-    used = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
-    used[faces.reshape(-1).long()] = True
-    remap = torch.cumsum(used.long(), 0) - 1
-    return verts[used], remap[faces.long()].to(torch.int32)
-
-
-def write_ply(path: str, verts: np.ndarray, faces: np.ndarray, colors: Optional[np.ndarray] = None):
-    """Binary little-endian PLY: float32 x y z [+ uchar red green blue alpha], faces as `list uchar int`."""
-    verts = np.asarray(verts, dtype="<f4").reshape(-1, 3)
-    faces = np.asarray(faces, dtype="<i4").reshape(-1, 3)
-    hdr = ["ply", "format binary_little_endian 1.0", f"element vertex {len(verts)}",
-           "property float x", "property float y", "property float z"]
-    if colors is not None:
-        hdr += ["property uchar red", "property uchar green", "property uchar blue", "property uchar alpha"]
-    hdr += [f"element face {len(faces)}", "property list uchar int vertex_indices", "end_header"]
-    vdt = [("xyz", "<f4", 3)] + ([("rgba", "u1", 4)] if colors is not None else [])
-    vrec = np.empty(len(verts), dtype=vdt)
-    vrec["xyz"] = verts
-    if colors is not None:
-        c = np.asarray(colors, dtype=np.uint8).reshape(len(verts), -1)
-        rgba = np.full((len(verts), 4), 255, dtype=np.uint8)
-        rgba[:, :c.shape[1]] = c
-        vrec["rgba"] = rgba
-    frec = np.empty(len(faces), dtype=[("n", "u1"), ("idx", "<i4", 3)])
-    frec["n"] = 3
-    frec["idx"] = faces
-    with open(path, "wb") as fh:
-        fh.write(("\n".join(hdr) + "\n").encode("ascii"))
-        fh.write(vrec.tobytes())
-        fh.write(frec.tobytes())
-
-
 def read_ply(path: str):
-    """Reader for what write_ply writes -> (verts float32 [V,3], faces int32 [F,3], colors uint8 [V,4] or None)."""
-    with open(path, "rb") as fh:
-        data = fh.read()
-    end = data.index(b"end_header\n") + len(b"end_header\n")
-    hdr = data[:end].decode("ascii").split("\n")
-    nv = int([h for h in hdr if h.startswith("element vertex")][0].split()[-1])
-    nf = int([h for h in hdr if h.startswith("element face")][0].split()[-1])
-    has_c = any(h.endswith(" red") for h in hdr)
-    vdt = [("xyz", "<f4", 3)] + ([("rgba", "u1", 4)] if has_c else [])
-    v = np.frombuffer(data, dtype=vdt, count=nv, offset=end)
-    f = np.frombuffer(data, dtype=[("n", "u1"), ("idx", "<i4", 3)], count=nf, offset=end + v.nbytes)
-    assert (f["n"] == 3).all()
-    return v["xyz"].copy(), f["idx"].copy(), (v["rgba"].copy() if has_c else None)
+    """What write_ply writes -> (verts float32 [V,3], faces int32 [F,3], colors uint8 [V,4] or None): read_mesh with the
+    colours, in write_ply's dtypes."""
+    v, f, c = read_mesh(path, colors=True)
+    return v.astype(np.float32), f.astype(np.int32), c
 
 
 class Mesher:

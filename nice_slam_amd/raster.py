@@ -31,8 +31,9 @@ import numpy as np
 import torch
 
 from . import _capi
-from . import bound as _bound
-from .recon import Engine, _faces, _gpu, _transform, align_icp, read_mesh
+from .bound import convex_hull, prefilter
+from .engine import Engine, gpu, pose_stack, w2c_rows
+from .recon import align_icp
 
 __all__ = ["render_depth", "depth_l1", "oriented_bounds", "cam_position", "viewmatrix", "view_draws", "views_from_draws",
            "views_unseen", "sample_views", "calc_2d_metric"]
@@ -41,21 +42,6 @@ H_REF, W_REF, FOCAL_REF = 500, 500, 300.0          # eval_recon.py:135-142
 FAR_REF = 20.0                                     # ctr.set_constant_z_far(20)
 NEAR_REL = 0.01                                    # near = 0.01 x the mesh's largest extent
 MAX_VIEWS_PER_LAUNCH = 64
-
-
-def _c2w_stack(c2w) -> np.ndarray:
-    m = c2w.detach().cpu().numpy() if isinstance(c2w, torch.Tensor) else np.asarray(c2w)
-    m = np.asarray(m, np.float64)
-    if m.shape == (4, 4):
-        m = m[None]
-    if m.ndim != 3 or m.shape[1:] != (4, 4):
-        raise ValueError(f"c2w must be [4, 4] or [K, 4, 4] (got {m.shape})")
-    return m
-
-
-def _w2c_rows(c2w: np.ndarray) -> np.ndarray:
-    """[K, 12] fp32: rows 0..2 of inv(c2w) taken in fp64"""
-    return np.ascontiguousarray(np.linalg.inv(c2w)[:, :3].reshape(len(c2w), 12).astype(np.float32))
 
 
 def max_extent(vertices) -> float:
@@ -81,11 +67,11 @@ def render_depth(vertices, faces, c2w, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_
     """Depth images [K, H, W] fp32 on the engine's device of the mesh (vertices [V, 3], faces [F, 3]) seen from each c2w
     ([4, 4] or [K, 4, 4], OpenCV convention: x right, y down, z forward).  Depth is camera-space z, 0 where nothing is drawn;
     fragments outside [near, far] are discarded; near defaults to 0.01 x the mesh's largest axis-aligned extent."""
-    E = engine or _gpu()
+    E = engine or gpu()
     lib = E.lib
     v = E.tensor(vertices, torch.float32, "render_depth: vertices")
-    f = _faces(E, faces)
-    c2w = _c2w_stack(c2w)
+    f = E.faces(faces)
+    c2w = pose_stack(c2w)
     K = len(c2w)
     if v.shape[0] == 0 or f.shape[0] == 0:
         raise _capi.NsrError("render_depth: empty mesh")
@@ -98,7 +84,7 @@ def render_depth(vertices, faces, c2w, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_
         near = NEAR_REL * max_extent(vertices)
     if not near > 0.0:
         raise _capi.NsrError(f"render_depth: near must be positive (got {near})")
-    w2c = torch.from_numpy(_w2c_rows(c2w)).to(E.device)
+    w2c = torch.from_numpy(w2c_rows(c2w, np.float64)).to(E.device)
     out = torch.empty((K, int(H), int(W)), dtype=torch.float32, device=E.device)
     nv, nf = v.shape[0], f.shape[0]
     step = _views_per_launch(E, nv, nf, int(H), int(W))
@@ -123,7 +109,7 @@ def render_depth(vertices, faces, c2w, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_
 
 def depth_l1(a: torch.Tensor, b: torch.Tensor, engine: Optional[Engine] = None) -> torch.Tensor:
     """per-view mean |a - b| [K] fp64 of two depth stacks [K, H, W] fp32 (fixed-order fp64 sums: bit-identical run to run)"""
-    E = engine or _gpu()
+    E = engine or gpu()
     lib = E.lib
     a = a.detach().to(E.device, torch.float32).contiguous()
     b = b.detach().to(E.device, torch.float32).contiguous()
@@ -181,11 +167,9 @@ def _min_rect(q: np.ndarray):
     return area[j], (e[j], p[j]), ((a[:, j].min(), a[:, j].max()), (b[:, j].min(), b[:, j].max()))
 
 
-def _hull_points(vertices, lib, device) -> np.ndarray:
-    v = vertices if isinstance(vertices, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(vertices, dtype=np.float64))
-    v = v.detach().to(device, torch.float64).contiguous()
-    pts = _bound.prefilter(v, _bound.Engine(lib, device)).cpu().numpy()
-    hv = _bound.convex_hull(pts, 1.0, lib=lib)
+def _hull_points(vertices, E: Engine) -> np.ndarray:
+    pts = prefilter(E.tensor(vertices, torch.float64, "oriented_bounds: vertices"), E).cpu().numpy()
+    hv = convex_hull(pts, 1.0, lib=E.lib)
     return hv[0], hv[3]
 
 
@@ -193,8 +177,8 @@ def oriented_bounds(vertices, engine: Optional[Engine] = None):
     """(to_origin 4x4 fp64, extents [3] ascending): the smallest-volume box with one face parallel to a face of the convex
     hull (trimesh.bounds.oriented_bounds).  Box axes in the order of their extents, right-handed; to_origin maps the box's
     centre to the origin and its axes onto x, y, z."""
-    E = engine or _gpu()
-    hv, planes = _hull_points(vertices, E.lib, E.device)
+    E = engine or gpu()
+    hv, planes = _hull_points(vertices, E)
     normals = np.unique(np.round(planes[:, :3], 12), axis=0)
     best = None
     for n in normals:
@@ -279,11 +263,9 @@ def views_from_draws(extents, transform, draws) -> np.ndarray:
 def views_unseen(c2w, unseen, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_REF, cx=249.5, cy=249.5,
                  engine: Optional[Engine] = None) -> np.ndarray:
     """bool [M]: check_proj of each candidate c2w against the unseen cloud: True iff the candidate sees some point of it"""
-    E = engine or _gpu()
-    c2w = _c2w_stack(c2w).copy()
-    c2w[:, :3, 1] *= -1.0
-    c2w[:, :3, 2] *= -1.0
-    w2c = torch.from_numpy(_w2c_rows(c2w)).to(E.device)
+    E = engine or gpu()
+    c2w = pose_stack(c2w, flip_yz=True)
+    w2c = torch.from_numpy(w2c_rows(c2w, np.float64)).to(E.device)
     pts = E.tensor(unseen, what="unseen points")
     sees = torch.empty(len(c2w), dtype=torch.uint8, device=E.device)
     with torch.no_grad(), E.guard():
@@ -297,7 +279,7 @@ def sample_views(extents, transform, n, unseen=None, seed=0, draws=None, H=H_REF
                  cy=249.5, engine: Optional[Engine] = None, max_candidates=10_000_000) -> np.ndarray:
     """[n, 4, 4] fp64 c2w: the first n candidates, in draw order, that see no point of ``unseen`` (None: every candidate is
     accepted) -- the reference's sequential rejection loop fed by numpy.random.default_rng(seed), or by ``draws`` [M, 6]."""
-    E = engine or _gpu()
+    E = engine or gpu()
     n = int(n)
     rng = np.random.default_rng(seed)
     out, used = [], 0
@@ -321,11 +303,6 @@ def sample_views(extents, transform, n, unseen=None, seed=0, draws=None, H=H_REF
 # --------------------------------------------------------------------------------------------------
 # the 2-D metric (calc_2d_metric, eval_recon.py:131-211)
 # --------------------------------------------------------------------------------------------------
-def _load_mesh(E: Engine, mesh):
-    v, f = read_mesh(mesh) if isinstance(mesh, str) else (mesh[0], mesh[1])
-    return E.tensor(v, torch.float64, "mesh vertices"), _faces(E, f)
-
-
 def calc_2d_metric(rec_mesh, gt_mesh, align=True, n_imgs=1000, unseen=None, seed=0, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_REF,
                    cx=249.5, cy=249.5, views_per_batch=100, engine: Optional[Engine] = None):
     """Depth L1 [cm] of a reconstructed mesh against the ground truth, as calc_2d_metric: (optionally) ICP-align the
@@ -334,7 +311,7 @@ def calc_2d_metric(rec_mesh, gt_mesh, align=True, n_imgs=1000, unseen=None, seed
     ``unseen``: None = the ground truth's ``_pc_unseen.npy`` beside it (required), a path or [N, 3] array, or False (accept
     every candidate).  The intrinsics default to the reference's.  Returns {"depth_l1_cm": float, "per_view": fp64 [n_imgs]
     (m), "c2w": fp64 [n_imgs, 4, 4]}."""
-    E = engine or _gpu()
+    E = engine or gpu()
     if unseen is None:
         if not isinstance(gt_mesh, str):
             raise ValueError("calc_2d_metric: pass unseen= (a path, an array or False) with an in-memory ground truth")
@@ -345,12 +322,12 @@ def calc_2d_metric(rec_mesh, gt_mesh, align=True, n_imgs=1000, unseen=None, seed
         unseen = np.load(unseen)
     if unseen is False:
         unseen = None
-    rv, rf = _load_mesh(E, rec_mesh)
-    gv, gf = _load_mesh(E, gt_mesh)
+    rv, rf = E.mesh(rec_mesh)
+    gv, gf = E.mesh(gt_mesh)
     if align:
         T = align_icp(rv, gv, 0.1, engine=E)[0]
         rv = rv.clone()
-        _transform(E, rv, T)
+        E.transform(rv, T)
     extents, transform = cam_position(gv, gf, E)
     poses = sample_views(extents, transform, n_imgs, unseen, seed, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, engine=E)
     near_gt, near_rec = NEAR_REL * max_extent(gv), NEAR_REL * max_extent(rv)

@@ -34,57 +34,13 @@ import numpy as np
 import torch
 
 from . import _capi
-from .common import _stream
-from .mesher import write_ply
+from .engine import Engine, c_doubles, gpu, w2c_rows
+from .engine import compact as compact_mesh
+from .ply import read_mesh, write_ply
 
 __all__ = ["nearest", "accuracy", "completion", "completion_ratio", "recon_metrics", "sample_surface", "align_icp",
            "calc_3d_metric", "cull_mesh", "load_poses", "read_mesh", "NNIndex",
            "render_depth", "depth_l1", "cam_position", "sample_views", "calc_2d_metric"]
-
-
-# --------------------------------------------------------------------------------------------------
-# the engine: one library (the product's libnsr.so on a GPU) and the device its tensors live on
-# --------------------------------------------------------------------------------------------------
-class Engine:
-    """Drives the reconstruction entry points of a loaded library on tensors of one device.  The product uses the GPU
-    engine (``_gpu()``); the CPU tests build one on the emulator library, which takes host pointers."""
-
-    def __init__(self, lib, device):
-        self.lib = lib
-        self.device = torch.device(device)
-
-    def stream(self):
-        return _stream(self.device) if self.device.type == "cuda" else None
-
-    def guard(self):
-        return _capi.on_device(self.device if self.device.type == "cuda" else None)
-
-    def tensor(self, a, dtype=None, what="points"):
-        """[N, 3] contiguous tensor on this device (numpy and tensors of any device accepted; fp32 / fp64 kept)."""
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-        if dtype is None:
-            dtype = t.dtype if t.dtype in (torch.float32, torch.float64) else torch.float64
-        t = t.detach().to(self.device, dtype).contiguous()
-        if t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError(f"{what} must be [N, 3] (got {tuple(t.shape)})")
-        return t
-
-
-_gpu_engine = None
-
-
-def _gpu() -> Engine:
-    global _gpu_engine
-    if _gpu_engine is None:
-        if not torch.cuda.is_available():
-            raise _capi.NsrError("nice_slam_amd.recon needs the AMD GPU; there is no CPU path")
-        _gpu_engine = Engine(_capi.get_lib(), torch.device("cuda", torch.cuda.current_device()))
-    return _gpu_engine
-
-
-def _dbl(v):
-    v = [float(x) for x in np.asarray(v, dtype=np.float64).reshape(-1)]
-    return (C.c_double * len(v))(*v)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -96,7 +52,7 @@ class NNIndex:
     ties to the smallest reference index."""
 
     def __init__(self, ref, engine: Optional[Engine] = None):
-        E = self.engine = engine or _gpu()
+        E = self.engine = engine or gpu()
         lib = E.lib
         r = self.ref = E.tensor(ref, what="nearest: ref")
         M = self.m = r.shape[0]
@@ -108,7 +64,7 @@ class NNIndex:
             lib.check(lib.nsr_nn_bounds(r.data_ptr(), M, self.fp64, bounds.data_ptr(), E.stream()), "nsr_nn_bounds")
             b = bounds[:6].cpu().numpy()
             self.plan = (C.c_double * 16)()
-            lib.check(lib.nsr_nn_plan(_dbl(b), M, self.plan), "nsr_nn_plan")
+            lib.check(lib.nsr_nn_plan(c_doubles(b), M, self.plan), "nsr_nn_plan")
             nbytes = lib.nsr_nn_workspace_bytes(self.plan, M)
             if nbytes < 0:
                 raise _capi.NsrError("nearest: invalid grid plan")
@@ -166,26 +122,26 @@ def _mean(E, dist):
 
 def accuracy(gt_points, rec_points, engine: Optional[Engine] = None) -> float:
     """Mean distance from each reconstructed point to the ground truth (eval_recon.py:32-36)."""
-    E = engine or _gpu()
+    E = engine or gpu()
     return _mean(E, nearest(rec_points, gt_points, E)[0])
 
 
 def completion(gt_points, rec_points, engine: Optional[Engine] = None) -> float:
     """Mean distance from each ground-truth point to the reconstruction (eval_recon.py:39-43)."""
-    E = engine or _gpu()
+    E = engine or gpu()
     return _mean(E, nearest(gt_points, rec_points, E)[0])
 
 
 def completion_ratio(gt_points, rec_points, dist_th=0.05, engine: Optional[Engine] = None) -> float:
     """Fraction of ground-truth points within ``dist_th`` of the reconstruction (eval_recon.py:24-29)."""
-    E = engine or _gpu()
+    E = engine or gpu()
     d = nearest(gt_points, rec_points, E)[0]
     return _dist_stats(E, d, dist_th)[1] / d.shape[0] if d.shape[0] else float("nan")
 
 
 def recon_metrics(gt_points, rec_points, dist_th=0.05, engine: Optional[Engine] = None):
     """(accuracy, completion, completion_ratio) from two nearest-neighbour passes (the reference makes three)."""
-    E = engine or _gpu()
+    E = engine or gpu()
     d_acc = nearest(rec_points, gt_points, E)[0]
     d_comp = nearest(gt_points, rec_points, E)[0]
     n = d_comp.shape[0]
@@ -196,21 +152,13 @@ def recon_metrics(gt_points, rec_points, dist_th=0.05, engine: Optional[Engine] 
 # --------------------------------------------------------------------------------------------------
 # surface sampling (trimesh.sample.sample_surface, eval_recon.py:103,106)
 # --------------------------------------------------------------------------------------------------
-def _faces(E: Engine, faces):
-    f = faces if isinstance(faces, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(faces))
-    f = f.detach().to(E.device)
-    if f.dim() != 2 or f.shape[1] != 3:
-        raise ValueError(f"faces must be [F, 3] (got {tuple(f.shape)})")
-    return f.to(torch.int32).contiguous()
-
-
 def sample_surface(vertices, faces, count: int, seed: int = 0, uniforms=None, engine: Optional[Engine] = None):
     """(points fp64 [count, 3], face_index int64 [count]): ``count`` points on the mesh, faces picked in proportion to their
     area.  ``uniforms`` [count, 3] fp64 (u0, a, b) replaces the in-kernel philox draws keyed by ``seed``."""
-    E = engine or _gpu()
+    E = engine or gpu()
     lib = E.lib
     v = E.tensor(vertices, torch.float64, "sample_surface: vertices")
-    f = _faces(E, faces)
+    f = E.faces(faces)
     n = int(count)
     pts = torch.empty((n, 3), dtype=torch.float64, device=E.device)
     fi = torch.empty(n, dtype=torch.int64, device=E.device)
@@ -230,12 +178,6 @@ def sample_surface(vertices, faces, count: int, seed: int = 0, uniforms=None, en
 # --------------------------------------------------------------------------------------------------
 # ICP (eval_recon.py:45-59: Open3D registration_icp, point to point)
 # --------------------------------------------------------------------------------------------------
-def _transform(E: Engine, pts: torch.Tensor, T: np.ndarray):
-    with E.guard():
-        E.lib.check(E.lib.nsr_transform_points(pts.data_ptr(), pts.shape[0], _dbl(np.asarray(T, np.float64)[:3, :4]), E.stream()),
-                    "nsr_transform_points")
-
-
 def _umeyama(stats: np.ndarray) -> np.ndarray:
     """The rigid update of Open3D's TransformationEstimationPointToPoint (Eigen::umeyama without scaling) from the
     correspondence statistics of nsr_icp_stats; identity without correspondences."""
@@ -263,7 +205,7 @@ def _icp(E: Engine, source, target, threshold=0.1, init=None, max_iteration=30, 
     n = pcd.shape[0]
     T = np.eye(4) if init is None else np.array(init, dtype=np.float64).reshape(4, 4)
     if not np.array_equal(T, np.eye(4)):
-        _transform(E, pcd, T)
+        E.transform(pcd, T)
     partial = torch.empty(int(lib.nsr_recon_partial_doubles(n)), dtype=torch.float64, device=E.device)
     out = torch.empty(17, dtype=torch.float64, device=E.device)
 
@@ -283,7 +225,7 @@ def _icp(E: Engine, source, target, threshold=0.1, init=None, max_iteration=30, 
         it += 1
         update = _umeyama(stats)
         T = update @ T
-        _transform(E, pcd, update)
+        E.transform(pcd, update)
         prev_f, prev_r = fitness, rmse
         stats, fitness, rmse = evaluate()
         if abs(prev_f - fitness) < relative_fitness and abs(prev_r - rmse) < relative_rmse:
@@ -296,34 +238,26 @@ def align_icp(source, target, threshold=0.1, init=None, max_iteration=30, relati
     """(T 4x4 fp64, fitness, inlier_rmse): point-to-point ICP of ``source`` onto ``target`` as Open3D's registration_icp
     (correspondences closer than ``threshold``, a rigid Umeyama update left-multiplied into T, stop when fitness and inlier
     RMSE both change by less than their tolerances, at most ``max_iteration`` updates)."""
-    T, fitness, rmse, _ = _icp(engine or _gpu(), source, target, threshold, init, max_iteration, relative_fitness, relative_rmse)
+    T, fitness, rmse, _ = _icp(engine or gpu(), source, target, threshold, init, max_iteration, relative_fitness, relative_rmse)
     return T, fitness, rmse
 
 
 # --------------------------------------------------------------------------------------------------
 # the 3-D metric (eval_recon.py:91-117)
 # --------------------------------------------------------------------------------------------------
-def _mesh(E: Engine, mesh):
-    if isinstance(mesh, str):
-        v, f = read_mesh(mesh)
-    else:
-        v, f = mesh[0], mesh[1]
-    return E.tensor(v, torch.float64, "mesh vertices"), _faces(E, f)
-
-
 def calc_3d_metric(rec_mesh, gt_mesh, align=True, n_points=200000, seed=0, engine: Optional[Engine] = None):
     """Accuracy [cm], completion [cm] and completion ratio [%] of a reconstructed mesh against the ground truth, as
     eval_recon.py's calc_3d_metric: (optionally) ICP-align the reconstruction's vertices to the ground truth's, sample
     ``n_points`` on each surface, then two nearest-neighbour passes.  Meshes: PLY paths or (vertices, faces) pairs (e.g. the
     device tensors ``Mesher.get_mesh`` returns).  The samplers are seeded (``seed`` for the reconstruction, ``seed + 1`` for
     the ground truth)."""
-    E = engine or _gpu()
-    rv, rf = _mesh(E, rec_mesh)
-    gv, gf = _mesh(E, gt_mesh)
+    E = engine or gpu()
+    rv, rf = E.mesh(rec_mesh)
+    gv, gf = E.mesh(gt_mesh)
     if align:
         T = align_icp(rv, gv, 0.1, engine=E)[0]
         rv = rv.clone()
-        _transform(E, rv, T)
+        E.transform(rv, T)
     rec_pts = sample_surface(rv, rf, n_points, seed=seed, engine=E)[0]
     gt_pts = sample_surface(gv, gf, n_points, seed=seed + 1, engine=E)[0]
     acc, comp, ratio = recon_metrics(gt_pts, rec_pts, 0.05, E)
@@ -350,19 +284,15 @@ def load_poses(path):
 def _w2c_rows(c2w_list) -> np.ndarray:
     """[K, 12] fp32: rows 0..2 of np.linalg.inv of each pose AS FLOAT32, which is what cull_mesh.py:49 computes (its poses are
     float32 tensors, so numpy inverts in single precision)."""
-    out = np.zeros((max(len(c2w_list), 1), 12), dtype=np.float32)
-    for k, c2w in enumerate(c2w_list):
-        c = c2w.detach().cpu().numpy() if isinstance(c2w, torch.Tensor) else np.asarray(c2w)
-        out[k] = np.linalg.inv(c.astype(np.float32)).astype(np.float32)[:3].reshape(-1)
-    return out
+    return w2c_rows(c2w_list, np.float32)
 
 
 def cull_masks(vertices, faces, c2w_list, H=680, W=1200, fx=600., fy=600., cx=599.5, cy=339.5, engine: Optional[Engine] = None):
     """(seen bool [V], keep bool [F]): vertices some pose sees, faces with at least one seen vertex (cull_mesh.py:45-75)."""
-    E = engine or _gpu()
+    E = engine or gpu()
     lib = E.lib
     v = E.tensor(vertices, what="cull_mesh: vertices")
-    f = _faces(E, faces)
+    f = E.faces(faces)
     K = len(c2w_list)
     w2c = torch.from_numpy(_w2c_rows(c2w_list)).to(E.device)
     seen = torch.empty(v.shape[0], dtype=torch.uint8, device=E.device)
@@ -379,109 +309,23 @@ def cull_mesh(vertices, faces, c2w_list, H=680, W=1200, fx=600., fy=600., cx=599
     """(vertices, faces) with every face removed that no pose of ``c2w_list`` sees any vertex of (cull_mesh.py).  As the
     reference's ``mesh.update_faces`` the vertex array is returned unchanged; ``compact=True`` drops unreferenced vertices
     and renumbers the faces."""
-    E = engine or _gpu()
+    E = engine or gpu()
     _, keep = cull_masks(vertices, faces, c2w_list, H, W, fx, fy, cx, cy, E)
     v = vertices if isinstance(vertices, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(vertices))
     v = v.to(E.device)
-    f = _faces(E, faces)[keep]
-    if compact:
-        used = torch.zeros(v.shape[0], dtype=torch.bool, device=E.device)
-        used[f.reshape(-1).long()] = True
-        remap = torch.cumsum(used.long(), 0) - 1
-        v, f = v[used], remap[f.long()].to(torch.int32)
-    return v, f
+    f = E.faces(faces)[keep]
+    return compact_mesh(v, f) if compact else (v, f)
 
 
-# --------------------------------------------------------------------------------------------------
-# PLY
-# --------------------------------------------------------------------------------------------------
-_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
-              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
-              "double": "f8", "float64": "f8"}
+# earlier names of the shared engine's pieces, still called by tools and tests written against them
+_gpu = gpu
 
 
-def read_mesh(path: str):
-    """(vertices float64 [V, 3], faces int64 [F, 3]) of a PLY file: binary little-endian or ASCII, any extra vertex properties
-    (normals, colours, alpha) skipped, the face list counted by uchar / int / uint with int / uint indices.  Other elements
-    are skipped; a face that is not a triangle is an error."""
-    with open(path, "rb") as fh:
-        data = fh.read()
-    end = data.find(b"end_header")
-    if not data.startswith(b"ply") or end < 0:
-        raise ValueError(f"{path}: not a PLY file")
-    body = data.index(b"\n", end) + 1
-    fmt, elements = None, []
-    for line in data[:end].decode("ascii", "replace").splitlines():
-        tok = line.split()
-        if not tok:
-            continue
-        if tok[0] == "format":
-            fmt = tok[1]
-        elif tok[0] == "element":
-            elements.append([tok[1], int(tok[2]), []])
-        elif tok[0] == "property" and elements:
-            if tok[1] == "list":
-                elements[-1][2].append((tok[4], "list", _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
-            else:
-                elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
-    if fmt not in ("ascii", "binary_little_endian"):
-        raise ValueError(f"{path}: PLY format {fmt!r} is not supported (ascii, binary_little_endian)")
-    verts = np.zeros((0, 3), np.float64)
-    faces = np.zeros((0, 3), np.int64)
-    if fmt == "ascii":
-        lines = data[body:].decode("ascii").split("\n")
-        pos = 0
-        for name, count, props in elements:
-            rows = []
-            for _ in range(count):
-                while not lines[pos].strip():
-                    pos += 1
-                rows.append(lines[pos].split())
-                pos += 1
-            if name == "vertex":
-                names = [p[0] for p in props]
-                cols = [names.index(c) for c in ("x", "y", "z")]
-                verts = np.array([[float(r[c]) for c in cols] for r in rows], dtype=np.float64).reshape(-1, 3)
-            elif name == "face":
-                fl = []
-                for r in rows:
-                    k = int(r[0])
-                    if k != 3:
-                        raise ValueError(f"{path}: face with {k} vertices (only triangles are supported)")
-                    fl.append([int(x) for x in r[1:4]])
-                faces = np.array(fl, dtype=np.int64).reshape(-1, 3)
-        return verts, faces
-    off = body
-    for name, count, props in elements:
-        if any(p[1] == "list" for p in props):
-            if len(props) != 1:
-                raise ValueError(f"{path}: element {name!r} mixes a list with other properties")
-            _, _, ct, it = props[0]
-            ct, it = np.dtype("<" + ct), np.dtype("<" + it)
-            if count == 0:
-                continue
-            # every face a triangle: fixed-size records; anything else is caught by the count check
-            rec = np.dtype([("n", ct), ("idx", it, 3)])
-            need = off + rec.itemsize * count
-            if need > len(data):
-                raise ValueError(f"{path}: truncated, or not every face is a triangle")
-            arr = np.frombuffer(data, dtype=rec, count=count, offset=off)
-            if not (arr["n"] == 3).all():
-                bad = int(arr["n"][arr["n"] != 3][0])
-                raise ValueError(f"{path}: face with {bad} vertices (only triangles are supported)")
-            if name == "face":
-                faces = arr["idx"].astype(np.int64)
-            off = need
-        else:
-            rec = np.dtype([(p[0], "<" + p[1]) for p in props])
-            arr = np.frombuffer(data, dtype=rec, count=count, offset=off)
-            if name == "vertex":
-                verts = np.stack([arr["x"], arr["y"], arr["z"]], 1).astype(np.float64)
-            off += rec.itemsize * count
-    return verts, faces
+def _transform(E: Engine, pts: torch.Tensor, T):
+    E.transform(pts, T)
 
 
-# the 2-D metric and the rasterizer live in raster.py (which imports this module's engine and ICP)
+# the 2-D metric and the rasterizer live in raster.py (which imports this module's ICP)
 from .raster import calc_2d_metric, cam_position, depth_l1, render_depth, sample_views  # noqa: E402
 
 

@@ -22,7 +22,8 @@ EMU_LIB = os.path.join(EMU_DIR, "libnsr_emu.so")
 def build_emu(force=False, variant=None, defs=""):
     """The emulator library; `variant` (a name) with `defs` (-D flags, e.g. the NSR_TEST_* hooks of nsr_api.cpp): a variant build
     of its own under tests/emu/_build_<variant>/."""
-    srcs = [os.path.join(ROOT, "nice_slam_amd", "csrc", f) for f in ("nsr_api.cpp", "nsr_kernels.h", "nsr_bwd2.h", "nsr_fwd2.h", "nsr_layout.h")]
+    srcs = [os.path.join(ROOT, "nice_slam_amd", "csrc", f) for f in ("nsr_api.cpp", "nsr_kernels.h", "nsr_bwd2.h", "nsr_fwd2.h", "nsr_layout.h",
+                                                                     "nsr_recon.h", "nsr_bound.h", "nsr_raster.h")]
     srcs += [os.path.join(EMU_DIR, f) for f in ("nsr_dev.h", "nsr_rt.h", "emu_runtime.cpp", "build_emu.sh")]
     srcs += [os.path.join(ROOT, "include", "nsr.h")]
     env, out = None, EMU_LIB

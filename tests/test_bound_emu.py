@@ -3,7 +3,6 @@
 tests/bound_reference.py (touched units and touch bits exact, tsdf / weight and surface points bit for bit), the host
 quickhull against scipy's Qhull, the point-in-hull test against a half-space test and Delaunay, and the C ABI's error paths."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -15,18 +14,15 @@ from scipy.spatial import ConvexHull, Delaunay  # noqa: E402
 import bound_reference as R  # noqa: E402
 import emu_harness  # noqa: E402
 from nice_slam_amd import _capi, bound  # noqa: E402
+from nice_slam_amd.engine import Engine  # noqa: E402
 
-BOUND_H = os.path.join(emu_harness.ROOT, "nice_slam_amd", "csrc", "nsr_bound.h")
 H, W, FX, FY, CX, CY = 60, 80, 40.0, 40.0, 39.5, 29.5
 SCALE = 4.0                                    # voxel_length 1/32 m: the 5 x 4 x 3 m room is 10 x 8 x 6 units
 
 
 @pytest.fixture(scope="module")
 def E():
-    # emu_harness' freshness check predates nsr_bound.h: rebuild when that header is newer than the emulator library
-    if not os.path.exists(emu_harness.EMU_LIB) or os.path.getmtime(emu_harness.EMU_LIB) < os.path.getmtime(BOUND_H):
-        emu_harness.build_emu(force=True)
-    return bound.Engine(emu_harness.emu_lib(), "cpu")
+    return Engine(emu_harness.emu_lib(), "cpu")
 
 
 @pytest.fixture(scope="module", params=[3, 6])

@@ -152,7 +152,7 @@ CASES = [  # show_forecast, depth_test, largest, mesh_bound, get_mask_use_all_fr
 
 @pytest.mark.parametrize("show_forecast,depth_test,largest,bounded,use_all", CASES)
 def test_get_mesh_end_to_end(tmp_path, show_forecast, depth_test, largest, bounded, use_all):
-    from nice_slam_amd.mesher import read_ply
+    from nice_slam_amd.ply import read_mesh
     sc, m, dec, grids, kfs, est = _setup(64, depth_test, largest)
     b = m.marching_cubes_bound.numpy()
     mesh_bound = _box(b[:, 0] + 0.15 * (b[:, 1] - b[:, 0]), b[:, 1] - 0.2 * (b[:, 1] - b[:, 0])) if bounded else None
@@ -171,7 +171,7 @@ def test_get_mesh_end_to_end(tmp_path, show_forecast, depth_test, largest, bound
         assert fore.any()
         want[fore] = [0, 255, 255]
     assert np.array_equal(gc.cpu().numpy(), want)
-    rv, rf, rc = read_ply(out)
+    rv, rf, rc = read_mesh(out, colors=True)
     assert np.array_equal(rv, (ev / m.scale).astype(np.float32)) and np.array_equal(rf, ef) and np.array_equal(rc[:, :3], want)
 
 

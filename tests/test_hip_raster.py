@@ -103,7 +103,7 @@ def test_metric_end_to_end():
 
 
 def test_depth_command(tmp_path):
-    from nice_slam_amd.mesher import write_ply
+    from nice_slam_amd.ply import write_ply
     v, f = room((20, 16, 12))
     gt, rec = str(tmp_path / "gt.ply"), str(tmp_path / "rec.ply")
     write_ply(gt, v, f)

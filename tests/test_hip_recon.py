@@ -107,12 +107,13 @@ def test_sampler():
 
 def test_icp_recovers_motion():
     from nice_slam_amd import recon
+    from nice_slam_amd.engine import gpu
     bf, bsp, borg = RS.bumpy_lattice(96)
     bv, _ = MR.marching_cubes(bf, 0.0, bsp, borg)
     M = RS.rigid([0.3, 0.5, 1.0], 5.0, [0.05, -0.03, 0.02])
     Mi = np.linalg.inv(M)
     src = bv @ Mi[:3, :3].T + Mi[:3, 3]
-    T, fit, rmse, it = recon._icp(recon._gpu(), torch.from_numpy(src).to(DEV), torch.from_numpy(bv).to(DEV))
+    T, fit, rmse, it = recon._icp(gpu(), torch.from_numpy(src).to(DEV), torch.from_numpy(bv).to(DEV))
     assert np.abs(T - M).max() < 1e-6 and fit == 1.0
     rT, rfit, rrmse, rit = icp_restated(src, bv)
     assert it == rit and np.abs(T - rT).max() < 1e-9
@@ -162,6 +163,7 @@ def cull_restated(verts, w2c, H=680, W=1200, fx=600., fy=600., cx=599.5, cy=339.
 
 def test_cull_2000_poses():
     from nice_slam_amd import recon
+    from nice_slam_amd.engine import w2c_rows
     rng = np.random.default_rng(8)
     verts = RS.room_surface_points(100000, 9)
     poses = []
@@ -170,7 +172,7 @@ def test_cull_2000_poses():
         M = RS.rigid([0.2 * np.sin(3 * a), 1.0, 0.1], np.rad2deg(a), [2.5 + np.cos(a), 2.0 + np.sin(a), 1.5])
         poses.append(torch.from_numpy(M).float())
     seen, keep = recon.cull_masks(torch.from_numpy(verts).to(DEV), torch.zeros((0, 3), dtype=torch.int32, device=DEV), poses)
-    ref = cull_restated(verts, recon._w2c_rows(poses))
+    ref = cull_restated(verts, w2c_rows(poses, np.float32))
     got = seen.cpu().numpy()
     assert 0 < ref.sum() < len(ref)
     assert np.array_equal(got, ref)
@@ -181,6 +183,7 @@ def test_room_end_to_end():
     path on the same field (tests/mesh_reference.py marching cubes + cKDTree, 200k samples each): accuracy 1.158 cm,
     completion 1.160 cm, ratio 100 % -- the sampling spacing of 200k points on ~105 m^2 dominates (the voxel is 2.5-4.1 cm)."""
     from nice_slam_amd import marching_cubes, recon
+    from nice_slam_amd.engine import gpu
     f, sp, org = RS.room_lattice(128)
     v, fc = marching_cubes(torch.from_numpy(f).to(DEV), 0.0, sp, org)
     gt = RS.room_surface_points(200000, 1)
@@ -188,9 +191,8 @@ def test_room_end_to_end():
     T = recon.align_icp(v, gtv)[0]
     assert np.abs(T - np.eye(4)).max() < 1e-4
     # the ground-truth "mesh" is a point set here: score the sampled reconstruction against the analytic samples
-    E = recon._gpu()
     rv = v.clone()
-    recon._transform(E, rv, T)
+    gpu().transform(rv, T)
     rec = recon.sample_surface(rv, fc, 200000, seed=0)[0]
     acc, comp, ratio = recon.recon_metrics(gtv, rec)
     assert acc < 0.0135 and comp < 0.0135 and ratio == 1.0
@@ -200,7 +202,7 @@ def test_room_end_to_end():
 
 
 def test_cli(tmp_path, gold):
-    from nice_slam_amd.mesher import write_ply
+    from nice_slam_amd.ply import write_ply
     bf, bsp, borg = RS.bumpy_lattice(64)
     bv, bfc = MR.marching_cubes(bf, 0.0, bsp, borg)
     a, b = str(tmp_path / "rec.ply"), str(tmp_path / "gt.ply")
@@ -219,6 +221,6 @@ def test_cli(tmp_path, gold):
     r = subprocess.run([sys.executable, "-m", "nice_slam_amd.recon", "cull", "--input_mesh", str(tmp_path / "in.ply"), "--traj", tp,
                         "--output_mesh", out], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr
-    from nice_slam_amd.recon import read_mesh
+    from nice_slam_amd.ply import read_mesh
     cv, cf = read_mesh(out)
     assert len(cv) == len(gold["cull/vertices"]) and len(cf) > 0

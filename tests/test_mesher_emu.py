@@ -1,35 +1,34 @@
-"""CPU tests of the mesh-extraction kernels (nice_slam_amd/csrc/nsr_kernels.h, "Mesh extraction"), executed under the
-emulator (tests/emu/) at small sizes, against the numpy restatements of tests/mesh_reference.py, scipy's connected
-components, and a golden minted from the reference's Mesher (tests/golden/make_golden_mesher.py)."""
-import ctypes as C
+"""CPU tests of the mesh-extraction kernels (nice_slam_amd/csrc/nsr_kernels.h, "Mesh extraction") and of the host glue in
+nice_slam_amd/mesher.py, executed under the emulator (tests/emu/) at small sizes, against the numpy restatements of
+tests/mesh_reference.py, scipy's connected components, and a golden minted from the reference's Mesher
+(tests/golden/make_golden_mesher.py)."""
 import os
 
 import numpy as np
 import pytest
+import torch
 
 import mesh_reference as MR
 from emu_harness import emu_lib, ptr
+from nice_slam_amd.engine import Engine, c_doubles
+from nice_slam_amd.mesher import face_components, keep_components, marching_cubes, point_masks_raw
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mesher_masks.npz")
 
 
-def dbl3(v):
-    return (C.c_double * 3)(*[float(x) for x in v])
+@pytest.fixture(scope="module")
+def E():
+    return Engine(emu_lib(), "cpu")
 
 
-def emu_mc(vol, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
-    lib = emu_lib()
-    vol = np.ascontiguousarray(vol, dtype=np.float32)
-    nx, ny, nz = vol.shape
-    ws = np.zeros(lib.nsr_mc_workspace_bytes(nx, ny, nz), dtype=np.uint8)
-    counts = np.zeros(2, dtype=np.int64)
-    lib.check(lib.nsr_mc_count(ptr(vol), nx, ny, nz, float(level), ptr(ws), ptr(counts), None), "nsr_mc_count")
-    nv, nf = (int(x) for x in counts)
-    verts = np.zeros((nv, 3), np.float64)
-    faces = np.zeros((nf, 3), np.int32)
-    lib.check(lib.nsr_mc_emit(ptr(vol), nx, ny, nz, float(level), dbl3(origin), dbl3(spacing), ptr(ws), nv, nf,
-                              ptr(verts), ptr(faces), None), "nsr_mc_emit")
-    return verts, faces
+def emu(E, fn, *args):
+    """one of the mesher's functions on host tensors under the emulator engine; numpy results"""
+    out = fn(*(torch.from_numpy(a) if isinstance(a, np.ndarray) else a for a in args), engine=E)
+    return tuple(t.numpy() for t in out) if isinstance(out, tuple) else out.numpy()
+
+
+def mc(E, vol, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+    return emu(E, marching_cubes, vol, level, spacing, origin)
 
 
 def lattice(n, shift=0.3):
@@ -62,7 +61,7 @@ def assert_same(got, ref):
 
 
 @pytest.mark.parametrize("name", ["sphere", "torus", "noise0", "noise1", "plane", "empty"])
-def test_mc_matches_restatement(name):
+def test_mc_matches_restatement(E, name):
     spacing, origin, level = (0.5, 0.25, 0.125), (-1.5, 2.0, 0.75), 0.0
     if name == "sphere":
         vol = sphere()
@@ -76,7 +75,7 @@ def test_mc_matches_restatement(name):
         vol[:, :, 5] += 0.5
     else:
         vol = np.full((9, 10, 11), -1.0, np.float32)
-    got = emu_mc(vol, level, spacing, origin)
+    got = mc(E, vol, level, spacing, origin)
     ref = MR.marching_cubes(vol, level, spacing, origin)
     assert_same(got, ref)
     if name == "empty":
@@ -86,8 +85,8 @@ def test_mc_matches_restatement(name):
 
 
 @pytest.mark.parametrize("seed", range(4))
-def test_mc_noise_is_crack_free(seed):
-    v, f = emu_mc(noise(seed), 0.0)
+def test_mc_noise_is_crack_free(E, seed):
+    v, f = mc(E, noise(seed), 0.0)
     assert len(f) > 1000
     assert set(MR.edge_use_counts(f).tolist()) == {2}     # every mesh edge of the closed surface: exactly two faces
 
@@ -100,14 +99,14 @@ def test_mc_table_properties():
         assert {e for t in tab[k] for e in t} == {e for t in tab[255 - k] for e in t}
 
 
-def test_mc_topology_volume_orientation():
+def test_mc_topology_volume_orientation(E):
     r = 12.0
-    v, f = emu_mc(sphere(32, r))
+    v, f = mc(E, sphere(32, r))
     assert MR.euler_characteristic(v, f) == 2
     vol = MR.signed_volume(v, f)
     assert vol > 0                                           # normals point toward decreasing field (outward)
     assert abs(vol / (4.0 / 3.0 * np.pi * r ** 3) - 1) < 0.01
-    v, f = emu_mc(torus())
+    v, f = mc(E, torus())
     assert MR.euler_characteristic(v, f) == 0 and MR.signed_volume(v, f) > 0
 
 
@@ -119,11 +118,11 @@ def test_mc_sphere_volume_at_r20():
     assert abs(MR.signed_volume(v, f) / (4.0 / 3.0 * np.pi * r ** 3) - 1) < 0.01
 
 
-def test_mc_vertices_on_straddling_edges():
+def test_mc_vertices_on_straddling_edges(E):
     vol = noise(7, (9, 10, 11))
     level = np.float32(0.2)
     sp, org = np.array([0.5, 0.25, 2.0]), np.array([1.0, -2.0, 3.0])
-    v, f = emu_mc(vol, level, sp, org)
+    v, f = mc(E, vol, level, sp, org)
     g = (v - org) / sp
     fl = np.floor(g + 1e-9)
     frac = g - fl
@@ -149,10 +148,11 @@ def test_mc_abi_errors():
     assert lib.nsr_mc_count(None, 4, 4, 4, 0.0, ptr(ws), ptr(counts), None) != 0
     assert lib.nsr_mc_count(ptr(vol), 4, 4, 4, 0.0, ptr(ws), None, None) != 0
     out_v, out_f = np.zeros((1, 3)), np.zeros((1, 3), np.int32)
-    assert lib.nsr_mc_emit(ptr(vol), 4, 4, 4, 0.0, dbl3((0, 0, 0)), dbl3((1, 1, 1)), ptr(ws), 1, 1 << 30, ptr(out_v), ptr(out_f), None) != 0
+    o, sp = c_doubles((0, 0, 0)), c_doubles((1, 1, 1))
+    assert lib.nsr_mc_emit(ptr(vol), 4, 4, 4, 0.0, o, sp, ptr(ws), 1, 1 << 30, ptr(out_v), ptr(out_f), None) != 0
     assert b"int32" in lib.nsr_last_error()
-    assert lib.nsr_mc_emit(ptr(vol), 4, 4, 4, 0.0, dbl3((0, 0, 0)), dbl3((1, 1, 1)), ptr(ws), 1 << 31, 1, ptr(out_v), ptr(out_f), None) != 0
-    assert lib.nsr_mc_emit(ptr(vol), 4, 4, 4, 0.0, dbl3((0, 0, 0)), dbl3((1, 1, 1)), ptr(ws), 1, 1, None, ptr(out_f), None) != 0
+    assert lib.nsr_mc_emit(ptr(vol), 4, 4, 4, 0.0, o, sp, ptr(ws), 1 << 31, 1, ptr(out_v), ptr(out_f), None) != 0
+    assert lib.nsr_mc_emit(ptr(vol), 4, 4, 4, 0.0, o, sp, ptr(ws), 1, 1, None, ptr(out_f), None) != 0
     assert lib.nsr_point_masks(None, 10, 5, 0, 1, None, None, None, 8, 8, 1.0, 1.0, 1.0, 1.0, None, None, None) != 0
     assert lib.nsr_point_masks(ptr(vol), 10, 5, 3, 0, None, None, None, 8, 8, 1.0, 1.0, 1.0, 1.0, None, ptr(ws), None) != 0
     assert lib.nsr_face_areas(None, None, 3, None, None) != 0
@@ -161,20 +161,8 @@ def test_mc_abi_errors():
 
 # ---- point masks ----
 
-def emu_masks(points, c2ws, depths, H, W, fx, fy, cx, cy, mode, chunk):
-    lib = emu_lib()
-    pts = np.ascontiguousarray(points, dtype=np.float32)
-    n, K = len(pts), len(c2ws)
-    w2c = np.zeros((max(K, 1), 12), np.float32)
-    for k, c in enumerate(c2ws):
-        w2c[k] = np.linalg.inv(np.asarray(c)).astype(np.float32)[:3].reshape(-1)
-    dep = np.ascontiguousarray(np.stack(depths).astype(np.float32)) if mode == 2 else None
-    lim = np.array([np.float32(d.max()) * np.float32(1.1) for d in depths], np.float32) if mode == 1 else None
-    ws = np.zeros(max(lib.nsr_point_masks_workspace_floats(n, chunk, K), 1), np.float32)
-    out = np.zeros(n, np.uint8)
-    lib.check(lib.nsr_point_masks(ptr(pts), n, chunk, mode, K, ptr(w2c), ptr(dep), ptr(lim), H, W, fx, fy, cx, cy, ptr(ws), ptr(out), None),
-              "nsr_point_masks")
-    return out
+def masks(E, points, c2ws, depths, H, W, fx, fy, cx, cy, mode, chunk):
+    return emu(E, point_masks_raw, points, c2ws, [torch.from_numpy(d) for d in depths], H, W, fx, fy, cx, cy, mode, chunk)
 
 
 @pytest.fixture(scope="module")
@@ -186,7 +174,7 @@ def mask_golden():
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2])
-def test_point_masks_match_reference_golden(mask_golden, mode):
+def test_point_masks_match_reference_golden(E, mask_golden, mode):
     g = mask_golden
     H, W = int(g["H"]), int(g["W"])
     fx, fy, cx, cy = (float(x) for x in g["intr"])
@@ -196,7 +184,7 @@ def test_point_masks_match_reference_golden(mask_golden, mode):
     else:
         c2ws, depths = list(g["kf_c2w"]), list(g["kf_depth"])
     want = g[f"mask_mode{mode}"]
-    got = emu_masks(pts, c2ws, depths, H, W, fx, fy, cx, cy, mode, chunk)
+    got = masks(E, pts, c2ws, depths, H, W, fx, fy, cx, cy, mode, chunk)
     ref = MR.point_masks(pts, c2ws, depths, H, W, fx, fy, cx, cy, mode, chunk)
     assert np.array_equal(got, ref)
     assert np.array_equal(got, want)
@@ -213,13 +201,13 @@ def test_point_masks_chunk_max_matters(mask_golden):
 
 
 @pytest.mark.parametrize("chunk", [64, 200, 5000])
-def test_point_masks_wave_reduced_chunk_max(mask_golden, chunk):
+def test_point_masks_wave_reduced_chunk_max(E, mask_golden, chunk):
     """chunks of >= 64 points: waves that lie in one chunk reduce the sampled depths before the atomic maximum"""
     g = mask_golden
     H, W = int(g["H"]), int(g["W"])
     fx, fy, cx, cy = (float(x) for x in g["intr"])
     args = (g["points"], list(g["kf_c2w"]), list(g["kf_depth"]), H, W, fx, fy, cx, cy, 2, chunk)
-    assert np.array_equal(emu_masks(*args), MR.point_masks(*args))
+    assert np.array_equal(masks(E, *args), MR.point_masks(*args))
 
 
 def test_grid_uniform_matches_reference_golden(mask_golden):
@@ -229,40 +217,13 @@ def test_grid_uniform_matches_reference_golden(mask_golden):
 
 # ---- connected components ----
 
-def emu_components(verts, faces):
-    """-> per-face label (largest face index of the component), per-face area, per-component area (by label order)"""
-    lib = emu_lib()
-    F = len(faces)
-    f = faces.astype(np.int64)
-    e = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
-    key = e.min(1) * len(verts) + e.max(1)
-    fid = np.tile(np.arange(F), 3)
-    order = np.argsort(key, kind="stable")
-    ks, fs = key[order], fid[order]
-    same = ks[1:] == ks[:-1]
-    pairs = np.ascontiguousarray(np.stack([fs[:-1][same], fs[1:][same]], 1).astype(np.int32))
-    parent = np.zeros(F, np.uint32)
-    changed = np.zeros(1, np.uint32)
-    lib.check(lib.nsr_cc_init(F, ptr(parent), ptr(changed), None))
-    r = 0
-    while True:
-        lib.check(lib.nsr_cc_round(ptr(pairs), len(pairs), F, ptr(parent), ptr(changed), r, None))
-        if changed[0] != r + 1:
-            break
-        r += 1
-    vv = np.ascontiguousarray(verts, np.float64)
-    ff = np.ascontiguousarray(faces, np.int32)
-    area = np.zeros(F)
-    lib.check(lib.nsr_face_areas(ptr(vv), ptr(ff), F, ptr(area), None))
-    label = parent.astype(np.int64)
-    order = np.argsort(label, kind="stable").astype(np.int64)
-    ls = label[order]
-    starts = np.concatenate([[0], np.nonzero(ls[1:] != ls[:-1])[0] + 1, [F]]).astype(np.int64)
-    seg_area = np.zeros(len(starts) - 1)
-    ls = np.ascontiguousarray(ls)
-    partial = np.zeros(F)
-    lib.check(lib.nsr_segment_sums(ptr(area), ptr(order), ptr(ls), F, ptr(starts), len(starts) - 1, ptr(partial), ptr(seg_area), None))
-    return label, area, seg_area, ls[starts[:-1]]
+def components(E, verts, faces):
+    """-> per-face label (largest face index of the component), per-face area, per-component area (by label order), component
+    labels; the per-face areas from the same mesh with every face split off into a component of its own"""
+    label, seg_area, first, _ = emu(E, face_components, verts, faces)
+    split = np.arange(3 * len(faces), dtype=np.int32).reshape(-1, 3)
+    area = emu(E, face_components, verts[faces].reshape(-1, 3), split)[1]
+    return label, area, seg_area, label[first]
 
 
 def two_spheres_and_blob():
@@ -274,9 +235,9 @@ def two_spheres_and_blob():
     return MR.marching_cubes(f.astype(np.float32))
 
 
-def test_components_match_scipy():
+def test_components_match_scipy(E):
     v, f = two_spheres_and_blob()
-    label, area, seg_area, seg_label = emu_components(v, f)
+    label, area, seg_area, seg_label = components(E, v, f)
     ref = MR.face_adjacency_components(f)
     assert len(np.unique(ref)) == 3 and len(seg_label) == 3
     # the same partition
@@ -290,53 +251,47 @@ def test_components_match_scipy():
         assert np.isclose(seg_area[s], area[label == lab].sum(), rtol=1e-12)
 
 
-def test_components_vertex_touch_stays_split():
+def test_components_vertex_touch_stays_split(E):
     # two triangle fans that share only vertex 0
     v = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0], [-1, 0, 0], [0, -1, 0], [-1, -1, 0]], np.float64)
     f = np.array([[0, 1, 2], [1, 3, 2], [0, 4, 5], [4, 6, 5]], np.int32)
-    label, *_ = emu_components(v, f)
+    label, *_ = components(E, v, f)
     assert label[0] == label[1] and label[2] == label[3] and label[0] != label[2]
     assert len(np.unique(MR.face_adjacency_components(f))) == 2
 
 
-def keep_rule(label, seg_area, seg_label, largest, min_area):
-    """Mesher.py:487-498 on the kernel outputs (what nice_slam_amd.mesher.keep_components does with torch)"""
-    first = np.array([np.nonzero(label == lab)[0].min() for lab in seg_label])
-    if largest:
-        best = seg_area == seg_area.max()
-        keep = np.zeros(len(seg_label), bool)
-        keep[np.argmin(np.where(best, first, len(label)))] = True
-    else:
-        keep = seg_area > min_area
-    return np.isin(label, seg_label[keep])
-
-
-def test_component_keep_rules():
+def test_component_keep_rules(E):
     v, f = two_spheres_and_blob()
-    label, area, seg_area, seg_label = emu_components(v, f)
     ref = MR.face_adjacency_components(f)
     ref_area = np.array([MR.face_areas(v, f)[ref == c].sum() for c in range(ref.max() + 1)])
-    keep_big = keep_rule(label, seg_area, seg_label, True, 0)
-    assert np.array_equal(keep_big, ref == np.argmax(ref_area))
+
+    def kept(largest, min_area):
+        """the corners of the faces keep_components keeps, in face order (its vertices are compacted, so compare positions)"""
+        kv, kf = emu(E, keep_components, v, f, largest, min_area)
+        assert len(np.unique(kf)) == len(kv)
+        return kv[kf]
+
+    keep_big = ref == np.argmax(ref_area)
+    assert np.array_equal(kept(True, 0), v[f[keep_big]])
     thr = np.sort(ref_area)[0] * 1.5                # drops the blob only
-    keep_thr = keep_rule(label, seg_area, seg_label, False, thr)
-    assert np.array_equal(keep_thr, ref_area[ref] > thr)
+    keep_thr = ref_area[ref] > thr
+    assert np.array_equal(kept(False, thr), v[f[keep_thr]])
     assert keep_thr.sum() < len(f) and keep_big.sum() < keep_thr.sum()
 
 
 # ---- PLY ----
 
 def test_ply_roundtrip(tmp_path):
-    from nice_slam_amd.mesher import read_ply, write_ply
+    from nice_slam_amd.ply import read_mesh, write_ply
     v, f = two_spheres_and_blob()
     col = (np.arange(len(v) * 3) % 256).astype(np.uint8).reshape(-1, 3)
     p = str(tmp_path / "m.ply")
     write_ply(p, v, f, col)
-    rv, rf, rc = read_ply(p)
+    rv, rf, rc = read_mesh(p, colors=True)
     assert np.array_equal(rv, v.astype(np.float32)) and np.array_equal(rf, f)
     assert np.array_equal(rc[:, :3], col) and (rc[:, 3] == 255).all()
     with open(p, "rb") as fh:
         assert fh.read(60).startswith(b"ply\nformat binary_little_endian 1.0\n")
     write_ply(p, v, f)
-    rv, rf, rc = read_ply(p)
+    rv, rf, rc = read_mesh(p, colors=True)
     assert rc is None and np.array_equal(rf, f)

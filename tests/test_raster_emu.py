@@ -13,20 +13,17 @@ from scipy.spatial import ConvexHull
 import emu_harness
 import raster_reference as R
 from nice_slam_amd import _capi, raster, recon
+from nice_slam_amd.engine import Engine
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "depth_eval.npz")
-RASTER_H = os.path.join(emu_harness.ROOT, "nice_slam_amd", "csrc", "nsr_raster.h")
 H, W, FX, FY, CX, CY = 48, 64, 40.0, 42.0, 31.5, 23.5
 ROOM_LO, ROOM_HI = np.array([0.0, 0.0, 0.0]), np.array([5.0, 4.0, 3.0])
 
 
 @pytest.fixture(scope="module")
 def E():
-    # emu_harness' freshness check predates nsr_raster.h: rebuild when that header is newer than the emulator library
-    if not os.path.exists(emu_harness.EMU_LIB) or os.path.getmtime(emu_harness.EMU_LIB) < os.path.getmtime(RASTER_H):
-        emu_harness.build_emu(force=True)
-    return recon.Engine(emu_harness.emu_lib(), "cpu")
+    return Engine(emu_harness.emu_lib(), "cpu")
 
 
 def render(E, v, f, c2w, near, far=20.0):
@@ -193,7 +190,7 @@ def test_metric_end_to_end(E, tmp_path):
     # the views lie in the camera box: inside the room, under the lifted centre's slab
     assert np.all((c2w[:, :3, 3] > ROOM_LO) & (c2w[:, :3, 3] < ROOM_HI))
     # the unseen cloud beside a PLY is required by default
-    from nice_slam_amd.mesher import write_ply
+    from nice_slam_amd.ply import write_ply
     gt = str(tmp_path / "gt.ply")
     write_ply(gt, gv, gf)
     with pytest.raises(FileNotFoundError, match="_pc_unseen.npy"):

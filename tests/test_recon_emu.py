@@ -12,19 +12,16 @@ from scipy.spatial import cKDTree
 
 import emu_harness
 from nice_slam_amd import _capi, recon
-from nice_slam_amd.mesher import write_ply
+from nice_slam_amd.engine import Engine, w2c_rows
+from nice_slam_amd.ply import write_ply
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "recon_eval.npz")
-RECON_H = os.path.join(emu_harness.ROOT, "nice_slam_amd", "csrc", "nsr_recon.h")
 
 
 @pytest.fixture(scope="module")
 def E():
-    # emu_harness' freshness check predates nsr_recon.h: rebuild when that header is newer than the emulator library
-    if not os.path.exists(emu_harness.EMU_LIB) or os.path.getmtime(emu_harness.EMU_LIB) < os.path.getmtime(RECON_H):
-        emu_harness.build_emu(force=True)
-    return recon.Engine(emu_harness.emu_lib(), "cpu")
+    return Engine(emu_harness.emu_lib(), "cpu")
 
 
 @pytest.fixture(scope="module")
@@ -287,7 +284,7 @@ def test_cull_matches_golden(E, gold, tmp_path):
     seen, keep = seen.numpy(), keep.numpy()
     # vertices within 1e-4 px (fp64) of a mask boundary are the only allowed exceptions: the fixture has none
     near = np.zeros(len(v), bool)
-    for u, vv, z in project64(v, recon._w2c_rows(poses)):
+    for u, vv, z in project64(v, w2c_rows(poses, np.float32)):
         near |= (np.minimum.reduce([np.abs(u), np.abs(u - 1200), np.abs(vv), np.abs(vv - 680)]) < 1e-4) & (z <= 0)
     assert near.sum() == 0
     assert np.array_equal(seen, gold["cull/vertex_seen"])

@@ -22,7 +22,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import raster_reference as R  # noqa: E402
-from nice_slam_amd import raster, recon  # noqa: E402
+from nice_slam_amd import raster  # noqa: E402
+from nice_slam_amd.engine import gpu, pose_stack, w2c_rows  # noqa: E402
 
 
 def room(scale):
@@ -45,11 +46,11 @@ def timed(fn, reps=5):
 
 def split(v, f, c2w, near):
     """(bin ms, depth ms) of one call each, library entry points timed apart with events"""
-    E = recon._gpu()
+    E = gpu()
     lib = E.lib
     vt = torch.from_numpy(v.astype(np.float32)).cuda()
     ft = torch.from_numpy(f).cuda()
-    w2c = torch.from_numpy(raster._w2c_rows(raster._c2w_stack(c2w))).cuda()
+    w2c = torch.from_numpy(w2c_rows(pose_stack(c2w), np.float64)).cuda()
     K = w2c.shape[0]
     ws = torch.empty(int(lib.nsr_raster_workspace_bytes(len(v), len(f), K, 500, 500)), dtype=torch.uint8, device="cuda")
     n = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -104,7 +105,7 @@ def main():
                                                                  "triangles": int(len(gf))}
         print("metric", align, dt, m["depth_l1_cm"], flush=True)
     # where the end-to-end time goes: the pieces of one run, timed apart
-    E = recon._gpu()
+    E = gpu()
     t = time.perf_counter()
     ext, tr = raster.cam_position(gvt, gft)
     res["cam_position_s"] = time.perf_counter() - t

@@ -110,7 +110,8 @@ def room_field(res):
 
 def analytic_field(res, reps):
     from nice_slam_amd import marching_cubes
-    from nice_slam_amd.mesher import keep_components, point_masks_raw, write_ply
+    from nice_slam_amd.mesher import keep_components, point_masks_raw
+    from nice_slam_amd.ply import write_ply
     H, W, fx, fy, cx, cy = 680, 1200, 600.0, 600.0, 599.5, 339.5
     cams = poses(np.array([3.0, 1.0, 2.5], np.float32))
     depths = [torch.full((H, W), 4.0) for _ in cams]

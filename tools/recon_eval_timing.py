@@ -59,8 +59,9 @@ def main():
     args = ap.parse_args()
     from scipy.spatial import cKDTree
     from nice_slam_amd import marching_cubes, recon
-    from nice_slam_amd.mesher import write_ply
-    E = recon._gpu()
+    from nice_slam_amd.engine import gpu
+    from nice_slam_amd.ply import write_ply
+    E = gpu()
     f, sp, org = RS.room_lattice(args.res)
     v, fc = marching_cubes(torch.from_numpy(f).to(DEV), 0.0, sp, org)
     out = {"device": torch.cuda.get_device_name(0), "mesh": {"res": args.res, "V": int(v.shape[0]), "F": int(fc.shape[0])}, "sizes": {}}
@@ -91,7 +92,7 @@ def main():
     # ICP on the mesh's vertices (a 2 deg / 2 cm offset), 30 iterations
     M = RS.rigid([0.3, 0.5, 1.0], 2.0, [0.02, -0.01, 0.01])
     src = v.clone()
-    recon._transform(E, src, np.linalg.inv(M))
+    E.transform(src, np.linalg.inv(M))
     t = time.perf_counter()
     T, fit, rmse, it = recon._icp(E, src, v, max_iteration=30, relative_fitness=0.0, relative_rmse=0.0)
     torch.cuda.synchronize()
