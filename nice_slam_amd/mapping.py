@@ -25,7 +25,7 @@ import torch
 from . import _capi
 from .common import _as_f32c, _require_cuda, _stream
 from .layout import param_count, stage_slots
-from .renderer import _fill_common, _gate, _prep_grids, render_backward
+from .renderer import RenderCall, _bound6, _gates, _prep_grids, forward_args, render_backward
 
 
 class WindowSamples:
@@ -47,9 +47,18 @@ def _frames_block(c2ws, depths, colors, dev):
 
 
 def _bound_arrays(bound):
-    lo = (C.c_double * 3)(*[float(bound[a][0]) for a in range(3)])
-    hi = (C.c_double * 3)(*[float(bound[a][1]) for a in range(3)])
-    return lo, hi
+    """the window kernels' bound arguments (lo, hi) as double[3] each (renderer._bound6)"""
+    b6 = _bound6(bound)
+    return (C.c_double * 3)(*b6[:3]), (C.c_double * 3)(*b6[3:])
+
+
+def _ray_buffer(N: int, buf: Optional[torch.Tensor] = None):
+    """The sampled rays of a window of N rays in ONE fp32 buffer: o [N,3] | d [N,3] | depth [N] | colour [N,3] | keep bytes [N].
+    Without ``buf``: its size in floats; with it: the views (rays_o, rays_d, gt_depth, gt_color, keep)."""
+    if buf is None:
+        return 10 * N + (N + 3) // 4
+    return (buf[:3 * N].view(N, 3), buf[3 * N:6 * N].view(N, 3), buf[6 * N:7 * N], buf[7 * N:10 * N].view(N, 3),
+            buf[10 * N:].view(torch.uint8)[:N])
 
 
 # Where the pixel indices of a window come from when the caller passes none (src/common.py:99: `torch.randint(h * w, (n,))`
@@ -68,6 +77,10 @@ def _capturing() -> bool:
     return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
+def _dev_key(dev) -> tuple:
+    return (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+
+
 def _set_state(st: torch.Tensor, seed: int):
     """(Re)start a draw state IN PLACE: a hipGraph captured earlier has the tensor's address baked into its window kernel, so
     the tensor must live -- at that address -- as long as the process; the replays then see the new seed."""
@@ -79,7 +92,7 @@ def _draw_state(dev) -> torch.Tensor:
     It follows torch.manual_seed (a new seed restarts the sequence, in place) and is advanced by the kernel itself, so replays
     of a captured graph draw afresh.  Never re-seeded while a stream is capturing (the copy would become part of the graph and
     reset the sequence on every replay): a capture keeps the state it finds."""
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    key = _dev_key(dev)
     seed = torch.initial_seed() & ((1 << 63) - 1)
     st = _DRAW_STATE.get(key)
     if st is None:
@@ -103,8 +116,7 @@ def seed_pixel_draws(seed: int, device=None):
     if device is None:
         keys = list(_DRAW_STATE)
     else:
-        d = torch.device(device)
-        keys = [(d.type, d.index if d.index is not None else torch.cuda.current_device())]
+        keys = [_dev_key(torch.device(device))]
     for key in keys:
         st = _DRAW_STATE.get(key)
         if st is None:
@@ -115,110 +127,93 @@ def seed_pixel_draws(seed: int, device=None):
 DEBUG_PTRS = {} if os.environ.get("NSR_DEBUG_PTRS") == "1" else None
 
 
-def _launch_window(indices, K, n, crop, intr, frames, bound6, sbuf, keep, kmax_ptr, dev, fused=None):
-    """``fused``: None, or (header tensor [4] fp32, zero span tensor) of a fused iteration -- the launch then also zero-fills the
-    span and writes the header {loss = 0 (fp64), kept max, 0} itself (nsr_get_samples_window_fused): no fill launch before it."""
+class _Window:
+    """One window to sample: ``n`` pixels from each of the K frames ``(c2ws, depths, colors)`` in the crop ``(H0, H1, W0, W1, W)``
+    under the intrinsics ``(fx, fy, cx, cy)``.  The pixels come from ``indices`` (given, or drawn by torch off the GPU), or the
+    window kernel draws them (``draw``: consumed by the launch, which writes them to ``indices``) from ``state`` (None: the
+    device's default draw state, above) -- with ``peers`` (ShardedMapping: the other ranks' seeds) repeating the peers' draws."""
+    __slots__ = ("indices", "K", "n", "crop", "intr", "c2ws", "depths", "colors", "bound", "dev", "draw", "state", "peers")
+
+    def __init__(self, crop, n, intr, c2ws, depths, colors, bound, device, indices=None, draw_state=None, peer_seeds=None):
+        self.K, self.n, self.dev = len(depths), int(n), torch.device(device)
+        self.crop, self.intr = tuple(int(v) for v in crop), tuple(float(v) for v in intr)
+        N = self.K * self.n
+        self.draw = indices is None and self.dev.type == "cuda"
+        if self.draw:
+            indices = torch.empty((N,), dtype=torch.int64, device=self.dev)          # filled by the window kernel (in-kernel draw, above)
+        elif indices is None:
+            H0, H1, W0, W1, _ = self.crop
+            # one draw for the window (common.py:99 per frame)
+            indices, draw_state = torch.randint((H1 - H0) * (W1 - W0), (N,), device=self.dev), None
+        else:
+            indices = indices.to(self.dev).reshape(-1).contiguous()
+        self.indices, self.state = indices, draw_state
+        self.peers = list(peer_seeds) if (self.draw and peer_seeds) else None
+        self.c2ws = [c if isinstance(c, torch.Tensor) else torch.as_tensor(c) for c in c2ws]
+        self.depths, self.colors, self.bound = list(depths), list(colors), bound
+
+
+def _launch_window(win: _Window, frames, rays, kmax_ptr, fused=None):
+    """One of the four window kernels over the sampled-ray views ``rays`` (``_ray_buffer``).  ``fused``: None, or (header tensor [4]
+    fp32, zero span tensor) of a fused iteration -- the launch then also zero-fills the span and writes the header {loss = 0 (fp64),
+    kept max, 0} itself (nsr_get_samples_window_fused): no fill launch before it."""
     lib = _capi.get_lib()
-    H0, H1, W0, W1, W_full = crop
-    fx, fy, cx, cy = intr
-    N = K * n
-    if fused is not None:
+    o, d, gd, gc, keep = rays
+    common = (win.K, win.n, *win.crop, *win.intr, frames, o.data_ptr(), d.data_ptr(), gd.data_ptr(), gc.data_ptr(),
+              *_bound_arrays(win.bound), keep.data_ptr())
+    draw, win.draw = win.draw, False                         # a kernel draw is used once: the pixels are in `indices` from now on
+    state = (win.state if win.state is not None else _draw_state(win.dev)) if (draw or fused is not None) else None
+    ind = win.indices.data_ptr()
+    stream = _stream(win.dev)
+    if fused is None and draw:                               # drawn by the kernel, written to `indices` for the backward / the caller
+        lib.check(lib.nsr_get_samples_window_draw(ind, state.data_ptr(), *common, kmax_ptr, stream), "nsr_get_samples_window_draw")
+    elif fused is None:
+        lib.check(lib.nsr_get_samples_window(ind, *common, kmax_ptr, stream), "nsr_get_samples_window")
+    else:
         hdr, zero = fused
-        draw = getattr(indices, "_nsr_draw", False)
-        indices._nsr_draw = False
-        state = getattr(indices, "_nsr_state", None)
-        if state is None:
-            state = _draw_state(dev)
-        peers = getattr(indices, "_nsr_peers", None)
-        if peers and draw:
+        tail = (hdr.data_ptr(), zero.data_ptr() if zero.numel() else None, zero.numel(), stream)
+        if win.peers and draw:
             # one rank of a ray-sharded iteration: the other ranks' draws are repeated for the batch-global depth cap (no collective)
-            seeds = (C.c_uint64 * len(peers))(*[int(v) for v in peers])
-            lib.check(lib.nsr_get_samples_window_sharded(indices.data_ptr(), state.data_ptr(), seeds, len(peers), K, n, H0, H1, W0, W1, W_full,
-                                                         fx, fy, cx, cy, frames, sbuf.data_ptr(), sbuf.data_ptr() + 12 * N, sbuf.data_ptr() + 24 * N,
-                                                         sbuf.data_ptr() + 28 * N, bound6[0], bound6[1], keep.data_ptr(), hdr.data_ptr(),
-                                                         zero.data_ptr() if zero.numel() else None, zero.numel(), _stream(dev)),
+            seeds = (C.c_uint64 * len(win.peers))(*[int(v) for v in win.peers])
+            lib.check(lib.nsr_get_samples_window_sharded(ind, state.data_ptr(), seeds, len(win.peers), *common, *tail),
                       "nsr_get_samples_window_sharded")
-            return
-        lib.check(lib.nsr_get_samples_window_fused(None if draw else indices.data_ptr(), indices.data_ptr() if draw else None, state.data_ptr(),
-                                                   K, n, H0, H1, W0, W1, W_full, fx, fy, cx, cy, frames, sbuf.data_ptr(),
-                                                   sbuf.data_ptr() + 12 * N, sbuf.data_ptr() + 24 * N, sbuf.data_ptr() + 28 * N, bound6[0],
-                                                   bound6[1], keep.data_ptr(), hdr.data_ptr(), zero.data_ptr() if zero.numel() else None,
-                                                   zero.numel(), _stream(dev)), "nsr_get_samples_window_fused")
-        return
-    if getattr(indices, "_nsr_draw", False):               # drawn by the kernel, written to `indices` for the backward / the caller
-        indices._nsr_draw = False
-        state = getattr(indices, "_nsr_state", None)
-        if state is None:
-            state = _draw_state(dev)
-        lib.check(lib.nsr_get_samples_window_draw(indices.data_ptr(), state.data_ptr(), K, n, H0, H1, W0, W1, W_full,
-                                                  fx, fy, cx, cy, frames, sbuf.data_ptr(), sbuf.data_ptr() + 12 * N,
-                                                  sbuf.data_ptr() + 24 * N, sbuf.data_ptr() + 28 * N, bound6[0], bound6[1],
-                                                  keep.data_ptr(), kmax_ptr, _stream(dev)), "nsr_get_samples_window_draw")
-        return
-    lib.check(lib.nsr_get_samples_window(indices.data_ptr(), K, n, H0, H1, W0, W1, W_full, fx, fy, cx, cy, frames,
-                                         sbuf.data_ptr(), sbuf.data_ptr() + 12 * N, sbuf.data_ptr() + 24 * N, sbuf.data_ptr() + 28 * N,
-                                         bound6[0], bound6[1], keep.data_ptr(), kmax_ptr, _stream(dev)), "nsr_get_samples_window")
+        else:
+            lib.check(lib.nsr_get_samples_window_fused(None if draw else ind, ind if draw else None, state.data_ptr(), *common, *tail),
+                      "nsr_get_samples_window_fused")
 
 
 class _WindowFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, meta, *c2ws):
-        with _capi.on_device(meta[8]):
-            return _WindowFn._forward_impl(ctx, meta, *c2ws)
-
-    @staticmethod
-    def _forward_impl(ctx, meta, *c2ws):
-        indices, K, n, crop, intr, depths, colors, bound, dev = meta
-        N = K * n
-        frames, hold = _frames_block(c2ws, depths, colors, dev)
-        sbuf = torch.empty((10 * N + (N + 3) // 4,), dtype=torch.float32, device=dev)      # o | d | depth | colour | keep bytes
-        keep = sbuf[10 * N:].view(torch.uint8)[:N]
-        kmax = torch.zeros((1,), dtype=torch.float32, device=dev)
-        _launch_window(indices, K, n, crop, intr, frames, _bound_arrays(bound), sbuf, keep, kmax.data_ptr(), dev)
-        ctx.meta = (indices, K, n, crop, intr, [tuple(c.shape) for c in c2ws], [c.dtype for c in c2ws], [c.device for c in c2ws])
-        outs = (sbuf[:3 * N].view(N, 3), sbuf[3 * N:6 * N].view(N, 3), sbuf[6 * N:7 * N], sbuf[7 * N:10 * N].view(N, 3), keep, kmax)
-        ctx.mark_non_differentiable(*outs[2:])
-        return outs
+    def forward(ctx, win, *c2ws):
+        with _capi.on_device(win.dev):
+            N = win.K * win.n
+            frames, hold = _frames_block(c2ws, win.depths, win.colors, win.dev)
+            sbuf = torch.empty((_ray_buffer(N),), dtype=torch.float32, device=win.dev)
+            rays = _ray_buffer(N, sbuf)
+            kmax = torch.zeros((1,), dtype=torch.float32, device=win.dev)
+            _launch_window(win, frames, rays, kmax.data_ptr())
+        ctx.win = win
+        ctx.mark_non_differentiable(*rays[2:], kmax)
+        return (*rays, kmax)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_o, g_d, *_):
-        indices, K, n, crop, intr, shapes, dtypes, devs = ctx.meta
-        grads, _ = pose_grads(indices, K, n, crop, intr, g_o.contiguous(), g_d.contiguous(), shapes)
-        return (None, *[g.to(device=dv, dtype=dt) for g, dv, dt in zip(grads, devs, dtypes)])
+        grads, _ = pose_grads(ctx.win, g_o.contiguous(), g_d.contiguous())
+        return (None, *[g.to(device=c.device, dtype=c.dtype) for g, c in zip(grads, ctx.win.c2ws)])
 
 
-def pose_grads(indices, K, n, crop, intr, g_o, g_d, shapes, out=None) -> List[torch.Tensor]:
+def pose_grads(win: _Window, g_o, g_d, out=None) -> List[torch.Tensor]:
     """d c2w[k] (shape of the pose, rows 0..2 filled) from the gradients of the window's rays: one launch.  ``out``: an already
     zero-filled [K, 4, 4] fp32 tensor (the fused iteration's one zero-filled buffer has room for it), else allocated here."""
     lib = _capi.get_lib()
     dev = g_o.device
-    H0, H1, W0, W1, _ = crop
-    fx, fy, cx, cy = intr
+    H0, H1, W0, W1, _ = win.crop
     if out is None:
-        out = torch.zeros((K, 4, 4), dtype=torch.float32, device=dev)
-    lib.check(lib.nsr_pose_grad(indices.data_ptr(), K, n, H0, H1, W0, W1, fx, fy, cx, cy, g_o.data_ptr(), g_d.data_ptr(),
+        out = torch.zeros((win.K, 4, 4), dtype=torch.float32, device=dev)
+    lib.check(lib.nsr_pose_grad(win.indices.data_ptr(), win.K, win.n, H0, H1, W0, W1, *win.intr, g_o.data_ptr(), g_d.data_ptr(),
                                 out.data_ptr(), 16, _stream(dev)), "nsr_pose_grad")
-    return [out[k, :shp[0], :] for k, shp in enumerate(shapes)], out
-
-
-def _window_meta(H0, H1, W0, W1, n, W, fx, fy, cx, cy, c2ws, depths, colors, bound, device, indices, draw_state=None, peer_seeds=None):
-    K = len(depths)
-    dev = torch.device(device)
-    if indices is None and dev.type == "cuda":
-        indices = torch.empty((K * n,), dtype=torch.int64, device=dev)            # filled by the window kernel (in-kernel draw, above)
-        indices._nsr_draw = True
-        indices._nsr_state = draw_state                                           # None: the device's default state
-        indices._nsr_peers = list(peer_seeds) if peer_seeds else None              # (ShardedMapping: the other ranks' seeds)
-    elif indices is None:
-        indices = torch.randint((H1 - H0) * (W1 - W0), (K * n,), device=dev)      # one draw for the window (common.py:99 per frame)
-    else:
-        indices = indices.to(dev).reshape(-1).contiguous().view(-1)             # (a tensor object of our own: it carries the state below)
-        indices._nsr_state = draw_state
-    c2ws = [c if isinstance(c, torch.Tensor) else torch.as_tensor(c) for c in c2ws]
-    crop = (int(H0), int(H1), int(W0), int(W1), int(W))
-    intr = (float(fx), float(fy), float(cx), float(cy))
-    return (indices, K, int(n), crop, intr, list(depths), list(colors), bound, dev), c2ws
+    return [out[k, :c.shape[0], :] for k, c in enumerate(win.c2ws)], out
 
 
 def get_samples_window(H0, H1, W0, W1, n, H, W, fx, fy, cx, cy, c2ws: Sequence[torch.Tensor], depths: Sequence[torch.Tensor],
@@ -228,40 +223,46 @@ def get_samples_window(H0, H1, W0, W1, n, H, W, fx, fy, cx, cy, c2ws: Sequence[t
     bounding-box pre-filter of :471-481 as ``keep`` (bool per ray) and ``kept_max`` (1-element tensor: maximum depth over
     the kept rays, to be passed as ``render_batch_ray(..., gt_max=kept_max)``).  ``indices``: optional [K*n] flat crop
     indices (default: drawn inside the kernel, see the in-kernel draw at the top of this module)."""
-    meta, c2ws = _window_meta(H0, H1, W0, W1, n, W, fx, fy, cx, cy, c2ws, depths, colors, bound, device, indices)
-    _require_cuda(depths[0] if depths[0].is_cuda else torch.empty(0, device=meta[-1]), "get_samples_window: frames")
-    ro, rd, gd, gc, keep, kmax = _WindowFn.apply(meta, *c2ws)
+    win = _Window((H0, H1, W0, W1, W), n, (fx, fy, cx, cy), c2ws, depths, colors, bound, device, indices)
+    _require_cuda(depths[0] if depths[0].is_cuda else torch.empty(0, device=win.dev), "get_samples_window: frames")
+    ro, rd, gd, gc, keep, kmax = _WindowFn.apply(win, *win.c2ws)
     w = WindowSamples()
-    w.rays_o, w.rays_d, w.gt_depth, w.gt_color, w.keep, w.kept_max, w.indices, w.geom = ro, rd, gd, gc, keep.bool(), kmax, meta[0], meta[1:5]
+    w.rays_o, w.rays_d, w.gt_depth, w.gt_color, w.keep, w.kept_max = ro, rd, gd, gc, keep.bool(), kmax
+    w.indices, w.geom = win.indices, (win.K, win.n, win.crop, win.intr)
     return w
 
 
 # --------------------------------------------------------------------------------------------------------------------
 # sampling + render + mapping loss as one autograd node
 # --------------------------------------------------------------------------------------------------------------------
+class _LossState:
+    """What the backward of a fused iteration needs of its forward (released by the first backward)."""
+    __slots__ = ("call", "win", "need", "dl_depth", "dl_rgb", "zero", "pose_buf", "loss", "loss32", "sharder", "from_forward")
+
+
 class _MappingLossFn(torch.autograd.Function):
-    """inputs: K poses, one grid per decoder of the stage, one gate per decoder (see renderer._RenderFn)."""
+    """inputs: renderer, decoders, stage, the window (``_Window``), w_color, sharder, out, track, then the K poses, one grid per
+    decoder of the stage and one gate per decoder (see renderer._RenderFn)."""
 
     @staticmethod
-    def forward(ctx, meta, *tensors):
-        with _capi.on_device(meta[3][8]):
-            return _MappingLossFn._forward_impl(ctx, meta, *tensors)
+    def forward(ctx, renderer, decoders, stage, win, w_color, sharder, out, track, *tensors):
+        with _capi.on_device(win.dev):
+            return _MappingLossFn._forward_impl(ctx, renderer, decoders, stage, win, w_color, sharder, out, track, *tensors)
 
     @staticmethod
-    def _forward_impl(ctx, meta, *tensors):
-        renderer, decoders, stage, wmeta, w_color, sharder, out, track = meta      # track: None | (handle_dynamic, use_color)
-        indices, K, n, crop, intr, depths, colors, bound, dev = wmeta
+    def _forward_impl(ctx, renderer, decoders, stage, win, w_color, sharder, out, track, *tensors):
+        # track: None | (handle_dynamic, use_color)
+        K, N, dev = win.K, win.K * win.n, win.dev
         lib = _capi.get_lib()
         slots = stage_slots(stage)
-        c2ws = tensors[:K]
-        grids = dict(zip(slots, tensors[K:K + len(slots)]))
+        grids = dict(zip(slots, tensors[K:]))
         stream = _stream(dev)
-        N = K * n
         guided = stage != "coarse"
         S = renderer.N_samples + (renderer.N_surface if guided else 0)
-        need_pose = any(ctx.needs_input_grad[1:1 + K])
-        need_grid = ctx.needs_input_grad[1 + K:1 + K + len(slots)]
-        need_par = ctx.needs_input_grad[1 + K + len(slots):1 + K + 2 * len(slots)]
+        need = ctx.needs_input_grad[8:]
+        need_pose = any(need[:K])
+        need_grid = need[K:K + len(slots)]
+        need_par = need[K + len(slots):K + 2 * len(slots)]
         need_bwd = need_pose or any(need_grid) or any(need_par)
         # ONE zero-filled buffer: loss (fp64) | kept_max | pad | every gradient of the backward (renderer.render_backward)
         n_grad = 0
@@ -271,46 +272,37 @@ class _MappingLossFn(torch.autograd.Function):
         n_pose = 16 * K if need_pose else 0                     # d c2w of the window (pose_grads), behind the gradients
         # (round 5: not a fill launch -- the window kernel zero-fills it beside its sampling blocks and writes the header)
         fuse_fill = N > 0
-        if fuse_fill and not getattr(indices, "_nsr_draw", False) and getattr(indices, "_nsr_state", None) is None and _capturing() \
-                and (dev.type, dev.index if dev.index is not None else torch.cuda.current_device()) not in _DRAW_STATE:
+        if fuse_fill and not win.draw and win.state is None and _capturing() and _dev_key(dev) not in _DRAW_STATE:
             # explicit indices, nothing is drawn -- but the fused launch borrows the device's draw state for its hand-off words, and that
             # tensor cannot be created under graph capture (it must outlive every graph): the separate fill + plain window launch instead
             fuse_fill = False
         Z = (torch.empty if fuse_fill else torch.zeros)((4 + n_grad + n_pose,), dtype=torch.float32, device=dev)
         loss = Z[:2].view(torch.float64)
         kmax = Z[2:3]
-        frames, hold = _frames_block(c2ws, depths, colors, dev)
+        frames, hold = _frames_block(win.c2ws, win.depths, win.colors, dev)
         # ONE allocation for everything the iteration writes besides the gradients: forward results (fp64 part, then fp32
         # part) and, behind them, the sampled rays (measured: no faster than two allocations, one launch-side call fewer)
         n64 = 3 * N + N * S
         nf32 = N * S * 4 + 6 * N
-        n_s = 10 * N + (N + 3) // 4
+        n_s = _ray_buffer(N)
         FS = torch.empty((n64 + (nf32 + 1) // 2 + (n_s + 1) // 2,), dtype=torch.float64, device=dev)
         F = FS[:n64 + (nf32 + 1) // 2]
         sbuf = FS[n64 + (nf32 + 1) // 2:].view(torch.float32)[:n_s]
-        keep = sbuf[10 * N:].view(torch.uint8)[:N]
-        _launch_window(indices, K, n, crop, intr, frames, _bound_arrays(bound), sbuf, keep, kmax.data_ptr(), dev,
-                       fused=(Z[:4], Z[4:]) if fuse_fill else None)
-        if sharder is not None and not (fuse_fill and getattr(indices, "_nsr_peers", None)):
+        rays = _ray_buffer(N, sbuf)
+        rays_o, rays_d, gt_depth, gt_color, keep = rays
+        _launch_window(win, frames, rays, kmax.data_ptr(), fused=(Z[:4], Z[4:]) if fuse_fill else None)
+        if sharder is not None and not (fuse_fill and win.peers):
             # the depth cap is a scalar of the WHOLE batch (Renderer.py:109,144): one 4-byte MAX all-reduce -- unless the window kernel
             # has just re-drawn the other ranks' pixels itself and its header already holds the maximum over the union (peer seeds)
             sharder.reduce_max(kmax)
-        rays_o, rays_d = sbuf[:3 * N].view(N, 3), sbuf[3 * N:6 * N].view(N, 3)
-        gt_depth, gt_color = sbuf[6 * N:7 * N], sbuf[7 * N:10 * N].view(N, 3)
         # forward results: depth | var | dl_depth | zvals (fp64), then raw | rgb | dl_rgb (fp32)
         f32 = F[n64:].view(torch.float32)
         depth, var, dl_depth, zvals = F[:N], F[N:2 * N], F[2 * N:3 * N], F[3 * N:n64].view(N, S)
         raw, rgb, dl_rgb = f32[:N * S * 4].view(N, S, 4), f32[N * S * 4:N * S * 4 + 3 * N].view(N, 3), f32[N * S * 4 + 3 * N:N * S * 4 + 6 * N].view(N, 3)
-        flats = {s: decoders.sub(s).flat_params() for s in slots}
-        packed = {s: decoders.sub(s).packed_params(lib, stream) for s in slots}
-        a = _capi.NsrRenderArgs.from_buffer_copy(renderer._arg_template)
-        a.n_samples, a.n_surface, a.n_rays = renderer.N_samples, renderer.N_surface, N
-        a.rays_o, a.rays_d = rays_o.data_ptr(), rays_d.data_ptr()
-        a.gt_depth, a.gt_max = gt_depth.data_ptr(), kmax.data_ptr()
-        _fill_common(a, stage, renderer.bound, decoders, grids, packed, flats)
-        if not guided:
-            a.n_surface = 0
-        a.depth, a.var, a.rgb, a.raw, a.zvals = depth.data_ptr(), var.data_ptr(), rgb.data_ptr(), raw.data_ptr(), zvals.data_ptr()
+        call = RenderCall(renderer, decoders, stage, grids, rays_o, rays_d, gt_depth, hook=None if sharder is None else sharder.collect)
+        acts = forward_args(call, renderer.N_surface if guided else 0, kmax, (depth, var, rgb, raw, zvals),
+                            [not g_ for g_ in need_par] if need_bwd else None)
+        a = call.args
         if track is None:                                       # the mapper's L1 loss is accumulated by the forward kernel itself
             a.gt_color, a.loss, a.w_color = gt_color.data_ptr(), loss.data_ptr(), float(w_color)
             a.dl_depth, a.dl_rgb = dl_depth.data_ptr(), dl_rgb.data_ptr()
@@ -320,7 +312,6 @@ class _MappingLossFn(torch.autograd.Function):
         a.skip_masked = 1 if (renderer.skip_masked_rays and need_bwd) else 0
         if need_bwd and renderer.profile_fwd_events is not None:
             a.ev_pass_start, a.ev_pass_stop = renderer.profile_fwd_events(stage)
-        acts = renderer._attach_acts(a, stage, N, S, dev, masks_only=[not g_ for g_ in need_par]) if need_bwd else None
         if DEBUG_PTRS is not None:                              # measurement (bench.py NSR_DEBUG_PTRS=1): where the iteration's buffers landed
             DEBUG_PTRS[stage] = {"Z": Z.data_ptr(), "Z_bytes": 4 * Z.numel(), "FS": FS.data_ptr(), "acts": None if acts is None else acts.data_ptr(),
                                  "acts_bytes": None if acts is None else 4 * acts.numel(), "grids": {s: grids[s].data_ptr() for s in slots}}
@@ -334,49 +325,48 @@ class _MappingLossFn(torch.autograd.Function):
                                             dl_depth.data_ptr(), dl_rgb.data_ptr(), stream), "nsr_tracking_loss")
         if out is not None:
             out.update(rays_o=rays_o, rays_d=rays_d, gt_depth=gt_depth, gt_color=gt_color, keep=keep, kept_max=kmax, depth=depth,
-                       uncertainty=var, color=rgb, indices=indices)
+                       uncertainty=var, color=rgb, indices=win.indices)
+        ctx.state = None
         if need_bwd:
-            ctx.sharder, ctx.loss32 = sharder, Z[3:4]
-            ctx.from_forward = track is None            # the mapper's loss epilogue wrote dl_* AND d raw; nobody touches them in between
-            ctx.pose_buf = Z[4 + n_grad:4 + n_grad + n_pose].view(K, 4, 4) if need_pose else None
-            ctx.state = (a, (renderer, decoders, stage, S, None if sharder is None else sharder.collect),
-                         ([kmax, F, sbuf, Z, hold, acts], rays_o, rays_d, gt_depth, grids, flats, packed, raw, depth),
-                         (need_pose, need_grid, need_par), dl_depth,
-                         dl_rgb if (stage == "color" and (track is None or track[1])) else None, Z[4:],
-                         (indices, K, n, crop, intr, [tuple(c.shape) for c in c2ws], [c.dtype for c in c2ws], [c.device for c in c2ws]))
+            call.hold += [F, sbuf, Z, hold, acts]
+            st = ctx.state = _LossState()
+            st.call, st.win, st.need, st.sharder = call, win, (need_pose, need_pose, need_grid, need_par), sharder
+            st.dl_depth, st.dl_rgb = dl_depth, dl_rgb if (stage == "color" and (track is None or track[1])) else None
+            st.zero, st.pose_buf = Z[4:], Z[4 + n_grad:4 + n_grad + n_pose].view(K, 4, 4) if need_pose else None
+            st.loss, st.loss32 = loss, Z[3:4]
+            st.from_forward = track is None             # the mapper's loss epilogue wrote dl_* AND d raw; nobody touches them in between
         return loss[0]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_loss):
         with _capi.on_device(g_loss.device):
-            return _MappingLossFn._backward_impl(ctx, g_loss)
+            st = ctx.state
+            if st is None:
+                raise RuntimeError("nice_slam_amd: backward through mapping_loss / tracking_loss a second time is not supported "
+                                   "(the saved buffers are released after the first backward)")
+            # d loss / d outputs were written by the forward for an incoming gradient of 1 (loss.backward(), Mapper.py:503); whatever
+            # autograd hands over (loss * w, loss / n, a GradScaler ...) multiplies them inside the backward kernel: device scalar,
+            # no host sync, no extra launch
+            gs = g_loss.detach().to(device=st.dl_depth.device, dtype=torch.float64).reshape(1)
+            d_o, d_d, d_grids = render_backward(st.call, st.need, st.dl_depth, None, st.dl_rgb, zero_buf=st.zero, grad_scale=gs,
+                                                loss_grads_from_forward=st.from_forward)
+            win = st.win
+            gp, pose_base = pose_grads(win, d_o, d_d, out=st.pose_buf) if st.need[0] else ([None] * win.K, None)
+            if st.sharder is not None:                         # multi-GPU: ONE packed all-reduce of everything this iteration produced
+                st.loss32.copy_(st.loss.to(torch.float32))
+                st.sharder.exchange([("grid_" + s_, g) for s_, g in zip(st.call.slots, d_grids) if g is not None], pose_base, st.loss32)
+            g_pose = [g.to(device=c.device, dtype=c.dtype) if nd else None
+                      for g, c, nd in zip(gp, win.c2ws, ctx.needs_input_grad[8:8 + win.K])]
+            ctx.state = None
+            return (None,) * 8 + (*g_pose, *d_grids, *([None] * len(d_grids)))
 
-    @staticmethod
-    def _backward_impl(ctx, g_loss):
-        if ctx.state is None:
-            raise RuntimeError("nice_slam_amd: backward through mapping_loss / tracking_loss a second time is not supported (the "
-                               "saved buffers are released after the first backward)")
-        a, meta, kept, (need_pose, need_grid, need_par), dl_depth, dl_rgb, zero_buf, wm = ctx.state
-        # d loss / d outputs were written by the forward for an incoming gradient of 1 (loss.backward(), Mapper.py:503); whatever
-        # autograd hands over (loss * w, loss / n, a GradScaler ...) multiplies them inside the backward kernel: device scalar,
-        # no host sync, no extra launch
-        gs = g_loss.detach().to(device=dl_depth.device, dtype=torch.float64).reshape(1)
-        d_o, d_d, d_grids = render_backward(a, meta, kept, (need_pose, need_pose, need_grid, need_par), dl_depth, None, dl_rgb,
-                                            zero_buf=zero_buf, grad_scale=gs, loss_grads_from_forward=ctx.from_forward)
-        indices, K, n, crop, intr, shapes, dtypes, devs = wm
-        g_pose = [None] * K
-        gp, pose_base = None, None
-        if need_pose:
-            gp, pose_base = pose_grads(indices, K, n, crop, intr, d_o, d_d, shapes, out=ctx.pose_buf)
-        if ctx.sharder is not None:                            # multi-GPU: ONE packed all-reduce of everything this iteration produced
-            ctx.loss32.copy_(kept[0][3][:2].view(torch.float64).to(torch.float32))
-            ctx.sharder.exchange([("grid_" + s_, g) for s_, g in zip(stage_slots(meta[2]), d_grids) if g is not None], pose_base, ctx.loss32)
-        if need_pose:
-            g_pose = [g.to(device=dv, dtype=dt) if nd else None for g, dv, dt, nd in zip(gp, devs, dtypes, ctx.needs_input_grad[1:1 + K])]
-        ctx.state = None
-        nslots = len(d_grids)
-        return (None, *g_pose, *d_grids, *([None] * nslots))
+
+def _fused_loss(renderer, c, decoders, stage, win, w_color, sharder, out, track):
+    slots = stage_slots(stage)
+    grids = _prep_grids(c, stage, win.dev)
+    return _MappingLossFn.apply(renderer, decoders, stage, win, w_color, sharder, out, track, *win.c2ws, *[grids[s] for s in slots],
+                                *_gates(renderer, decoders, slots, win.dev))
 
 
 def mapping_loss(renderer, c, decoders, frames: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]], pixs_per_image: int,
@@ -398,15 +388,10 @@ def mapping_loss(renderer, c, decoders, frames: Sequence[Tuple[torch.Tensor, tor
         raise ValueError("the coarse mapper optimises in stage 'coarse' (Mapper.py:403-404)")
     dev = torch.device(device) if device is not None else frames[0][1].device
     H0, H1, W0, W1 = crop if crop is not None else (0, renderer.H, 0, renderer.W)
-    wmeta, c2ws = _window_meta(H0, H1, W0, W1, pixs_per_image, renderer.W, renderer.fx, renderer.fy, renderer.cx, renderer.cy,
-                               [f[0] for f in frames], [f[1] for f in frames], [f[2] for f in frames], renderer.bound, dev, indices,
-                               draw_state=draw_state, peer_seeds=peer_seeds)
-    slots = stage_slots(stage)
-    grids = _prep_grids(c, stage, dev)
-    gates = [_gate(dev, torch.is_grad_enabled() and decoders.sub(s).wants_grad() and
-                   (renderer.decoder_grads is None or s in renderer.decoder_grads)) for s in slots]
-    meta = (renderer, decoders, stage, wmeta, w_color, sharder, out, None)
-    return _MappingLossFn.apply(meta, *c2ws, *[grids[s] for s in slots], *gates)
+    win = _Window((H0, H1, W0, W1, renderer.W), pixs_per_image, (renderer.fx, renderer.fy, renderer.cx, renderer.cy),
+                  [f[0] for f in frames], [f[1] for f in frames], [f[2] for f in frames], renderer.bound, dev, indices,
+                  draw_state=draw_state, peer_seeds=peer_seeds)
+    return _fused_loss(renderer, c, decoders, stage, win, w_color, sharder, out, None)
 
 
 def tracking_loss(renderer, c, decoders, c2w: torch.Tensor, depth: torch.Tensor, color: torch.Tensor, n_pixels: int,
@@ -421,14 +406,9 @@ def tracking_loss(renderer, c, decoders, c2w: torch.Tensor, depth: torch.Tensor,
     dX, pose gradient; + dW / the partial sum only if a decoder wants parameter gradients) instead of ~80.  Returns an fp64 scalar (an ordinary autograd node: an incoming gradient other than 1 scales the pose gradient)."""
     dev = torch.device(device) if device is not None else depth.device
     H0, H1, W0, W1 = int(ignore_edge_H), renderer.H - int(ignore_edge_H), int(ignore_edge_W), renderer.W - int(ignore_edge_W)
-    wmeta, c2ws = _window_meta(H0, H1, W0, W1, n_pixels, renderer.W, renderer.fx, renderer.fy, renderer.cx, renderer.cy,
-                               [c2w], [depth], [color], renderer.bound, dev, indices)
-    slots = stage_slots("color")
-    grids = _prep_grids(c, "color", dev)
-    gates = [_gate(dev, torch.is_grad_enabled() and decoders.sub(s).wants_grad() and
-                   (renderer.decoder_grads is None or s in renderer.decoder_grads)) for s in slots]
-    meta = (renderer, decoders, "color", wmeta, w_color, None, out, (bool(handle_dynamic), bool(use_color)))
-    return _MappingLossFn.apply(meta, *c2ws, *[grids[s] for s in slots], *gates)
+    win = _Window((H0, H1, W0, W1, renderer.W), n_pixels, (renderer.fx, renderer.fy, renderer.cx, renderer.cy), [c2w], [depth], [color],
+                  renderer.bound, dev, indices)
+    return _fused_loss(renderer, c, decoders, "color", win, w_color, None, out, (bool(handle_dynamic), bool(use_color)))
 
 
 _ONES = {}

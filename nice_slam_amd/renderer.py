@@ -19,12 +19,14 @@ from .layout import param_count, stage_slots
 _SLOT_IDX = {s: i for i, s in enumerate(_capi.SLOT_NAMES)}
 
 
-def _bound6(t: Optional[torch.Tensor]) -> tuple:
-    """(lo_x, lo_y, lo_z, hi_x, hi_y, hi_z) as python floats.  The conversion is cached ON the tensor object
-    (keyed by its version counter), so a CUDA-resident bound costs one host sync ever and a recycled id() /
-    data_ptr() can never alias another tensor's values."""
+def _bound6(t) -> tuple:
+    """(lo_x, lo_y, lo_z, hi_x, hi_y, hi_z) as python floats of a [3,2] bound: a tensor, a numpy array or a nested list.  For a
+    tensor the conversion is cached ON the tensor object (keyed by its version counter), so a CUDA-resident bound costs one host
+    sync ever and a recycled id() / data_ptr() can never alias another tensor's values."""
     if t is None:
         return (float("-inf"),) * 3 + (float("inf"),) * 3
+    if not isinstance(t, torch.Tensor):
+        return tuple(float(t[i][0]) for i in range(3)) + tuple(float(t[i][1]) for i in range(3))
     cached = getattr(t, "_nsr_bound6", None)
     if cached is not None and cached[0] == t._version:
         return cached[1]
@@ -71,6 +73,12 @@ def _prep_grids(c: Dict[str, torch.Tensor], stage: str, device) -> Dict[str, tor
     return out
 
 
+def _decoder_params(decoders, slots, dev):
+    """({slot: flat parameter blob}, {slot: packed operand stream}) of the stage's decoders (a changed decoder is re-packed: one launch)"""
+    lib, stream = _capi.get_lib(), _stream(dev)
+    return {s: decoders.sub(s).flat_params() for s in slots}, {s: decoders.sub(s).packed_params(lib, stream) for s in slots}
+
+
 def eval_points_raw(p: torch.Tensor, decoders, c: Dict[str, torch.Tensor], stage: str, bound: Optional[torch.Tensor]):
     """Forward-only point query: (M,3) world points -> (M,4) fp32 [r,g,b,occ]; occ := 100 outside the open
     ``bound`` box when ``bound`` is given (src/utils/Renderer.py:43-46,57)."""
@@ -80,159 +88,175 @@ def eval_points_raw(p: torch.Tensor, decoders, c: Dict[str, torch.Tensor], stage
     with torch.no_grad(), _capi.on_device(dev):
         pts = p.detach().to(torch.float64).contiguous()
         grids = _prep_grids({k: v.detach() for k, v in c.items()}, stage, dev)
-        stream = _stream(dev)
-        flats = {s: decoders.sub(s).flat_params() for s in stage_slots(stage)}
-        packed = {s: decoders.sub(s).packed_params(lib, stream) for s in stage_slots(stage)}
+        flats, packed = _decoder_params(decoders, stage_slots(stage), dev)
         a = _capi.NsrRenderArgs()
         a.n_samples, a.n_surface, a.n_rays = 1, 0, 0
         _fill_common(a, stage, bound, decoders, grids, packed, flats)
         out = torch.empty((pts.shape[0], 4), dtype=torch.float32, device=dev)
-        lib.check(lib.nsr_eval_points_fwd(C.byref(a), pts.data_ptr(), pts.shape[0], out.data_ptr(), stream), "nsr_eval_points_fwd")
+        lib.check(lib.nsr_eval_points_fwd(C.byref(a), pts.data_ptr(), pts.shape[0], out.data_ptr(), _stream(dev)), "nsr_eval_points_fwd")
     return out
 
 
 _GATES = {}
 
 
-def _gate(dev, want: bool) -> torch.Tensor:
-    """0-dim tensor whose only job is to tell _RenderFn (via needs_input_grad) whether a decoder wants parameter
-    gradients; one per (device, flag) for the life of the process instead of a fill kernel per decoder per call."""
-    key = (dev, want)
-    g = _GATES.get(key)
-    if g is None:
-        g = _GATES[key] = torch.zeros((), device=dev, requires_grad=want)
-    return g
+def _gates(renderer, decoders, slots, dev) -> list:
+    """One 0-dim 'gate' tensor per decoder of the stage whose only job is to tell the autograd node (via needs_input_grad)
+    whether that decoder wants parameter gradients; one per (device, flag) for the life of the process instead of a fill
+    kernel per decoder per call."""
+    out = []
+    for s in slots:
+        key = (dev, torch.is_grad_enabled() and decoders.sub(s).wants_grad() and
+               (renderer.decoder_grads is None or s in renderer.decoder_grads))
+        g = _GATES.get(key)
+        if g is None:
+            g = _GATES[key] = torch.zeros((), device=dev, requires_grad=key[1])
+        out.append(g)
+    return out
+
+
+class RenderCall:
+    """One render call (of ``_RenderFn``, a chunk of ``_chunked_backward`` or the fused mapping loss, mapping.py): its inputs, the
+    forward's argument block ``args`` (``forward_args``) and what the backward needs of the forward.  ``hook``: the multi-GPU
+    gradient hook (see ``render_backward``); ``hold``: further tensors the argument block points into, kept alive with it."""
+    __slots__ = ("args", "renderer", "decoders", "stage", "slots", "S", "hook", "rays_o", "rays_d", "gt_depth", "gt_max",
+                 "grids", "flats", "packed", "raw", "depth", "hold")
+
+    def __init__(self, renderer, decoders, stage, grids, rays_o, rays_d, gt_depth=None, hook=None, params=None):
+        self.renderer, self.decoders, self.stage, self.hook = renderer, decoders, stage, hook
+        self.slots = stage_slots(stage)
+        self.grids, self.rays_o, self.rays_d, self.gt_depth = grids, rays_o, rays_d, gt_depth
+        self.S = renderer.N_samples + (renderer.N_surface if (gt_depth is not None and stage != "coarse") else 0)
+        self.flats, self.packed = params if params is not None else _decoder_params(decoders, self.slots, rays_o.device)
+        self.args = self.gt_max = self.raw = self.depth = None
+        self.hold = []
+
+
+def forward_args(call: RenderCall, n_surface: int, gt_max, outs, masks_only=None):
+    """Fill ``call.args``, the forward's argument block: sample template and counts, ray and gt pointers, bound / grids / decoders
+    and the outputs ``outs`` = (depth, var, rgb, raw, zvals) (raw / zvals may be None).  ``n_surface``: the block's surface-sample
+    count; ``gt_max``: 1-element device tensor, the batch's depth cap -- given, the block reads ``call.gt_depth`` and it;
+    ``masks_only`` (differentiated forwards only; one bool per decoder, True = it wants no parameter gradients): attach an
+    activation buffer.  -> that buffer, or None (none asked for, or it does not fit)."""
+    renderer = call.renderer
+    a = call.args = _capi.NsrRenderArgs.from_buffer_copy(renderer._arg_template)     # sample fractions pre-filled
+    n = call.rays_o.shape[0]
+    a.n_samples, a.n_surface, a.n_rays = renderer.N_samples, n_surface, n
+    a.rays_o, a.rays_d = call.rays_o.data_ptr(), call.rays_d.data_ptr()
+    call.gt_max = gt_max
+    if gt_max is not None:
+        a.gt_depth, a.gt_max = call.gt_depth.data_ptr(), gt_max.data_ptr()
+    _fill_common(a, call.stage, renderer.bound, call.decoders, call.grids, call.packed, call.flats)
+    depth, var, rgb, raw, zvals = outs
+    a.depth, a.var, a.rgb = depth.data_ptr(), var.data_ptr(), rgb.data_ptr()
+    a.raw = raw.data_ptr() if raw is not None else None
+    a.zvals = zvals.data_ptr() if zvals is not None else None
+    call.raw, call.depth = raw, depth
+    return None if masks_only is None else renderer._attach_acts(a, call.stage, n, call.S, call.rays_o.device, masks_only)
 
 
 class _RenderFn(torch.autograd.Function):
-    """inputs: rays_o, rays_d, then one grid per decoder of the stage, then one 0-dim 'gate' tensor per
-    decoder (requires_grad iff that decoder's parameters do).  Parameter gradients are published straight
-    into ``Parameter.grad`` as views of one flat buffer (no per-tensor kernels)."""
+    """inputs: renderer, decoders, stage, gt_depth, gt_max (or None), reduce hook, then rays_o, rays_d, one grid per decoder of
+    the stage and one gate per decoder (``_gates``).  Parameter gradients are published straight into ``Parameter.grad`` as
+    views of one flat buffer (no per-tensor kernels)."""
 
     @staticmethod
-    def forward(ctx, meta, rays_o, rays_d, *tensors):
+    def forward(ctx, renderer, decoders, stage, gt_depth, gt_max, hook, rays_o, rays_d, *tensors):
         with _capi.on_device(rays_o.device):
-            return _RenderFn._forward_impl(ctx, meta, rays_o, rays_d, *tensors)
+            return _RenderFn._forward_impl(ctx, renderer, decoders, stage, gt_depth, gt_max, hook, rays_o, rays_d, *tensors)
 
     @staticmethod
-    def _forward_impl(ctx, meta, rays_o, rays_d, *tensors):
-        renderer, decoders, stage, gt_depth, reduce_hook = meta
+    def _forward_impl(ctx, renderer, decoders, stage, gt_depth, gt_max, hook, rays_o, rays_d, *tensors):
         lib = _capi.get_lib()
         slots = stage_slots(stage)
-        grids = dict(zip(slots, tensors[:len(slots)]))
+        call = RenderCall(renderer, decoders, stage, dict(zip(slots, tensors)), rays_o, rays_d, gt_depth, hook)
         dev = rays_o.device
-        stream = _stream(dev)
-        n = rays_o.shape[0]
-        guided = gt_depth is not None and stage != "coarse"
-        S = renderer.N_samples + (renderer.N_surface if guided else 0)
-        flats = {s: decoders.sub(s).flat_params() for s in slots}
-        packed = {s: decoders.sub(s).packed_params(lib, stream) for s in slots}
-        a = _capi.NsrRenderArgs.from_buffer_copy(renderer._arg_template)     # sample fractions pre-filled
-        a.n_samples, a.n_surface, a.n_rays = renderer.N_samples, renderer.N_surface, n
-        a.rays_o, a.rays_d = rays_o.data_ptr(), rays_d.data_ptr()
-        keep = []
-        if guided:
-            gmax = renderer._gt_max if renderer._gt_max is not None else torch.max(gt_depth).reshape(1)
-            keep.append(gmax)
-            a.gt_depth, a.gt_max = gt_depth.data_ptr(), gmax.data_ptr()
-        _fill_common(a, stage, renderer.bound, decoders, grids, packed, flats)
+        n, S = rays_o.shape[0], call.S
+        if gt_depth is None:
+            gt_max = None
+        elif gt_max is None:
+            gt_max = torch.max(gt_depth).reshape(1)
         depth = torch.empty((n,), dtype=torch.float64, device=dev)
         var = torch.empty((n,), dtype=torch.float64, device=dev)
         rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        need_bwd = any(ctx.needs_input_grad)
+        need = ctx.needs_input_grad[6:]
+        need_bwd = any(need)
         raw = torch.empty((n, S, 4), dtype=torch.float32, device=dev) if need_bwd else None
-        a.depth, a.var, a.rgb = depth.data_ptr(), var.data_ptr(), rgb.data_ptr()
-        a.raw = raw.data_ptr() if raw is not None else None
         zsave = torch.empty((n, S), dtype=torch.float64, device=dev) if need_bwd else None
-        a.zvals = zsave.data_ptr() if zsave is not None else None
-        keep.append(zsave)
-        chunk = 0
-        if need_bwd:
-            n_sl = len(slots)
-            masks_only = [not g_ for g_ in ctx.needs_input_grad[3 + n_sl:3 + 2 * n_sl]]     # per decoder: one nobody differentiates saves its relu masks only
-            acts = renderer._attach_acts(a, stage, n, S, dev, masks_only=masks_only)
-            keep.append(acts)
-            if acts is None:
-                # The activation buffer of the whole batch does not fit (Renderer.max_saved_activation_bytes / free memory / 2^25
-                # sample points): this forward runs without one and the backward goes through the batch in chunks, each chunk a
-                # forward that saves its activations followed by the split backward (_chunked_backward).
-                chunk = renderer.acts_chunk_rays(stage, S, dev)
-                a.raw = a.zvals = None
-                raw = zsave = None
-        lib.check(lib.nsr_render_fwd(C.byref(a), stream), "nsr_render_fwd")
-        ctx.chunk = chunk
+        masks_only = [not g_ for g_ in need[2 + len(slots):]] if need_bwd else None     # a decoder nobody differentiates saves its relu masks only
+        acts = forward_args(call, renderer.N_surface, gt_max, (depth, var, rgb, raw, zsave), masks_only)
+        ctx.chunk = 0
+        if need_bwd and acts is None:
+            # The activation buffer of the whole batch does not fit (Renderer.max_saved_activation_bytes / free memory / 2^25
+            # sample points): this forward runs without one and the backward goes through the batch in chunks, each chunk a
+            # forward that saves its activations followed by the split backward (_chunked_backward).
+            ctx.chunk = renderer.acts_chunk_rays(stage, S, dev)
+            call.args.raw = call.args.zvals = None
+            call.raw = zsave = None
+        lib.check(lib.nsr_render_fwd(C.byref(call.args), _stream(dev)), "nsr_render_fwd")
+        ctx.call = None
         if need_bwd:
             # `depth` is an OUTPUT: kept as a detached alias (same storage, different tensor object), so that no reference
             # cycle output -> grad_fn -> ctx -> output forms (a forward whose backward never runs is then freed normally)
-            ctx.args, ctx.keep = a, (keep, rays_o, rays_d, gt_depth, grids, flats, packed, raw, depth.detach())
-            ctx.meta = (renderer, decoders, stage, S, reduce_hook)
+            call.depth = depth.detach()
+            call.hold += [zsave, acts]
+            ctx.call = call
         return depth, var, rgb
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_depth, g_var, g_rgb):
         with _capi.on_device(g_depth.device):
-            return _RenderFn._backward_impl(ctx, g_depth, g_var, g_rgb)
-
-    @staticmethod
-    def _backward_impl(ctx, g_depth, g_var, g_rgb):
-        slots = stage_slots(ctx.meta[2])
-        need = (ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3:3 + len(slots)],
-                ctx.needs_input_grad[3 + len(slots):3 + 2 * len(slots)])
-        if ctx.keep is None:
-            raise RuntimeError("nice_slam_amd: backward through render_batch_ray a second time is not supported (the saved "
-                               "buffers are released after the first backward; render again instead of retain_graph=True)")
-        g_depth = g_depth.to(torch.float64).contiguous()
-        g_var = g_var.to(torch.float64).contiguous()
-        g_rgb = g_rgb.to(torch.float32).contiguous()
-        if ctx.chunk:
-            d_o, d_d, d_grids = _chunked_backward(ctx.args, ctx.meta, ctx.keep, need, g_depth, g_var, g_rgb, ctx.chunk)
-        else:
-            d_o, d_d, d_grids = render_backward(ctx.args, ctx.meta, ctx.keep, need, g_depth, g_var, g_rgb)
-        ctx.keep = ctx.args = None
-        return (None, d_o, d_d, *d_grids, *([None] * len(slots)))
+            call = ctx.call
+            if call is None:
+                raise RuntimeError("nice_slam_amd: backward through render_batch_ray a second time is not supported (the saved "
+                                   "buffers are released after the first backward; render again instead of retain_graph=True)")
+            ns = len(call.slots)
+            need = ctx.needs_input_grad[6:]
+            need = (need[0], need[1], need[2:2 + ns], need[2 + ns:2 + 2 * ns])
+            g_depth = g_depth.to(torch.float64).contiguous()
+            g_var = g_var.to(torch.float64).contiguous()
+            g_rgb = g_rgb.to(torch.float32).contiguous()
+            if ctx.chunk:
+                d_o, d_d, d_grids = _chunked_backward(call, need, g_depth, g_var, g_rgb, ctx.chunk)
+            else:
+                d_o, d_d, d_grids = render_backward(call, need, g_depth, g_var, g_rgb)
+            ctx.call = None
+            return (None,) * 6 + (d_o, d_d, *d_grids, *([None] * ns))
 
 
-def _chunked_backward(a, meta, kept, need, g_depth, g_var, g_rgb, chunk):
+def _chunked_backward(call: RenderCall, need, g_depth, g_var, g_rgb, chunk):
     """Backward of a batch whose activation buffer was too large to keep: per chunk of ``chunk`` rays the forward is run again
     with an activation buffer (same kernels, same batch-global depth cap) and the split backward follows; grid and decoder
     gradients accumulate over the chunks, the ray gradients are written per chunk."""
     lib = _capi.get_lib()
-    renderer, decoders, stage, S, reduce_hook = meta
-    keep, rays_o, rays_d, gt_depth, grids, flats, packed, _, _ = kept
-    if reduce_hook is not None:
+    if call.hook is not None:
         raise _capi.NsrError("nice_slam_amd: a sharded render call whose activation buffer does not fit is not supported (use smaller batches)")
-    slots = stage_slots(stage)
-    dev = rays_o.device
+    renderer, S = call.renderer, call.S
+    dev = call.rays_o.device
     stream = _stream(dev)
-    n = rays_o.shape[0]
-    need_o, need_d, need_grid, need_par = need
-    d_o = torch.zeros_like(rays_o) if (need_o or need_d) else None
-    d_d = torch.zeros_like(rays_d) if (need_o or need_d) else None
-    d_grids = [None] * len(slots)
+    n = call.rays_o.shape[0]
+    need_o, need_d, _, need_par = need
+    d_o = torch.zeros_like(call.rays_o) if (need_o or need_d) else None
+    d_d = torch.zeros_like(call.rays_d) if (need_o or need_d) else None
+    d_grids = [None] * len(call.slots)
     for i0 in range(0, n, chunk):
         i1 = min(n, i0 + chunk)
         m = i1 - i0
-        ac = _capi.NsrRenderArgs.from_buffer_copy(a)
-        ac.n_rays = m
-        ro, rd = rays_o[i0:i1].contiguous(), rays_d[i0:i1].contiguous()
-        ac.rays_o, ac.rays_d = ro.data_ptr(), rd.data_ptr()
-        gdc = None
-        if gt_depth is not None and a.gt_depth:
-            gdc = gt_depth[i0:i1].contiguous()
-            ac.gt_depth = gdc.data_ptr()
+        ro, rd = call.rays_o[i0:i1].contiguous(), call.rays_d[i0:i1].contiguous()
+        gdc = call.gt_depth[i0:i1].contiguous() if call.gt_max is not None else None
+        cc = RenderCall(renderer, call.decoders, call.stage, call.grids, ro, rd, gdc, params=(call.flats, call.packed))
         depth = torch.empty((m,), dtype=torch.float64, device=dev)
         var = torch.empty((m,), dtype=torch.float64, device=dev)
         rgb = torch.empty((m, 3), dtype=torch.float32, device=dev)
         raw = torch.empty((m, S, 4), dtype=torch.float32, device=dev)
         zs = torch.empty((m, S), dtype=torch.float64, device=dev)
-        ac.depth, ac.var, ac.rgb, ac.raw, ac.zvals = depth.data_ptr(), var.data_ptr(), rgb.data_ptr(), raw.data_ptr(), zs.data_ptr()
-        acts = renderer._attach_acts(ac, stage, m, S, dev, masks_only=[not g_ for g_ in need_par])
+        acts = forward_args(cc, renderer.N_surface, call.gt_max, (depth, var, rgb, raw, zs), [not g_ for g_ in need_par])
         if acts is None:
             raise _capi.NsrError("nice_slam_amd: no room for the activation buffer of a %d-ray chunk" % m)
-        lib.check(lib.nsr_render_fwd(C.byref(ac), stream), "nsr_render_fwd(chunk)")
-        kc = (keep + [acts, zs, gdc], ro, rd, gdc, grids, flats, packed, raw, depth)
-        co, cd, cg = render_backward(ac, meta, kc, need, g_depth[i0:i1].contiguous(), g_var[i0:i1].contiguous(), g_rgb[i0:i1].contiguous())
+        lib.check(lib.nsr_render_fwd(C.byref(cc.args), stream), "nsr_render_fwd(chunk)")
+        cc.hold += [acts, zs]
+        co, cd, cg = render_backward(cc, need, g_depth[i0:i1].contiguous(), g_var[i0:i1].contiguous(), g_rgb[i0:i1].contiguous())
         if co is not None:
             d_o[i0:i1] = co
         if cd is not None:
@@ -243,9 +267,9 @@ def _chunked_backward(a, meta, kept, need, g_depth, g_var, g_rgb, chunk):
     return (d_o if need_o else None, d_d if need_d else None, d_grids)
 
 
-def render_backward(a, meta, kept, need, g_depth, g_var, g_rgb, zero_buf=None, grad_scale=None, loss_grads_from_forward=False):
+def render_backward(call: RenderCall, need, g_depth, g_var, g_rgb, zero_buf=None, grad_scale=None, loss_grads_from_forward=False):
     """The backward launch of one render call (shared by ``_RenderFn`` and the fused mapping loss, mapping.py).
-    ``a``: the forward's argument block; ``need`` = (rays_o, rays_d, per-grid, per-decoder) gradient requests;
+    ``call``: the forward's record; ``need`` = (rays_o, rays_d, per-grid, per-decoder) gradient requests;
     ``g_*``: gradients of the outputs (contiguous, fp64 / fp64 / fp32) or None; ``zero_buf``: an already zero-filled fp32
     buffer of the size ``backward_buffer_floats`` returns (saves the fill launch); ``grad_scale``: optional 1-element fp64 device
     tensor every ``g_*`` is multiplied by inside the kernel (the incoming gradient of a fused loss node);
@@ -253,18 +277,16 @@ def render_backward(a, meta, kept, need, g_depth, g_var, g_rgb, zero_buf=None, g
     then starts from the ``d raw`` the forward's loss epilogue precomputed, nsr_bwd_args.loss_grads_from_forward).
     -> (d_rays_o, d_rays_d, [d_grid ...])."""
     lib = _capi.get_lib()
-    renderer, decoders, stage, S, reduce_hook = meta
-    keep, rays_o, rays_d, gt_depth, grids, flats, packed, raw, depth = kept
-    slots = stage_slots(stage)
-    dev = rays_o.device
+    a, renderer, decoders, stage, slots, grids = call.args, call.renderer, call.decoders, call.stage, call.slots, call.grids
+    dev = call.rays_o.device
     stream = _stream(dev)
-    n = rays_o.shape[0]
+    n = call.rays_o.shape[0]
     need_o, need_d, need_grid, need_par = need
     b = _capi.NsrBwdArgs()
     b.d_depth = g_depth.data_ptr() if g_depth is not None else None
     b.d_var = g_var.data_ptr() if g_var is not None else None
     b.d_rgb = g_rgb.data_ptr() if g_rgb is not None else None
-    b.depth = depth.data_ptr()
+    b.depth = call.depth.data_ptr()
     b.grad_scale = grad_scale.data_ptr() if grad_scale is not None else None
     b.loss_grads_from_forward = 1 if loss_grads_from_forward else 0
     # every gradient this call produces lives in ONE zero-filled buffer (a single fill kernel): channels-last views for
@@ -274,7 +296,7 @@ def render_backward(a, meta, kept, need, g_depth, g_var, g_rgb, zero_buf=None, g
     # decoder gradients: straight into each decoder's persistent blob when possible (see _FlatDecoder.grad_target);
     # the multi-GPU path and foreign .grad tensors use a temporary blob inside the fused buffer
     direct = {}
-    if reduce_hook is None:
+    if call.hook is None:
         for s, nd in zip(slots, need_par):
             if nd:
                 tgt, mode = decoders.sub(s).grad_target()
@@ -326,7 +348,7 @@ def render_backward(a, meta, kept, need, g_depth, g_var, g_rgb, zero_buf=None, g
                 poff += cnt
             else:
                 a.dec[i].dparams = None
-        nws = lib.nsr_bwd_workspace_floats(_capi.STAGE_ID[stage], n, S, renderer.bwd_max_blocks)
+        nws = lib.nsr_bwd_workspace_floats(_capi.STAGE_ID[stage], n, call.S, renderer.bwd_max_blocks)
         ws = renderer._workspace(nws, dev)
         b.workspace, b.workspace_floats = ws.data_ptr(), nws
     else:
@@ -352,7 +374,7 @@ def render_backward(a, meta, kept, need, g_depth, g_var, g_rgb, zero_buf=None, g
     # same collective as the grid rows, which autograd hands over a moment later); the `.grad` tensors are then
     # published by the hook after that exchange -- never before, or an accumulation into pre-existing `.grad`s would
     # consume rank-local values
-    deferred = reduce_hook is not None and bool(reduce_hook([g for g in d_grids if g is not None], gflat, publish))
+    deferred = call.hook is not None and bool(call.hook([g for g in d_grids if g is not None], gflat, publish))
     if not deferred:
         publish()
     return (d_o if need_o else None, d_d if need_d else None, d_grids)
@@ -464,19 +486,12 @@ class Renderer(object):
             return (torch.zeros((0,), dtype=torch.float64, device=dev) + z, torch.zeros((0,), dtype=torch.float64, device=dev) + z,
                     torch.zeros((0, 3), dtype=torch.float32, device=dev) + z)
         grids = _prep_grids(c, stage, dev)
-        gates = []
-        for s in slots:
-            want = torch.is_grad_enabled() and decoders.sub(s).wants_grad() and \
-                (self.decoder_grads is None or s in self.decoder_grads)
-            gates.append(_gate(dev, want))
-        meta = (self, decoders, stage, gt_depth, self._reduce_hook)
-        if gt_max is not None and self._gt_max is None:
-            self._gt_max = gt_max.detach().to(device=dev, dtype=torch.float32).reshape(1)
-            try:
-                return _RenderFn.apply(meta, rays_o, rays_d, *[grids[s] for s in slots], *gates)
-            finally:
-                self._gt_max = None
-        return _RenderFn.apply(meta, rays_o, rays_d, *[grids[s] for s in slots], *gates)
+        gates = _gates(self, decoders, slots, dev)
+        if self._gt_max is not None:             # the multi-GPU wrapper's batch-global max(gt_depth)
+            gt_max = self._gt_max
+        elif gt_max is not None:
+            gt_max = gt_max.detach().to(device=dev, dtype=torch.float32).reshape(1)
+        return _RenderFn.apply(self, decoders, stage, gt_depth, gt_max, self._reduce_hook, rays_o, rays_d, *[grids[s] for s in slots], *gates)
 
     def _acts_budget(self, dev) -> int:
         """bytes an activation buffer may take right now (not queried while a stream is capturing: the cap alone applies)"""
@@ -500,10 +515,11 @@ class Renderer(object):
             raise _capi.NsrError("nice_slam_amd: not enough device memory for the activation buffer of even 64 rays")
         return rays
 
-    def _attach_acts(self, a, stage, n, S, dev, masks_only=False):
+    def _attach_acts(self, a, stage, n, S, dev, masks_only):
         """allocate the activation buffer of a differentiable forward and point the argument block at it; None when it does not
         fit (budget, 2^25 sample points per call, or the allocation fails): the caller then differentiates in chunks.
-        ``masks_only``: no decoder will want parameter gradients (tracking) -- the forward then only writes the relu masks"""
+        ``masks_only``: one bool per decoder pass of the stage, in slot order -- True: that decoder will want no parameter
+        gradients, its pass only saves the relu masks (nsr_render_args.acts_masks_only)"""
         nfl = _capi.get_lib().nsr_acts_floats(_capi.STAGE_ID[stage], n, S)
         if nfl <= 0:
             raise _capi.NsrError("nsr_acts_floats: bad arguments")
@@ -516,14 +532,10 @@ class Renderer(object):
         except torch.cuda.OutOfMemoryError:
             return None
         a.acts = acts.data_ptr()
-        # masks_only: bool (every decoder) or one bool per decoder pass of the stage, in slot order (nsr_render_args.acts_masks_only)
-        if isinstance(masks_only, (list, tuple)):
-            masks_only = list(masks_only)
-            if len(masks_only) >= 2 and not masks_only[1]:
-                masks_only[0] = False               # the fine decoder's dW reads the middle pass's saved features ([c_fine | c_mid], decoder.py:182-187)
-            a.acts_masks_only = 1 if all(masks_only) else sum(2 << i for i, m in enumerate(masks_only) if m)
-        else:
-            a.acts_masks_only = 1 if masks_only else 0
+        masks_only = list(masks_only)
+        if len(masks_only) >= 2 and not masks_only[1]:
+            masks_only[0] = False                   # the fine decoder's dW reads the middle pass's saved features ([c_fine | c_mid], decoder.py:182-187)
+        a.acts_masks_only = 1 if all(masks_only) else sum(2 << i for i, m in enumerate(masks_only) if m)
         return acts
 
     def render_img(self, c, decoders, c2w, device, stage, gt_depth=None):

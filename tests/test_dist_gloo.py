@@ -181,14 +181,14 @@ def test_shard_range_partition():
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# the renderer <-> ShardedRenderer hook protocol (nice_slam_amd/renderer.py:_RenderFn.backward): decoder gradients come
+# the renderer <-> ShardedRenderer hook protocol (nice_slam_amd/renderer.py:render_backward): decoder gradients come
 # as ONE flat blob handed to `_reduce_hook(d_grids, gflat, publish)`; with voxel masks set the blob is parked and reduced
 # later together with the grid rows, and only THEN published as Parameter.grad
 # ----------------------------------------------------------------------------------------------------------------------
 class _ToyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, owner, rays_o, grid):
-        ctx.owner, ctx.hook = owner, owner._reduce_hook          # the hook is captured at forward time, like _RenderFn's meta
+        ctx.owner, ctx.hook = owner, owner._reduce_hook          # the hook is captured at forward time, like RenderCall.hook
         ctx.save_for_backward(rays_o, grid)
         s = rays_o.sum(1).double()
         return s * float(grid.sum()) + float(owner.theta.sum()), s * 0.0, rays_o * 0.0
