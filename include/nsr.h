@@ -361,6 +361,22 @@ int nsr_frustum_mask(const float *w2c, const float *cam_center, double fx, doubl
                      int32_t H, int32_t W, const float *depth, const float *xs, const float *ys, const float *zs,
                      int32_t nx, int32_t ny, int32_t nz, float *workspace, uint8_t *voxel_mask, void *stream);
 
+/* --- Overlap keyframe selection --------------------------------------------------------------------------------------------
+ * The arithmetic of Mapper.keyframe_selection_overlap (src/Mapper.py:166-228) in one launch: for each of the n_rays drawn pixel
+ * indices (flat into the [H][W] frame, device int64; the draw of get_samples, :185-186) the ray is formed as nsr_get_samples
+ * forms it (fp32 intrinsics, pose c2w: device, rows 0..2 c2w_stride floats apart); n_samples points per ray at
+ * z = near * (1 - t) + far * t, near = depth * 0.8, far = depth + 0.5 (fp32; t_vals: HOST array of n_samples floats, the
+ * reference's torch.linspace(0, 1, n_samples) on the CPU, :187-196).  Each point is projected with each keyframe's
+ * w2c = inv(est_c2w) rows 0..2 (w2c: [K][12] fp32 device; fp32 sum, x negated, fp64 K, z + 1e-5, uv rounded to fp32, :199-212)
+ * and counted when edge < u < W - edge, edge < v < H - edge and z < 0 (:213-217).  counts: [K] int32 device, fully written:
+ * counts[k] / (n_rays * n_samples) is the reference's percent_inside of keyframe k.  Deterministic; no zero fill needed.
+ * 1 <= n_samples <= 64, 1 <= n_rays <= 2^24, 0 <= 2 * edge < min(H, W) (the reference uses edge = 20); K = 0 launches nothing
+ * (w2c and counts may then be NULL). */
+int nsr_keyframe_overlap(const int64_t *indices, int32_t n_rays, int32_t n_samples, const float *t_vals,
+                         int32_t H, int32_t W, double fx, double fy, double cx, double cy, int32_t edge,
+                         const float *c2w, int32_t c2w_stride, const float *depth,
+                         const float *w2c, int32_t K, int32_t *counts, void *stream);
+
 /* --- SURVEY §8(f) rank 1 (third item): the callers' bounding-box pre-filter without compaction --------------------------
  * Mapper.optimize_map (src/Mapper.py:471-481) and Tracker.optimize_cam_in_batch (src/Tracker.py:95-104) drop, before
  * rendering, every ray whose depth lies beyond the scene bound:  t = min_axis max((lo-o)/d, (hi-o)/d)  (fp64),

@@ -5,6 +5,7 @@ path, drop-in behind the reference's Renderer / decoder / get_samples call surfa
     from nice_slam_amd import Mesher, marching_cubes
     from nice_slam_amd import recon        # eval_recon.py / cull_mesh.py: calc_3d_metric, calc_2d_metric, render_depth, cull_mesh, ...
     from nice_slam_amd import bound_from_frames, ConvexBound     # Mesher.get_bound_from_frames: TSDF fusion + convex hull
+    from nice_slam_amd import KeyframeSelector                   # Mapper.keyframe_selection_overlap
 
 No CPU / PyTorch fallback exists: every arithmetic entry point goes through libnsr.so.
 """
@@ -13,6 +14,7 @@ from .decoders import NICE, MLP, MLP_no_xyz  # noqa: F401
 from .renderer import Renderer  # noqa: F401
 from .optim import FlatAdam, MaskedGridAdam  # noqa: F401
 from .frustum import FrustumSelector  # noqa: F401
+from .keyframes import KeyframeSelector  # noqa: F401
 from .mapping import backward, get_samples_window, mapping_loss, seed_pixel_draws, tracking_loss  # noqa: F401
 from . import graphs  # noqa: F401
 from .mesher import Mesher, marching_cubes  # noqa: F401
@@ -22,7 +24,7 @@ from . import bound  # noqa: F401
 from .bound import ConvexBound, bound_from_frames, surface_points, tsdf_fuse  # noqa: F401
 
 __all__ = ["Renderer", "NICE", "MLP", "MLP_no_xyz", "get_samples", "get_rays", "grid_init", "load_bound",
-           "to_channels_last", "MaskedGridAdam", "FlatAdam", "FrustumSelector", "aabb_keep", "get_samples_window", "mapping_loss", "tracking_loss", "seed_pixel_draws", "get_camera_from_tensor", "backward",
+           "to_channels_last", "MaskedGridAdam", "FlatAdam", "FrustumSelector", "KeyframeSelector", "aabb_keep", "get_samples_window", "mapping_loss", "tracking_loss", "seed_pixel_draws", "get_camera_from_tensor", "backward",
            "Mesher", "marching_cubes",
            "recon", "nearest", "sample_surface", "align_icp", "calc_3d_metric", "cull_mesh",
            "bound", "bound_from_frames", "ConvexBound", "tsdf_fuse", "surface_points"]

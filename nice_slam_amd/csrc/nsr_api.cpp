@@ -28,6 +28,7 @@ int fail(const std::string &msg) {
 constexpr int kMaxTiles = 12;            // 12 waves = 768 threads per block
 constexpr int kDefaultBwdBlocks = 256;   // persistent-grid cap of the backward kernels: one block per CU (LDS-bound)
 constexpr int kLdsLimit = 160 * 1024;
+constexpr int kKeyframeBlocks = 256;        // keyframe selection: one block per CU, grid-stride over the keyframes
 
 // ---- launch policy: one value per choice, each the measured winner (profiles/) ----------------------------------
 // The three NSR_TEST_* hooks let the CPU emulator tests build variants that reach other shapes of the same code
@@ -594,6 +595,33 @@ int nsr_frustum_mask(const float *w2c, const float *cam_center, double fx, doubl
     NSR_LAUNCH(nsr::frustum_mask_kernel<0>, dim3((unsigned)P.nblocks), dim3(tb), tb * sizeof(float), stream, P);
     NSR_LAUNCH(nsr::frustum_mask_kernel<1>, dim3((unsigned)P.nblocks), dim3(tb), tb * sizeof(float), stream, P);
     return finish("nsr_frustum_mask");
+}
+
+int nsr_keyframe_overlap(const int64_t *indices, int32_t n_rays, int32_t n_samples, const float *t_vals,
+                         int32_t H, int32_t W, double fx, double fy, double cx, double cy, int32_t edge,
+                         const float *c2w, int32_t c2w_stride, const float *depth,
+                         const float *w2c, int32_t K, int32_t *counts, void *stream) {
+    if (!indices || !t_vals || !c2w || !depth || (K > 0 && (!w2c || !counts))) return fail("nsr_keyframe_overlap: null pointer");
+    if (K < 0) return fail("nsr_keyframe_overlap: K must be >= 0");
+    if (n_rays < 1 || n_rays > (1 << 24)) return fail("nsr_keyframe_overlap: n_rays must be in [1, 2^24]");
+    if (n_samples < 1 || n_samples > NSR_KF_MAX_SAMPLES) return fail("nsr_keyframe_overlap: n_samples must be in [1, 64]");
+    if (H <= 0 || W <= 0 || H > 32766 || W > 32766) return fail("nsr_keyframe_overlap: bad image shape");
+    if (edge < 0 || 2 * edge >= W || 2 * edge >= H) return fail("nsr_keyframe_overlap: edge must satisfy 0 <= 2 * edge < min(H, W)");
+    if (c2w_stride < 4) return fail("nsr_keyframe_overlap: c2w_stride must be >= 4");
+    if (K == 0) return 0;
+    nsr::KeyframeParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.indices = reinterpret_cast<const long long *>(indices);
+    P.c2w = c2w; P.depth = depth; P.w2c = w2c; P.counts = counts;
+    P.n_rays = n_rays; P.n_samples = n_samples; P.H = H; P.W = W; P.K = K; P.edge = edge; P.c2w_stride = c2w_stride;
+    P.fx = (float)fx; P.fy = (float)fy; P.cx = (float)cx; P.cy = (float)cy;
+    P.dfx = fx; P.dfy = fy; P.dcx = cx; P.dcy = cy;
+    for (int i = 0; i < n_samples; ++i) P.t_vals[i] = t_vals[i];
+    const int tb = NSR_KF_THREADS;
+    const int blocks = K < kKeyframeBlocks ? K : kKeyframeBlocks;
+    NSR_LAUNCH(nsr::keyframe_overlap_kernel, dim3((unsigned)blocks), dim3(tb), 3 * NSR_KF_CHUNK * sizeof(float) + (tb / 64) * sizeof(int),
+               stream, P);
+    return finish("nsr_keyframe_overlap");
 }
 
 }  // extern "C"

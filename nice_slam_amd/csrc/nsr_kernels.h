@@ -1244,6 +1244,19 @@ struct SampleParams {
     float *rays_o, *rays_d, *out_depth, *out_color;
 };
 
+// the ray through pixel (row, col) of a frame with pose c2w (rows 0..2, `stride` floats apart): get_rays_from_uv (common.py:74-88),
+// the same expressions as get_samples_kernel below (which keeps its own copy: its register allocation stays as it was)
+NSR_DEV void pixel_ray(const float *c2w, int stride, float fx, float fy, float cx, float cy, int row, int col, float o[3], float d[3]) {
+    const float dx = ((float)col - cx) / fx, dy = -(((float)row - cy) / fy), dzv = -1.f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float *R = c2w + a * stride;
+        // torch.sum(dirs * c2w[:3,:3], -1): products, then left-to-right sum (common.py:87)
+        d[a] = (dx * R[0] + dy * R[1]) + dzv * R[2];
+        o[a] = R[3];
+    }
+}
+
 NSR_KERNEL void get_samples_kernel(const SampleParams P) {
     const long long t = (long long)bid_x() * nthreads() + tid();
     if (t >= P.n) return;
@@ -1567,6 +1580,112 @@ NSR_KERNEL void frustum_mask_kernel(const FrustumParams P) {
         const float dx = R.px - P.cam_o[0], dy = R.py - P.cam_o[1], dz = R.pz - P.cam_o[2];
         const float dist = (dx * dx + dy * dy) + dz * dz;
         P.mask[vox] = (in || dist < 0.25f) ? 1 : 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// overlap keyframe selection (Mapper.keyframe_selection_overlap, Mapper.py:166-228): from the drawn pixel indices of the
+// current frame to one count per keyframe, in one launch.  Every block forms the points (n_rays rays x n_samples samples,
+// :185-196) itself and stages them in LDS -- once, when they fit in one chunk, else chunk by chunk per keyframe -- then
+// walks its keyframes (grid-stride over K): project each point with that keyframe's w2c exactly as frustum_project does
+// (:199-212), count the points inside the image less `edge` pixels in front of the camera (:213-217) per wave (ballot +
+// popcount), sum the waves in LDS, one plain store of counts[k].  No global atomics, no zero fill, same integers every run.
+// ------------------------------------------------------------------------------------------------
+#define NSR_KF_MAX_SAMPLES 64
+#define NSR_KF_CHUNK 2048          // points per LDS chunk: 3 x 2048 floats = 24 KB
+#define NSR_KF_THREADS 256
+
+struct KeyframeParams {
+    const long long *indices;      // [n_rays] flat pixel indices into the [H][W] frame (torch.randint(H*W), common.py:99)
+    const float *c2w;              // current pose, rows 0..2, c2w_stride floats apart
+    const float *depth;            // [H][W]
+    const float *w2c;              // [K][12] rows 0..2 of inv(est_c2w) per keyframe, fp32 (:200)
+    int *counts;                   // [K]
+    int n_rays, n_samples, H, W, K, edge, c2w_stride;
+    float fx, fy, cx, cy;          // the ray directions use fp32 intrinsics (get_samples)
+    double dfx, dfy, dcx, dcy;     // the projection uses the fp64 K (:205-206)
+    float t_vals[NSR_KF_MAX_SAMPLES];  // torch.linspace(0, 1, n_samples) computed on the CPU (:190)
+};
+
+// the point p of sample s on the ray through indices[r] (:185-196): near = d*0.8, far = d+0.5, z = near*(1-t) + far*t, p = o + d_ray*z
+NSR_DEV void keyframe_point(const KeyframeParams &P, int r, int s, float p[3]) {
+    long long idx = P.indices[r];
+    const long long n_pix = (long long)P.H * P.W;
+    idx = idx < 0 ? 0 : (idx >= n_pix ? n_pix - 1 : idx);     // the draw is in range; this only keeps a bad one in bounds
+    const int row = (int)(idx / P.W), col = (int)(idx % P.W);
+    float o[3], d[3];
+    pixel_ray(P.c2w, P.c2w_stride, P.fx, P.fy, P.cx, P.cy, row, col, o, d);
+    const float dep = P.depth[idx];
+    const float t = P.t_vals[s];
+    const float z = (dep * 0.8f) * (1.f - t) + (dep + 0.5f) * t;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p[a] = o[a] + d[a] * z;
+}
+
+// :201-217 for one point and one keyframe: fp32 w2c @ [p,1] (sequential sum), x *= -1, fp64 K @ cam, z + 1e-5, uv to fp32
+NSR_DEV bool keyframe_inside(const KeyframeParams &P, const float *M, float px, float py, float pz) {
+    float cam[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        cam[r] = ((M[r * 4 + 0] * px + M[r * 4 + 1] * py) + M[r * 4 + 2] * pz) + M[r * 4 + 3];
+    const double X = (double)(cam[0] * -1.f), Y = (double)cam[1], Z = (double)cam[2];
+    const double uh = (P.dfx * X + 0.0 * Y) + P.dcx * Z;
+    const double vh = (0.0 * X + P.dfy * Y) + P.dcy * Z;
+    const double zc = Z + 1e-5;
+    const float u = (float)(uh / zc), v = (float)(vh / zc);
+    const float e = (float)P.edge;
+    return (u < (float)(P.W - P.edge)) && (u > e) && (v < (float)(P.H - P.edge)) && (v > e) && (zc < 0.0);
+}
+
+// stage points [beg, beg + m) as x | y | z rows of NSR_KF_CHUNK floats
+NSR_DEV void keyframe_stage(const KeyframeParams &P, float *pts, long long beg, int m) {
+    for (int j = tid(); j < m; j += nthreads()) {
+        const long long g = beg + j;
+        float p[3];
+        keyframe_point(P, (int)(g / P.n_samples), (int)(g % P.n_samples), p);
+        pts[j] = p[0];
+        pts[NSR_KF_CHUNK + j] = p[1];
+        pts[2 * NSR_KF_CHUNK + j] = p[2];
+    }
+}
+
+NSR_KERNEL NSR_BOUNDS(NSR_KF_THREADS) void keyframe_overlap_kernel(const KeyframeParams P) {
+    float *pts = reinterpret_cast<float *>(lds_base());                   // [3][NSR_KF_CHUNK]
+    int *wave_cnt = reinterpret_cast<int *>(pts + 3 * NSR_KF_CHUNK);       // [nthreads / 64]
+    const long long n_pts = (long long)P.n_rays * P.n_samples;
+    const int n_chunks = (int)((n_pts + NSR_KF_CHUNK - 1) / NSR_KF_CHUNK);
+    if (n_chunks == 1) {
+        keyframe_stage(P, pts, 0, (int)n_pts);
+        block_sync();
+    }
+    for (int k = bid_x(); k < P.K; k += nblk_x()) {                       // block-uniform loop: every barrier is reached by all
+        float M[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) M[i] = P.w2c[(long long)k * 12 + i];
+        int cnt = 0;                                                       // wave-uniform (sum of ballot popcounts)
+        for (int c = 0; c < n_chunks; ++c) {
+            const long long beg = (long long)c * NSR_KF_CHUNK;
+            const int m = (int)(n_pts - beg < NSR_KF_CHUNK ? n_pts - beg : NSR_KF_CHUNK);
+            if (n_chunks > 1) {
+                block_sync();                                              // the previous chunk is counted by every wave
+                keyframe_stage(P, pts, beg, m);
+                block_sync();
+            }
+            for (int base = 0; base < m; base += nthreads()) {             // wave-uniform trip count: the ballot sees all 64 lanes
+                const int j = base + tid();
+                bool in = false;
+                if (j < m) in = keyframe_inside(P, M, pts[j], pts[NSR_KF_CHUNK + j], pts[2 * NSR_KF_CHUNK + j]);
+                cnt += __builtin_popcountll(ballot64(in));
+            }
+        }
+        if ((tid() & 63) == 0) wave_cnt[tid() >> 6] = cnt;
+        block_sync();
+        if (tid() == 0) {
+            int s = 0;
+            for (int w = 0; w < (nthreads() >> 6); ++w) s += wave_cnt[w];
+            P.counts[k] = s;
+        }
+        block_sync();                                                      // wave_cnt is rewritten for the next keyframe
     }
 }
 
