@@ -540,7 +540,12 @@ int nsr_hull_contains(const void *pts, int64_t n, int32_t fp64, const double *pl
  *                               nsr_depth_error_partial_doubles(K, n_pixels) doubles of device scratch
  *   nsr_view_unseen             check_proj for K candidate poses: sees [K] uint8 = 1 iff some point of pts [n][3] (fp32 / fp64)
  *                               projects into the image; w2c [K][12] fp32: rows 0..2 of inv of the FLIPPED c2w (y, z columns
- *                               negated), as nsr_cull_vertices. */
+ *                               negated), as nsr_cull_vertices.
+ *   nsr_points_visible          visibility of pts [n][3] (fp32 / fp64) from K views against their depth images (as nsr_raster_depth
+ *                               wrote them, same w2c and intrinsics): count [n] int32 += the number of views in which the point
+ *                               lies in [near, far], projects to a pixel of the image (nearest centre) and is not behind the
+ *                               depth there by more than eps (a pixel reading 0 hides nothing).  The caller zeroes count and
+ *                               calls once per batch of views on one stream.  n >= 1, K >= 1, near < far, eps >= 0. */
 int64_t nsr_raster_workspace_bytes(int64_t n_verts, int64_t n_faces, int32_t K, int32_t H, int32_t W);
 int nsr_raster_bin(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *w2c, int32_t K, int32_t H,
                    int32_t W, double fx, double fy, double cx, double cy, double near, double far, void *workspace, int64_t *n_entries,
@@ -552,6 +557,8 @@ int64_t nsr_depth_error_partial_doubles(int32_t K, int64_t n_pixels);
 int nsr_depth_error(const float *a, const float *b, int32_t K, int64_t n_pixels, double *partial, double *out, void *stream);
 int nsr_view_unseen(const void *pts, int64_t n, int32_t fp64, const float *w2c, int32_t K, int32_t H, int32_t W, double fx, double fy,
                     double cx, double cy, uint8_t *sees, void *stream);
+int nsr_points_visible(const void *pts, int64_t n, int32_t fp64, const float *w2c, int32_t K, const float *depth, int32_t H, int32_t W,
+                       double fx, double fy, double cx, double cy, double near, double far, double eps, int32_t *count, void *stream);
 
 #ifdef __cplusplus
 }

@@ -190,6 +190,9 @@ SYMBOLS = (
     ("nsr_depth_error", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("nsr_view_unseen", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                   C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    ("nsr_points_visible", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                     C.c_void_p]),
 )
 
 

@@ -1608,4 +1608,24 @@ int nsr_view_unseen(const void *pts, int64_t n, int32_t fp64, const float *w2c, 
     return finish("nsr_view_unseen");
 }
 
+int nsr_points_visible(const void *pts, int64_t n, int32_t fp64, const float *w2c, int32_t K, const float *depth, int32_t H, int32_t W,
+                       double fx, double fy, double cx, double cy, double near, double far, double eps, int32_t *count, void *stream) {
+    if (n < 1) return fail("nsr_points_visible: no points");
+    if (n > 2147483647ll) return fail("nsr_points_visible: more than 2^31 - 1 points");
+    if (K < 1) return fail("nsr_points_visible: no views");
+    if (H < 1 || W < 1) return fail("nsr_points_visible: empty image");
+    if (!(near < far)) return fail("nsr_points_visible: need near < far");
+    if (!(eps >= 0.0)) return fail("nsr_points_visible: eps must be non-negative");
+    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail("nsr_points_visible: intrinsics must be finite");
+    if (!pts || !w2c || !depth || !count) return fail("nsr_points_visible: null pointer");
+    nsr::VisParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.pts = pts; P.n = n; P.fp64 = fp64 ? 1 : 0; P.K = K; P.H = H; P.W = W; P.w2c = w2c; P.depth = depth;
+    P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.near = near; P.far = far; P.eps = eps; P.count = count;
+    const int T = nsr::kRasterThreads;
+    NSR_LAUNCH(nsr::points_visible_kernel, dim3(nblk(n, T)), dim3(T), nsr::kRasterViewChunk * 12 * 4, stream, P);
+    return finish("nsr_points_visible");
+}
+
 }  // extern "C"

@@ -436,4 +436,60 @@ NSR_KERNEL void raster_view_kernel(const ViewParams V) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Point visibility against the z-buffers of a batch of views (occlusion-aware culling, unseen-region clouds): one thread owns
+// a point, the poses travel through LDS in chunks as in cull_vertex_kernel, the thread loops over the views and finishes with
+// one plain read-modify-write of its own counter.  No atomics: counts are bit-identical run to run; successive batches of a
+// trajectory are successive launches on one stream.  Contract (tests/occlusion_reference.py restates it in numpy):
+//   Camera     the point rounded to fp32, then c_r = ((w_r0 x + w_r1 y) + w_r2 z) + w_r3 in fp32: raster_vertex_kernel's
+//              expression, so a mesh's own vertices get the numbers its z-buffer was drawn from.
+//   Range      in range iff near <= (double)c_z <= far.
+//   Pixel      fp64: u = ((double)c_x / (double)c_z) fx + cx, v = ((double)c_y / (double)c_z) fy + cy; i = floor(u + 0.5),
+//              j = floor(v + 0.5); inside iff 0 <= i < W and 0 <= j < H (a NaN is outside).
+//   Occlusion  d = depth[k][j][i]; visible iff d == 0 (nothing drawn there) or (double)c_z <= (double)d + eps.
+//   Count      count[p] += the number of the K views in which p is in range, inside and visible.
+// ------------------------------------------------------------------------------------------------
+struct VisParams {
+    const void *pts;                 // [n][3] fp32 or fp64
+    long long n;
+    int fp64, K, H, W;
+    const float *w2c;                // [K][12]
+    const float *depth;              // [K][H][W]
+    double fx, fy, cx, cy, near, far, eps;
+    int *count;                      // [n], accumulated
+};
+
+NSR_KERNEL void points_visible_kernel(const VisParams P) {
+    float *pose = reinterpret_cast<float *>(lds_base());           // [kRasterViewChunk][12]
+    const long long i = (long long)bid_x() * kRasterThreads + tid();
+    const bool live = i < P.n;
+    float px = 0.f, py = 0.f, pz = 0.f;
+    if (live) {
+        double x, y, z;
+        nn_load(P.pts, P.fp64, i, x, y, z);
+        px = (float)x; py = (float)y; pz = (float)z;
+    }
+    int c = 0;
+    for (int k0 = 0; k0 < P.K; k0 += kRasterViewChunk) {
+        const int nk = P.K - k0 < kRasterViewChunk ? P.K - k0 : kRasterViewChunk;
+        block_sync();                                               // the previous chunk is no longer read
+        for (int e = tid(); e < 12 * nk; e += kRasterThreads) pose[e] = P.w2c[12ll * k0 + e];
+        block_sync();
+        if (!live) continue;
+        for (int k = 0; k < nk; ++k) {
+            const float *w = pose + 12 * k;
+            const float cz = ((w[8] * px + w[9] * py) + w[10] * pz) + w[11];
+            const double z = (double)cz;
+            if (!(z >= P.near && z <= P.far)) continue;
+            const float xc = ((w[0] * px + w[1] * py) + w[2] * pz) + w[3];
+            const float yc = ((w[4] * px + w[5] * py) + w[6] * pz) + w[7];
+            const double u = floor((((double)xc / z) * P.fx + P.cx) + 0.5), v = floor((((double)yc / z) * P.fy + P.cy) + 0.5);
+            if (!(u >= 0.0 && u < (double)P.W && v >= 0.0 && v < (double)P.H)) continue;
+            const float d = P.depth[((long long)(k0 + k) * P.H + (long long)v) * P.W + (long long)u];
+            if (d == 0.f || z <= (double)d + P.eps) ++c;
+        }
+    }
+    if (live) P.count[i] = P.count[i] + c;
+}
+
 }  // namespace nsr

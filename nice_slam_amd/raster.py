@@ -6,11 +6,16 @@
     depth = recon.render_depth(vertices, faces, c2w)              # [K, 500, 500] fp32 device tensor, 0 = background
     recon.calc_2d_metric("rec.ply", "gt.ply")                      # {"depth_l1_cm": ..., "per_view": ...}
 
+    count = recon.visibility_counts(points, vertices, faces, c2w, 680, 1200, 600., 600., 599.5, 339.5)   # int32 [N]
+    np.save("gt_pc_unseen.npy", recon.unseen_points("gt.ply", recon.load_poses("traj.txt")))
+
     python -m nice_slam_amd.recon depth --rec_mesh R --gt_mesh G
+    python -m nice_slam_amd.recon unseen --gt_mesh G --traj traj.txt --output G_pc_unseen.npy
 
 Every per-pixel and per-point loop runs in libnsr.so (include/nsr.h, "Depth rasterization"; the rules are written out in
-csrc/nsr_raster.h): a tiled z-buffer rasterizer (nsr_raster_bin, nsr_raster_depth), the per-view depth L1 (nsr_depth_error) and
-the candidate-view test (nsr_view_unseen).  The oriented box of the camera positions is the library's fp64 convex hull plus
+csrc/nsr_raster.h): a tiled z-buffer rasterizer (nsr_raster_bin, nsr_raster_depth), the per-view depth L1 (nsr_depth_error),
+the candidate-view test (nsr_view_unseen) and the visibility of points against the z-buffers of a trajectory
+(nsr_points_visible).  The oriented box of the camera positions is the library's fp64 convex hull plus
 a minimum-area rectangle per hull-face normal on the host.
 
 Deviations from the reference (also in INTEGRATION.md):
@@ -20,7 +25,9 @@ Deviations from the reference (also in INTEGRATION.md):
     inside the bounding box, recalled from its source), far plane 20;
   * the view stream is a seeded numpy Generator (the reference draws from the unseeded ``random`` / numpy streams);
   * the oriented box orders its axes by ascending extent (trimesh's ``oriented_bounds(ordered=True)`` as recalled; trimesh
-    is not used) with each of the two shorter axes pointing to the positive side of its largest component.
+    is not used) with each of the two shorter axes pointing to the positive side of its largest component;
+  * ``visibility_counts`` and ``unseen_points`` have no counterpart in the reference: its cull is frustum-only and its unseen
+    clouds ship as files for the authors' scenes.
 """
 from __future__ import annotations
 
@@ -33,15 +40,18 @@ import torch
 from . import _capi
 from .bound import convex_hull, prefilter
 from .engine import Engine, gpu, pose_stack, w2c_rows
-from .recon import align_icp
+from .recon import align_icp, sample_surface
 
 __all__ = ["render_depth", "depth_l1", "oriented_bounds", "cam_position", "viewmatrix", "view_draws", "views_from_draws",
-           "views_unseen", "sample_views", "calc_2d_metric"]
+           "views_unseen", "sample_views", "calc_2d_metric", "raster_divisor", "scaled_camera", "visibility_counts", "unseen_points"]
 
 H_REF, W_REF, FOCAL_REF = 500, 500, 300.0          # eval_recon.py:135-142
 FAR_REF = 20.0                                     # ctr.set_constant_z_far(20)
 NEAR_REL = 0.01                                    # near = 0.01 x the mesh's largest extent
 MAX_VIEWS_PER_LAUNCH = 64
+MAX_IMAGE = 1024                                   # the rasterizer's limit per image side (kRasterMaxTiles)
+H_CULL, W_CULL, F_CULL, CX_CULL, CY_CULL = 680, 1200, 600.0, 599.5, 339.5      # cull_mesh.py's camera (Replica)
+EPS_VISIBLE = 0.03                                 # a point this far (m) behind the rendered depth still counts as seen
 
 
 def max_extent(vertices) -> float:
@@ -62,6 +72,25 @@ def _views_per_launch(E: Engine, nv: int, nf: int, H: int, W: int) -> int:
     return int(max(1, min(MAX_VIEWS_PER_LAUNCH, free // 4 // per_view)))
 
 
+def _scene(E: Engine, vertices, faces, c2w, near, what: str):
+    """(vertices fp32, faces int32, w2c [K, 12] fp32, near) on the engine's device, checked: what a batch of views is drawn from"""
+    v = E.tensor(vertices, torch.float32, what + ": vertices")
+    f = E.faces(faces)
+    c2w = pose_stack(c2w)
+    if v.shape[0] == 0 or f.shape[0] == 0:
+        raise _capi.NsrError(what + ": empty mesh")
+    if len(c2w) == 0:
+        raise _capi.NsrError(what + ": no views")
+    lo, hi = int(f.min()), int(f.max())
+    if lo < 0 or hi >= v.shape[0]:
+        raise _capi.NsrError(f"{what}: face indices out of range [0, {v.shape[0]}) (found {lo}..{hi})")
+    if near is None:
+        near = NEAR_REL * max_extent(vertices)
+    if not near > 0.0:
+        raise _capi.NsrError(f"{what}: near must be positive (got {near})")
+    return v, f, torch.from_numpy(w2c_rows(c2w, np.float64)).to(E.device), near
+
+
 def render_depth(vertices, faces, c2w, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_REF, cx=249.5, cy=249.5, near=None, far=FAR_REF,
                  engine: Optional[Engine] = None) -> torch.Tensor:
     """Depth images [K, H, W] fp32 on the engine's device of the mesh (vertices [V, 3], faces [F, 3]) seen from each c2w
@@ -69,22 +98,8 @@ def render_depth(vertices, faces, c2w, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_
     fragments outside [near, far] are discarded; near defaults to 0.01 x the mesh's largest axis-aligned extent."""
     E = engine or gpu()
     lib = E.lib
-    v = E.tensor(vertices, torch.float32, "render_depth: vertices")
-    f = E.faces(faces)
-    c2w = pose_stack(c2w)
-    K = len(c2w)
-    if v.shape[0] == 0 or f.shape[0] == 0:
-        raise _capi.NsrError("render_depth: empty mesh")
-    if K == 0:
-        raise _capi.NsrError("render_depth: no views")
-    lo, hi = int(f.min()), int(f.max())
-    if lo < 0 or hi >= v.shape[0]:
-        raise _capi.NsrError(f"render_depth: face indices out of range [0, {v.shape[0]}) (found {lo}..{hi})")
-    if near is None:
-        near = NEAR_REL * max_extent(vertices)
-    if not near > 0.0:
-        raise _capi.NsrError(f"render_depth: near must be positive (got {near})")
-    w2c = torch.from_numpy(w2c_rows(c2w, np.float64)).to(E.device)
+    v, f, w2c, near = _scene(E, vertices, faces, c2w, near, "render_depth")
+    K = len(w2c)
     out = torch.empty((K, int(H), int(W)), dtype=torch.float32, device=E.device)
     nv, nf = v.shape[0], f.shape[0]
     step = _views_per_launch(E, nv, nf, int(H), int(W))
@@ -343,3 +358,87 @@ def calc_2d_metric(rec_mesh, gt_mesh, align=True, n_imgs=1000, unseen=None, seed
     for x in per_view:                              # in view order
         total += float(x)
     return {"depth_l1_cm": total / max(len(per_view), 1) * 100, "per_view": per_view, "c2w": poses}
+
+
+# --------------------------------------------------------------------------------------------------
+# visibility of points over a trajectory: occlusion-aware culling and unseen-region clouds
+# --------------------------------------------------------------------------------------------------
+def raster_divisor(H: int, W: int) -> int:
+    """the smallest integer m with ceil(H / m) <= 1024 and ceil(W / m) <= 1024: the scale the rasterizer renders H x W at"""
+    m = 1
+    while -(-int(H) // m) > MAX_IMAGE or -(-int(W) // m) > MAX_IMAGE:
+        m += 1
+    return m
+
+
+def scaled_camera(H, W, fx, fy, cx, cy, m: int):
+    """(Hs, Ws, fx, fy, cx, cy) of the image at 1 / m scale: pixel (i, j) of it covers the m x m block at (m i, m j), so a
+    pixel centre u of the full image lies at (u + 0.5) / m - 0.5"""
+    m = int(m)
+    if m < 1:
+        raise ValueError(f"raster_div must be a positive integer (got {m})")
+    return -(-int(H) // m), -(-int(W) // m), float(fx) / m, float(fy) / m, (float(cx) + 0.5) / m - 0.5, (float(cy) + 0.5) / m - 0.5
+
+
+def visibility_counts(points, vertices, faces, c2w, H, W, fx, fy, cx, cy, eps=EPS_VISIBLE, near=None, far=1e3, raster_div=None,
+                      views_per_launch=None, engine: Optional[Engine] = None) -> torch.Tensor:
+    """int32 [N] on the engine's device: for each of ``points`` [N, 3] (fp32 / fp64) the number of the poses ``c2w`` ([K, 4, 4],
+    OpenCV convention) that see it: the point lies in [near, far], projects into the H x W image and is at most ``eps`` behind
+    the depth of the mesh (vertices, faces) at the nearest pixel centre.  The depth images are rendered a batch of views at a
+    time into one reused stack (``views_per_launch``: default what the free memory allows, at most 64) and the counts
+    accumulate over the batches, so memory is bounded by one batch whatever K is.  Images larger than the rasterizer's 1024
+    pixels a side are rendered at 1 / m scale (``raster_div``, default the smallest m that fits: 2 for 680 x 1200) with the
+    intrinsics of ``scaled_camera``.  near defaults to 0.01 x the mesh's largest axis-aligned extent."""
+    E = engine or gpu()
+    lib = E.lib
+    pts = E.tensor(points, what="visibility_counts: points")
+    v, f, w2c, near = _scene(E, vertices, faces, c2w, near, "visibility_counts")
+    K, N, nv, nf = len(w2c), pts.shape[0], v.shape[0], f.shape[0]
+    m = raster_divisor(H, W) if raster_div is None else int(raster_div)
+    Hs, Ws, fxs, fys, cxs, cys = scaled_camera(H, W, fx, fy, cx, cy, m)
+    count = torch.zeros(N, dtype=torch.int32, device=E.device)
+    if N == 0:
+        return count
+    step = min(K, int(views_per_launch) if views_per_launch is not None else _views_per_launch(E, nv, nf, Hs, Ws))
+    if step < 1:
+        raise ValueError(f"visibility_counts: views_per_launch must be positive (got {views_per_launch})")
+    nbytes = int(lib.nsr_raster_workspace_bytes(nv, nf, step, Hs, Ws))
+    if nbytes < 0:
+        raise _capi.NsrError(f"visibility_counts: unsupported sizes ({nv} vertices, {nf} faces, {Hs} x {Ws})")
+    args = (Hs, Ws, fxs, fys, cxs, cys, float(near), float(far))
+    with torch.no_grad(), E.guard():
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)          # one batch's workspace, depth stack and bins,
+        depth = torch.empty((step, Hs, Ws), dtype=torch.float32, device=E.device)   # reused by every batch
+        n_ent = torch.zeros(1, dtype=torch.int64, device=E.device)
+        bins = torch.empty(1, dtype=torch.int32, device=E.device)
+        for k0 in range(0, K, step):
+            kb = min(step, K - k0)
+            wk = w2c[k0:k0 + kb]
+            lib.check(lib.nsr_raster_bin(v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), n_ent.data_ptr(),
+                                         E.stream()), "nsr_raster_bin")
+            n = int(n_ent.item())
+            if n > bins.numel():
+                del bins
+                bins = torch.empty(n + n // 4, dtype=torch.int32, device=E.device)
+            lib.check(lib.nsr_raster_depth(v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), bins.data_ptr(), n,
+                                           depth.data_ptr(), E.stream()), "nsr_raster_depth")
+            lib.check(lib.nsr_points_visible(pts.data_ptr(), N, int(pts.dtype == torch.float64), wk.data_ptr(), kb, depth.data_ptr(),
+                                             Hs, Ws, fxs, fys, cxs, cys, float(near), float(far), float(eps), count.data_ptr(),
+                                             E.stream()), "nsr_points_visible")
+    return count
+
+
+def unseen_points(gt_mesh, c2w_list, n_points=200000, seed=0, H=H_CULL, W=W_CULL, fx=F_CULL, fy=F_CULL, cx=CX_CULL, cy=CY_CULL,
+                  eps=EPS_VISIBLE, stride=1, near=None, far=1e3, raster_div=None, views_per_launch=None,
+                  engine: Optional[Engine] = None) -> np.ndarray:
+    """fp64 [M, 3]: the points of ``n_points`` seeded surface samples of the ground-truth mesh (a PLY path or a (vertices,
+    faces) pair) that no pose of the trajectory sees, tested against the mesh's own z-buffers: the ``<gt_mesh>_pc_unseen.npy``
+    that calc_2d_metric rejects candidate views with.  ``c2w_list``: the poses as ``load_poses`` returns them (y and z axes
+    flipped), every ``stride``-th one used; the camera defaults to cull_mesh.py's."""
+    E = engine or gpu()
+    gv, gf = E.mesh(gt_mesh)
+    c2w = pose_stack(list(c2w_list)[::int(stride)], flip_yz=True)
+    pts = sample_surface(gv, gf, n_points, seed=seed, engine=E)[0]
+    count = visibility_counts(pts, gv, gf, c2w, H, W, fx, fy, cx, cy, eps=eps, near=near, far=far, raster_div=raster_div,
+                              views_per_launch=views_per_launch, engine=E)
+    return pts[count == 0].cpu().numpy()

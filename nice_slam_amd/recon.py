@@ -7,7 +7,8 @@
 
     python -m nice_slam_amd.recon eval --rec_mesh R --gt_mesh G -3d
     python -m nice_slam_amd.recon depth --rec_mesh R --gt_mesh G
-    python -m nice_slam_amd.recon cull --input_mesh M --traj traj.txt --output_mesh OUT
+    python -m nice_slam_amd.recon cull --input_mesh M --traj traj.txt --output_mesh OUT [--occlusion]
+    python -m nice_slam_amd.recon unseen --gt_mesh G --traj traj.txt --output G_pc_unseen.npy
 
 Every per-point loop runs in libnsr.so (include/nsr.h, "Reconstruction evaluation"): exact nearest neighbour over a cell grid
 (nsr_nn_*: the cKDTree queries), area-weighted surface sampling (nsr_sample_surface: trimesh.sample.sample_surface),
@@ -21,7 +22,10 @@ Deviations from the reference (also in INTEGRATION.md):
   * ICP is Open3D's point-to-point ``registration_icp`` loop restated (the same correspondences, update and stopping rule),
     not Open3D itself: the transform agrees to rounding;
   * the 2-D depth metric (``calc_2d_metric``, ``render_depth``: nice_slam_amd/raster.py) renders with this library's tiled
-    rasterizer, not Open3D's OpenGL depth buffer; its own deviations are listed in raster.py.
+    rasterizer, not Open3D's OpenGL depth buffer; its own deviations are listed in raster.py;
+  * ``cull_mesh(occlusion=True)`` (``cull --occlusion``) also drops what the mesh itself hides from every camera, a test
+    cull_mesh.py does not have; off by default.  ``unseen_points`` (``unseen``) makes the ``_pc_unseen.npy`` cloud of a ground
+    truth, which the reference ships only for its own scenes.
 """
 from __future__ import annotations
 
@@ -34,13 +38,14 @@ import numpy as np
 import torch
 
 from . import _capi
-from .engine import Engine, c_doubles, gpu, w2c_rows
+from .engine import Engine, c_doubles, gpu, pose_stack, w2c_rows
 from .engine import compact as compact_mesh
 from .ply import read_mesh, write_ply
 
 __all__ = ["nearest", "accuracy", "completion", "completion_ratio", "recon_metrics", "sample_surface", "align_icp",
            "calc_3d_metric", "cull_mesh", "load_poses", "read_mesh", "NNIndex",
-           "render_depth", "depth_l1", "cam_position", "sample_views", "calc_2d_metric"]
+           "render_depth", "depth_l1", "cam_position", "sample_views", "calc_2d_metric", "cull_masks", "visibility_counts",
+           "unseen_points"]
 
 
 # --------------------------------------------------------------------------------------------------
@@ -287,12 +292,21 @@ def _w2c_rows(c2w_list) -> np.ndarray:
     return w2c_rows(c2w_list, np.float32)
 
 
-def cull_masks(vertices, faces, c2w_list, H=680, W=1200, fx=600., fy=600., cx=599.5, cy=339.5, engine: Optional[Engine] = None):
-    """(seen bool [V], keep bool [F]): vertices some pose sees, faces with at least one seen vertex (cull_mesh.py:45-75)."""
+def cull_masks(vertices, faces, c2w_list, H=680, W=1200, fx=600., fy=600., cx=599.5, cy=339.5, engine: Optional[Engine] = None, *,
+               occlusion=False, eps=0.03, min_views=1, stride=1):
+    """(seen bool [V], keep bool [F]): vertices some pose sees, faces with at least one seen vertex (cull_mesh.py:45-75).
+    ``occlusion=True``: a vertex is seen by a pose only if it also is at most ``eps`` behind the depth of the mesh itself
+    rendered from that pose (raster.visibility_counts), and seen at all if at least ``min_views`` of every ``stride``-th pose
+    see it.  The poses are those ``load_poses`` returns (y and z axes flipped) either way."""
     E = engine or gpu()
     lib = E.lib
     v = E.tensor(vertices, what="cull_mesh: vertices")
     f = E.faces(faces)
+    if occlusion:
+        c2w = pose_stack(list(c2w_list)[::int(stride)], flip_yz=True)       # back to the rasterizer's OpenCV convention
+        count = visibility_counts(v, v, f, c2w, H, W, fx, fy, cx, cy, eps=eps, engine=E)
+        seen = count >= int(min_views)
+        return seen, seen[f.long()].any(1)
     K = len(c2w_list)
     w2c = torch.from_numpy(_w2c_rows(c2w_list)).to(E.device)
     seen = torch.empty(v.shape[0], dtype=torch.uint8, device=E.device)
@@ -305,12 +319,13 @@ def cull_masks(vertices, faces, c2w_list, H=680, W=1200, fx=600., fy=600., cx=59
 
 
 def cull_mesh(vertices, faces, c2w_list, H=680, W=1200, fx=600., fy=600., cx=599.5, cy=339.5, compact=False,
-              engine: Optional[Engine] = None):
+              engine: Optional[Engine] = None, *, occlusion=False, eps=0.03, min_views=1, stride=1):
     """(vertices, faces) with every face removed that no pose of ``c2w_list`` sees any vertex of (cull_mesh.py).  As the
     reference's ``mesh.update_faces`` the vertex array is returned unchanged; ``compact=True`` drops unreferenced vertices
-    and renumbers the faces."""
+    and renumbers the faces.  ``occlusion``, ``eps``, ``min_views``, ``stride``: as cull_masks."""
     E = engine or gpu()
-    _, keep = cull_masks(vertices, faces, c2w_list, H, W, fx, fy, cx, cy, E)
+    _, keep = cull_masks(vertices, faces, c2w_list, H, W, fx, fy, cx, cy, E, occlusion=occlusion, eps=eps, min_views=min_views,
+                         stride=stride)
     v = vertices if isinstance(vertices, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(vertices))
     v = v.to(E.device)
     f = E.faces(faces)[keep]
@@ -326,11 +341,12 @@ def _transform(E: Engine, pts: torch.Tensor, T):
 
 
 # the 2-D metric and the rasterizer live in raster.py (which imports this module's ICP)
-from .raster import calc_2d_metric, cam_position, depth_l1, render_depth, sample_views  # noqa: E402
+from .raster import (calc_2d_metric, cam_position, depth_l1, render_depth, sample_views, unseen_points,  # noqa: E402
+                     visibility_counts)
 
 
 # --------------------------------------------------------------------------------------------------
-# command line: eval_recon.py -3d / calc_2d_metric and cull_mesh.py
+# command line: eval_recon.py -3d / calc_2d_metric, cull_mesh.py and the unseen cloud of a ground truth
 # --------------------------------------------------------------------------------------------------
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m nice_slam_amd.recon", description="Reconstruction evaluation on the GPU.")
@@ -354,6 +370,16 @@ def main(argv=None):
     cu.add_argument("--input_mesh", type=str, help="path to the mesh to be culled")
     cu.add_argument("--traj", type=str, help="path to the trajectory")
     cu.add_argument("--output_mesh", type=str, help="path to the output mesh")
+    cu.add_argument("--occlusion", action="store_true", help="also drop what the mesh itself hides from every camera")
+    cu.add_argument("--eps", type=float, default=0.03, help="with --occlusion: depth a vertex may lie behind the rendered surface (m)")
+    cu.add_argument("--min_views", type=int, default=1, help="with --occlusion: cameras that must see a vertex")
+    cu.add_argument("--stride", type=int, default=1, help="with --occlusion: use every stride-th pose")
+    us = sub.add_parser("unseen", help="the ground-truth surface points no camera of a trajectory sees (<gt_mesh>_pc_unseen.npy)")
+    us.add_argument("--gt_mesh", type=str, required=True, help="ground truth mesh file path")
+    us.add_argument("--traj", type=str, required=True, help="path to the trajectory")
+    us.add_argument("--output", type=str, required=True, help="path to the output point cloud (.npy)")
+    us.add_argument("--n_points", type=int, default=200000, help="number of surface samples tested")
+    us.add_argument("--seed", type=int, default=0, help="seed of the surface sampler")
     args = ap.parse_args(argv)
     if args.cmd == "eval":
         if args.metric_2d:
@@ -368,10 +394,14 @@ def main(argv=None):
         unseen = False if args.no_unseen else args.unseen
         m = calc_2d_metric(args.rec_mesh, args.gt_mesh, align=not args.no_align, n_imgs=args.n_imgs, unseen=unseen, seed=args.seed)
         print("Depth L1: ", m["depth_l1_cm"])
+    elif args.cmd == "unseen":
+        pts = unseen_points(args.gt_mesh, load_poses(args.traj), n_points=args.n_points, seed=args.seed)
+        np.save(args.output, pts)
+        print("unseen points: ", len(pts), "of", args.n_points)
     else:
         v, f = read_mesh(args.input_mesh)
         poses = load_poses(args.traj)
-        _, keep = cull_masks(v, f, poses)
+        _, keep = cull_masks(v, f, poses, occlusion=args.occlusion, eps=args.eps, min_views=args.min_views, stride=args.stride)
         write_ply(args.output_mesh, v, f[keep.cpu().numpy()])
     return 0
 
