@@ -23,6 +23,9 @@ SCENES = {
     "apartment": ([[-5.8, 11.3], [-4.0, 4.5], [-7.9, 4.9]], GRID_LEN, (720, 1280, 607.4694213867188, 607.4534912109375, 636.9967041015625, 369.2689514160156)),
     # BASELINE configs[4]: synthetic stress, 1024x1024, bound +-5.12 -> fine/color 64^3, middle 32^3
     "synthetic": ([[-5.12, 5.11], [-5.12, 5.11], [-5.12, 5.11]], GRID_LEN, (1024, 1024, 512.0, 512.0, 511.5, 511.5)),
+    # a dense coarse level over a small, cheap scene: 16 x 16 x 12 = 3072 coarse voxels (the coarse stage's gradient grid then cannot sit
+    # in a dX block's LDS: 160 KB / 128 B per voxel = 1280), the other levels coarsened to 10 x 10 x 8 and 5 x 5 x 4
+    "coarse_dense": ([[-1.6, 1.5], [-1.6, 1.5], [-1.2, 1.3]], dict(coarse=0.4, middle=0.64, fine=0.32, color=0.32), (48, 64, 60.0, 60.0, 31.5, 23.5)),
 }
 
 
@@ -68,7 +71,7 @@ def _loss(depth, var, rgb, w):
         (rgb * w["rgb"].to(rgb.device)).sum()
 
 
-def oracle_render(sc, stage, backward=False, with_depth=True, rays=None, lo=torch.float32):
+def oracle_render(sc, stage, backward=False, with_depth=True, rays=None, lo=torch.float32, n_samples=32, n_surface=16):
     """Reference result on the CPU: dict of outputs (+ every gradient the reference's autograd produces).
     ``lo=torch.float64`` evaluates decoder + compositor in double on the SAME sample positions: the "truth" used to
     measure the fp32 noise floor of the reference path itself."""
@@ -78,7 +81,7 @@ def oracle_render(sc, stage, backward=False, with_depth=True, rays=None, lo=torc
     o = sc["rays_o"][sl].clone().requires_grad_(backward)
     d = sc["rays_d"][sl].clone().requires_grad_(backward)
     gd = sc["gt_depth"][sl] if with_depth else None
-    depth, var, rgb = orc.render_batch_ray(grids, params, d, o, stage, gd, sc["bound"], lo=lo)
+    depth, var, rgb = orc.render_batch_ray(grids, params, d, o, stage, gd, sc["bound"], n_samples=n_samples, n_surface=n_surface, lo=lo)
     out = {"depth": depth.detach(), "var": var.detach(), "rgb": rgb.detach()}
     if backward:
         w = {k: v[sl].to(lo if v.dtype == torch.float32 else v.dtype) for k, v in sc["w"].items()}
@@ -191,7 +194,7 @@ def secondary_ceiling(tag):
 SELF_DISAGREEMENT = {}      # tag -> {tensor: rel. distance between two legitimate fp32 evaluations of the REFERENCE's own operators}
 
 
-def reference_self_disagreement(sc, stage, backward=True, with_depth=True, rays=None):
+def reference_self_disagreement(sc, stage, backward=True, with_depth=True, rays=None, **samples):
     """The reference path against ITSELF in fp32: the oracle's index-arithmetic trilinear with one thread vs the same graph
     through ATen's grid_sampler_3d (decoder.py:173, what the reference calls) with every host thread -- two evaluations a user
     of the reference gets on two machines.  -> {tensor: max|a-b| / max|b|}."""
@@ -200,17 +203,18 @@ def reference_self_disagreement(sc, stage, backward=True, with_depth=True, rays=
     try:
         torch.set_num_threads(1)
         orc.TRILINEAR_IMPL = "index"
-        a = oracle_render(sc, stage, backward=backward, with_depth=with_depth, rays=rays)
+        a = oracle_render(sc, stage, backward=backward, with_depth=with_depth, rays=rays, **samples)
         torch.set_num_threads(max(nthr, min(16, os.cpu_count() or 1)))
         orc.TRILINEAR_IMPL = "grid_sample"
-        b = oracle_render(sc, stage, backward=backward, with_depth=with_depth, rays=rays)
+        b = oracle_render(sc, stage, backward=backward, with_depth=with_depth, rays=rays, **samples)
     finally:
         torch.set_num_threads(nthr)
         orc.TRILINEAR_IMPL = impl
     return {k: rel_err(a[k], b[k]) for k in b}
 
 
-def parity_failures(got, sc, stage, tol=1e-4, backward=True, with_depth=True, rays=None, ref=None, truth_fn=None, tag=None):
+def parity_failures(got, sc, stage, tol=1e-4, backward=True, with_depth=True, rays=None, ref=None, truth_fn=None, tag=None,
+                    n_samples=32, n_surface=16):
     """Keys of ``got`` that are NOT at parity with the reference path.
 
     Primary gate, every tensor: max|a-b| / max|b| <= tol against the fp32 oracle (BASELINE.json north_star).
@@ -232,13 +236,15 @@ def parity_failures(got, sc, stage, tol=1e-4, backward=True, with_depth=True, ra
     noisier than 2x the reference itself.  Where the reference is accurate and stable (noise << tol) this reduces to the
     primary gate.  The forward outputs (depth, var, rgb) never take the secondary gate.  Every tensor that does is recorded in
     SECONDARY_LOG (tests/conftest.py writes the list out and prints it), and with a `tag` it must be on the committed list of
-    that test case (``secondary_allowed``) unless NSR_PARITY_COLLECT=1."""
-    ref = ref or oracle_render(sc, stage, backward=backward, with_depth=with_depth, rays=rays)
+    that test case (``secondary_allowed``) unless NSR_PARITY_COLLECT=1.  ``n_samples`` / ``n_surface``: the sample counts of every
+    oracle evaluation made here."""
+    samples = dict(n_samples=n_samples, n_surface=n_surface)
+    ref = ref or oracle_render(sc, stage, backward=backward, with_depth=with_depth, rays=rays, **samples)
     bad = [k for k in ref if rel_err(got[k], ref[k]) >= tol]
     if not bad:
         return []
     truth = truth_fn() if truth_fn is not None else \
-        oracle_render(sc, stage, backward=backward, with_depth=with_depth, rays=rays, lo=torch.float64)
+        oracle_render(sc, stage, backward=backward, with_depth=with_depth, rays=rays, lo=torch.float64, **samples)
     out, pert = [], None
     for k in bad:
         if k in PRIMARY_ONLY:
@@ -249,7 +255,7 @@ def parity_failures(got, sc, stage, tol=1e-4, backward=True, with_depth=True, ra
         if e_truth > max(2.0 * e_ref, tol) and truth_fn is None:
             if pert is None:                                    # ... and its sensitivity to a one-ulp change of the inputs
                 n_pert = 3 if sc["rays_o"].shape[0] <= 1000 else 1          # (three draws where the oracle is cheap)
-                pert = [oracle_render(ulp_perturbed(sc, 1234 + i), stage, backward=backward, with_depth=with_depth, rays=rays)
+                pert = [oracle_render(ulp_perturbed(sc, 1234 + i), stage, backward=backward, with_depth=with_depth, rays=rays, **samples)
                         for i in range(n_pert)]
             e_ref = max([e_ref] + [rel_err(p_[k], truth[k]) for p_ in pert])
         if e_truth > max(2.0 * e_ref, tol) or e_truth >= 3e-2:
@@ -270,17 +276,17 @@ def parity_failures(got, sc, stage, tol=1e-4, backward=True, with_depth=True, ra
             out.append((tag, "%d tensors took the secondary gate, the committed budget of this case is %d" % (len(took), secondary_ceiling(tag))))
         if took and tag not in SELF_DISAGREEMENT and truth_fn is None and sc["rays_o"].shape[0] <= 5000:
             # what the same tensors do between two fp32 evaluations of the reference itself (recorded in parity_report.json)
-            sd = reference_self_disagreement(sc, stage, backward=backward, with_depth=with_depth, rays=rays)
+            sd = reference_self_disagreement(sc, stage, backward=backward, with_depth=with_depth, rays=rays, **samples)
             SELF_DISAGREEMENT[tag] = {e[1]: sd.get(e[1]) for e in took}
     return out
 
 
-def build_product(sc, device):
+def build_product(sc, device, n_samples=32, n_surface=16):
     """Product-side objects (nice_slam_amd.Renderer / NICE / channels-last grids) for a scene."""
     import types
     import nice_slam_amd as nsa
     from nice_slam_amd.common import set_decoder_bounds
-    cfg = {"rendering": {"lindisp": False, "perturb": 0.0, "N_samples": 32, "N_surface": 16, "N_importance": 0},
+    cfg = {"rendering": {"lindisp": False, "perturb": 0.0, "N_samples": n_samples, "N_surface": n_surface, "N_importance": 0},
            "scale": 1, "occupancy": True}
     H, W, fx, fy, cx, cy = sc["intr"]
     slam = types.SimpleNamespace(nice=True, bound=sc["bound"], H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy)
@@ -293,28 +299,54 @@ def build_product(sc, device):
     return renderer, dec, grids
 
 
-def hip_render(sc, stage, device="cuda:0", backward=False, with_depth=True, rays=None, product=None):
+def hip_render(sc, stage, device="cuda:0", backward=False, with_depth=True, rays=None, product=None, want=("grids", "params", "rays"),
+               twice=False):
+    """``want``: which of the three input groups require grad in a differentiated call; the result holds only their gradients.
+    ``twice``: run the backward a second time over the SAME saved forward -> (first result, second result).  The render node drops
+    its record of the forward with its first backward (renderer.py::_RenderFn); the record is handed back to it in between, so both
+    backward launches read the same activation buffer, ``raw`` and sample depths."""
     renderer, dec, grids = product or build_product(sc, device)
-    grids = {k: v.detach().clone(memory_format=torch.preserve_format).requires_grad_(backward) for k, v in grids.items()}
+    assert set(want) <= {"grids", "params", "rays"}, want
+    g_grid, g_par, g_ray = (backward and k in want for k in ("grids", "params", "rays"))
+    grids = {k: v.detach().clone(memory_format=torch.preserve_format).requires_grad_(g_grid) for k, v in grids.items()}
     for p in dec.parameters():
         p.grad = None
-        p.requires_grad_(backward)
+        p.requires_grad_(g_par)
     sl = slice(None) if rays is None else rays
-    o = sc["rays_o"][sl].to(device).requires_grad_(backward)
-    d = sc["rays_d"][sl].to(device).requires_grad_(backward)
+    o = sc["rays_o"][sl].to(device).requires_grad_(g_ray)
+    d = sc["rays_d"][sl].to(device).requires_grad_(g_ray)
     gd = sc["gt_depth"][sl].to(device) if with_depth else None
     depth, var, rgb = renderer.render_batch_ray(grids, dec, d, o, device, stage, gt_depth=gd)
     out = {"depth": depth.detach(), "var": var.detach(), "rgb": rgb.detach()}
-    if backward:
-        w = {k: v[sl] for k, v in sc["w"].items()}
-        _loss(depth, var, rgb, w).backward()
-        out["d_rays_o"], out["d_rays_d"] = o.grad, d.grad
+
+    def gradients(res):
+        if g_ray:
+            res["d_rays_o"], res["d_rays_d"] = o.grad, d.grad
         for k, v in grids.items():
             if v.grad is not None:
-                out["d_" + k] = v.grad
+                res["d_" + k] = v.grad
         for k, p in dec.named_parameters():
             if p.grad is not None:
-                out["dparam/" + k] = p.grad.clone()       # .grad is a view of the decoder's persistent gradient blob
+                res["dparam/" + k] = p.grad.clone()       # .grad is a view of the decoder's persistent gradient blob
+        return res
+
+    if backward:
+        w = {k: v[sl] for k, v in sc["w"].items()}
+        loss = _loss(depth, var, rgb, w)
+        node = depth.grad_fn
+        call = node.call if twice else None
+        loss.backward(retain_graph=twice)
+        gradients(out)
+        if twice:
+            torch.cuda.synchronize()
+            for t in [o, d] + list(grids.values()) + list(dec.parameters()):
+                t.grad = None
+            assert node.call is None and call is not None
+            node.call = call
+            loss.backward()
+            second = gradients({k: out[k] for k in PRIMARY_ONLY})
+            torch.cuda.synchronize()
+            return out, second
     torch.cuda.synchronize()
     return out
 
