@@ -560,6 +560,27 @@ int nsr_view_unseen(const void *pts, int64_t n, int32_t fp64, const float *w2c, 
 int nsr_points_visible(const void *pts, int64_t n, int32_t fp64, const float *w2c, int32_t K, const float *depth, int32_t H, int32_t W,
                        double fx, double fy, double cx, double cy, double near, double far, double eps, int32_t *count, void *stream);
 
+/* --- Rendering evaluation (src/utils/Visualizer.py:53-65, with PSNR / SSIM / depth L1 of the re-rendered frames) ------------
+ * One launch pair evaluates B frame pairs; the numerical contract is written out in nice_slam_amd/csrc/nsr_imgmetrics.h.
+ * color / gt_color [B][H][W][3] fp32 (rendered / input), depth / gt_depth [B][H][W] fp32; a pixel is valid iff its input depth
+ * is not 0.  H, W >= 11 (one 11 x 11 SSIM window), B <= 65535; B = 0 succeeds and launches nothing.
+ *   nsr_image_metrics_workspace_bytes  device workspace of the call (-1: invalid sizes)
+ *   nsr_image_metrics                  result [B][8] fp64 per frame:
+ *                                        [0] sum over pixels and channels of (clip(color) - clip(gt_color))^2, clip to [0, 1]
+ *                                        [1] the number of pixels H W        (PSNR = -10 log10([0] / (3 [1])), data range 1)
+ *                                        [2], [3] the same sum and count over the valid pixels
+ *                                        [4] SSIM (Gaussian 11 x 11, sigma 1.5, windows inside the image, mean over windows and
+ *                                            channels, clipped colours, not masked)
+ *                                        [5] sum of |gt_depth - depth| over the valid pixels (count: [3]; metric 100 [5] / [3] cm)
+ *                                        [6] the maximum of gt_depth        [7] 0
+ *                                      depth_residual [B][H][W], color_residual [B][H][W][3] (either may be null): |gt - rendered|
+ *                                      of the depth and of the unclipped colour, 0 where the pixel is not valid.
+ *                                      Fixed-order fp64 sums, no atomics: bit-identical run to run and independent of a
+ *                                      frame's place in the batch. */
+int64_t nsr_image_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int nsr_image_metrics(const float *color, const float *gt_color, const float *depth, const float *gt_depth, int32_t B, int32_t H, int32_t W,
+                      double *result, float *depth_residual, float *color_residual, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

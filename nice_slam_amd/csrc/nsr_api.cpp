@@ -15,6 +15,7 @@
 #include "../../nice_slam_amd/csrc/nsr_recon.h"
 #include "../../nice_slam_amd/csrc/nsr_bound.h"
 #include "../../nice_slam_amd/csrc/nsr_raster.h"
+#include "../../nice_slam_amd/csrc/nsr_imgmetrics.h"
 
 namespace {
 
@@ -1626,6 +1627,59 @@ int nsr_points_visible(const void *pts, int64_t n, int32_t fp64, const float *w2
     const int T = nsr::kRasterThreads;
     NSR_LAUNCH(nsr::points_visible_kernel, dim3(nblk(n, T)), dim3(T), nsr::kRasterViewChunk * 12 * 4, stream, P);
     return finish("nsr_points_visible");
+}
+
+}  // extern "C"
+
+// ---- rendering evaluation (include/nsr.h, "Rendering evaluation") ----
+namespace {
+
+// tiles of window positions per row and per column; false: sizes the kernel does not take
+bool imgmetrics_tiles(int32_t B, int32_t H, int32_t W, int &tx, int &ty) {
+    if (B < 0 || B > 65535 || H < nsr::kImWin || W < nsr::kImWin || H > 32768 || W > 32768) return false;
+    tx = (W - (nsr::kImWin - 1) + nsr::kImTile - 1) / nsr::kImTile;
+    ty = (H - (nsr::kImWin - 1) + nsr::kImTile - 1) / nsr::kImTile;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nsr_image_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+    int tx = 0, ty = 0;
+    if (!imgmetrics_tiles(B, H, W, tx, ty)) return -1;
+    return 8ll * nsr::kImPartials * B * tx * ty;
+}
+
+int nsr_image_metrics(const float *color, const float *gt_color, const float *depth, const float *gt_depth, int32_t B, int32_t H, int32_t W,
+                      double *result, float *depth_residual, float *color_residual, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (B < 0) return fail("nsr_image_metrics: negative batch size");
+    if (H < nsr::kImWin || W < nsr::kImWin) return fail("nsr_image_metrics: images must be at least 11 x 11 (one SSIM window)");
+    nsr::ImgMetricsParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (!imgmetrics_tiles(B, H, W, P.tx, P.ty)) return fail("nsr_image_metrics: at most 65535 frames of at most 32768 x 32768");
+    if (B == 0) return 0;
+    if (!color || !gt_color || !depth || !gt_depth || !result || !workspace) return fail("nsr_image_metrics: null pointer");
+    P.ntiles = P.tx * P.ty;
+    if (workspace_bytes < 8ll * nsr::kImPartials * B * P.ntiles)
+        return fail("nsr_image_metrics: workspace too small (nsr_image_metrics_workspace_bytes)");
+    P.color = color; P.gt_color = gt_color; P.depth = depth; P.gt_depth = gt_depth;
+    P.B = B; P.H = H; P.W = W;
+    P.partial = static_cast<double *>(workspace); P.out = result;
+    P.depth_res = depth_residual; P.color_res = color_residual;
+    double g[nsr::kImWin], sum = 0.0;
+    for (int i = 0; i < nsr::kImWin; ++i) {
+        const double d = i - nsr::kImWin / 2;
+        g[i] = std::exp(-(d * d) / (2.0 * 1.5 * 1.5));
+        sum += g[i];
+    }
+    for (int i = 0; i < nsr::kImWin; ++i) P.g[i] = (float)(g[i] / sum);
+    if (int rc = launch_cfg(nsr::imgmetrics_tile_kernel, nsr::kImLds, "nsr_image_metrics")) return rc;
+    const int T = nsr::kImThreads;
+    NSR_LAUNCH(nsr::imgmetrics_tile_kernel, dim3(P.ntiles, B), dim3(T), nsr::kImLds, stream, P);
+    NSR_LAUNCH(nsr::imgmetrics_final_kernel, dim3(B), dim3(T), nsr::kImFinalLds, stream, P);
+    return finish("nsr_image_metrics");
 }
 
 }  // extern "C"

@@ -1,0 +1,188 @@
+"""Rendering evaluation on the GPU: how well the learned scene re-renders the frames it was built from -- PSNR, SSIM and the
+rendered-depth L1 against the input frames, with the residual maps of the reference's ``Visualizer.vis``
+(src/utils/Visualizer.py:53-65: ``|gt - rendered|`` of depth and colour, zeroed where the input depth is 0).
+
+    from nice_slam_amd import imgeval
+    m = imgeval.image_metrics(color, gt_color, depth, gt_depth)            # {"psnr", "psnr_valid", "ssim", "depth_l1_cm", ...}
+    r = imgeval.evaluate_rendering(renderer, c, decoders, frames)          # {"frames": [...], "mean": {...}, ...}
+
+    python -m nice_slam_amd.imgeval RENDERED.npz GT.npz                    # each file: arrays ``color`` and ``depth``
+
+Every per-pixel and per-window loop runs in libnsr.so (include/nsr.h, "Rendering evaluation"; the definitions are written out
+in csrc/nsr_imgmetrics.h): one launch evaluates a whole batch of frame pairs.
+
+  * PSNR: ``-10 log10(mean((clip(a, 0, 1) - clip(b, 0, 1))^2))``, data range 1, over all pixels (``psnr``) and over the pixels
+    with an input depth (``psnr_valid``); the clip is the Visualizer's (:85-87).
+  * SSIM: Wang et al. 2004 in the convention of ``pytorch_msssim.ssim(X, Y, data_range=1)``: clipped colours, a normalised
+    11 x 11 Gaussian (sigma 1.5), windows wholly inside the image, biased moments, C1 = 0.01^2, C2 = 0.03^2, the mean over
+    windows and channels; not masked by depth.
+  * Depth L1: ``100 mean |gt - rendered|`` (cm) over the pixels whose input depth is not 0; NaN for a frame without one.
+
+Not here: the matplotlib figure of the Visualizer, and LPIPS (it needs trained network weights).
+"""
+from __future__ import annotations
+
+import argparse
+import math
+import sys
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _capi
+from .common import get_camera_from_tensor
+from .engine import Engine, gpu
+
+__all__ = ["image_metrics", "evaluate_rendering", "RESULT_DOUBLES"]
+
+RESULT_DOUBLES = 8               # per frame, include/nsr.h
+MIN_SIDE = 11                    # one SSIM window
+MAX_FRAMES_PER_LAUNCH = 65535
+
+
+def _images(E: Engine, x, channels: bool, what: str) -> torch.Tensor:
+    """[B, H, W(, 3)] contiguous fp32 on the engine's device of one image or a batch (tensor or array, any device, fp32 / fp64)"""
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x))
+    t = t.detach()
+    nd = 3 if channels else 2
+    if t.dim() == nd:
+        t = t[None]
+    if t.dim() != nd + 1 or (channels and t.shape[-1] != 3):
+        raise ValueError(f"image_metrics: {what} must be [H, W{', 3' if channels else ''}] or a batch of them (got {tuple(t.shape)})")
+    return t.to(E.device, torch.float32).contiguous()
+
+
+def image_metrics(color, gt_color, depth, gt_depth, residuals: bool = False, engine: Optional[Engine] = None) -> dict:
+    """Metrics of rendered images against the input frames, one frame (``color`` [H, W, 3], ``depth`` [H, W]) or a batch
+    ([B, H, W, 3] / [B, H, W]); tensors or arrays of any device, fp32 or fp64 (evaluated as fp32).  Returns per-frame tensors
+    on the engine's device ([B], or 0-dim for one frame): ``psnr``, ``psnr_valid``, ``ssim``, ``depth_l1_cm`` (fp64),
+    ``n_valid`` (int64: pixels whose input depth is not 0), ``depth_max`` (fp32: the largest input depth, the Visualizer's
+    ``vmax``) and the raw fp64 sums behind them, ``sq_err`` / ``sq_err_valid`` (squared colour error over all / the valid
+    pixels, three channels) and ``depth_abs_err`` (m, over the valid pixels); with ``residuals`` also ``depth_residual``
+    [B, H, W] and ``color_residual`` [B, H, W, 3] (fp32).  The sums are taken in a fixed order: the same input gives the same
+    bits, whatever else is in the batch."""
+    E = engine or gpu()
+    lib = E.lib
+    single = (color.ndim if hasattr(color, "ndim") else np.asarray(color).ndim) == 3
+    a, b = _images(E, color, True, "color"), _images(E, gt_color, True, "gt_color")
+    d, g = _images(E, depth, False, "depth"), _images(E, gt_depth, False, "gt_depth")
+    if a.shape != b.shape or d.shape != g.shape or a.shape[:3] != d.shape:
+        raise ValueError(f"image_metrics: shapes differ (color {tuple(a.shape)}, gt_color {tuple(b.shape)}, depth {tuple(d.shape)}, "
+                         f"gt_depth {tuple(g.shape)})")
+    B, H, W = d.shape
+    if H < MIN_SIDE or W < MIN_SIDE:
+        raise _capi.NsrError(f"image_metrics: images must be at least {MIN_SIDE} x {MIN_SIDE} (got {H} x {W})")
+    res = torch.zeros((B, RESULT_DOUBLES), dtype=torch.float64, device=E.device)
+    dres = torch.empty((B, H, W), dtype=torch.float32, device=E.device) if residuals else None
+    cres = torch.empty((B, H, W, 3), dtype=torch.float32, device=E.device) if residuals else None
+    with torch.no_grad(), E.guard():
+        for k0 in range(0, B, MAX_FRAMES_PER_LAUNCH):
+            kb = min(MAX_FRAMES_PER_LAUNCH, B - k0)
+            nbytes = int(lib.nsr_image_metrics_workspace_bytes(kb, H, W))
+            if nbytes < 0:
+                raise _capi.NsrError(f"image_metrics: unsupported sizes ({kb} frames of {H} x {W})")
+            ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=E.device)
+            sl = slice(k0, k0 + kb)
+            lib.check(lib.nsr_image_metrics(a[sl].data_ptr(), b[sl].data_ptr(), d[sl].data_ptr(), g[sl].data_ptr(), kb, H, W,
+                                            res[sl].data_ptr(), dres[sl].data_ptr() if residuals else None,
+                                            cres[sl].data_ptr() if residuals else None, ws.data_ptr(), nbytes, E.stream()),
+                      "nsr_image_metrics")
+    se_all, n_all, se_valid, n_valid, ssim, l1, dmax = (res[:, i] for i in range(7))
+    out = {"psnr": -10.0 * torch.log10(se_all / (3.0 * n_all)),
+           "psnr_valid": -10.0 * torch.log10(se_valid / (3.0 * n_valid)),        # 0 / 0: NaN for a frame without valid depth
+           "ssim": ssim.clone(),
+           "depth_l1_cm": 100.0 * l1 / n_valid,
+           "n_valid": n_valid.to(torch.int64),
+           "depth_max": dmax.to(torch.float32),
+           "sq_err": se_all.clone(), "sq_err_valid": se_valid.clone(), "depth_abs_err": l1.clone()}
+    if residuals:
+        out["depth_residual"], out["color_residual"] = dres, cres
+    if single:
+        out = {k: v[0] for k, v in out.items()}
+    return out
+
+
+METRICS = ("psnr", "psnr_valid", "ssim", "depth_l1_cm")
+
+
+def _means(rows) -> dict:
+    """the mean of each metric over the frames where it is a number (a frame without valid depth has no depth L1 and no
+    psnr_valid), summed in frame order"""
+    out = {}
+    for k in METRICS:
+        vals = [r[k] for r in rows if not math.isnan(r[k])]
+        out[k] = math.fsum(vals) / len(vals) if vals else float("nan")
+    return out
+
+
+def evaluate_rendering(renderer, c, decoders, frames, stage: str = "color", device="cuda:0", batch: int = 8, residuals: bool = False,
+                       engine: Optional[Engine] = None) -> dict:
+    """Re-render frames and measure them: ``frames`` is an iterable of ``(idx, gt_color [H, W, 3], gt_depth [H, W],
+    c2w_or_camera_tensor)``; a 7-float camera tensor (quaternion, translation) goes through ``get_camera_from_tensor`` as in
+    Visualizer.py:43-51.  Each frame is rendered with ``renderer.render_img(c, decoders, c2w, device, stage, gt_depth=gt_depth)``
+    and ``batch`` frames at a time are evaluated by one launch.  Returns
+
+        {"frames": [{"idx", "psnr", "psnr_valid", "ssim", "depth_l1_cm", "n_valid", "depth_max"}, ...],     # floats, frame order
+         "mean": {"psnr", "psnr_valid", "ssim", "depth_l1_cm"},      # each over the frames where it is a number
+         "n_frames": int, "n_no_depth": int}                          # frames without any valid depth: not in the depth mean
+
+    With ``residuals`` every frame's row also holds the rendered ``depth`` and ``color`` and the two residual maps (fp32, on
+    the engine's device)."""
+    E = engine or gpu()
+    batch = max(1, int(batch))
+    rows, pending = [], []
+
+    def flush():
+        if not pending:
+            return
+        m = image_metrics(torch.stack([p[1] for p in pending]), torch.stack([p[2] for p in pending]),
+                          torch.stack([p[3] for p in pending]), torch.stack([p[4] for p in pending]), residuals=residuals, engine=E)
+        host = {k: m[k].cpu() for k in METRICS + ("n_valid", "depth_max")}
+        for i, p in enumerate(pending):
+            row = {"idx": p[0]}
+            row.update({k: float(host[k][i]) for k in METRICS})
+            row["n_valid"], row["depth_max"] = int(host["n_valid"][i]), float(host["depth_max"][i])
+            if residuals:
+                row.update(depth=p[3], color=p[1], depth_residual=m["depth_residual"][i], color_residual=m["color_residual"][i])
+            rows.append(row)
+        pending.clear()
+
+    with torch.no_grad():
+        for idx, gt_color, gt_depth, pose in frames:
+            if len(pose.shape) == 1:
+                bottom = torch.tensor([[0.0, 0.0, 0.0, 1.0]], dtype=torch.float32, device=pose.device)
+                c2w = torch.cat([get_camera_from_tensor(pose.clone().detach()), bottom], dim=0)
+            else:
+                c2w = pose
+            depth, _, color = renderer.render_img(c, decoders, c2w, device, stage, gt_depth=gt_depth)
+            pending.append((idx, color.detach().to(E.device, torch.float32), torch.as_tensor(gt_color).detach().to(E.device, torch.float32),
+                            depth.detach().to(E.device, torch.float32), torch.as_tensor(gt_depth).detach().to(E.device, torch.float32)))
+            if len(pending) == batch:
+                flush()
+        flush()
+    return {"frames": rows, "mean": _means(rows), "n_frames": len(rows), "n_no_depth": sum(1 for r in rows if r["n_valid"] == 0)}
+
+
+# --------------------------------------------------------------------------------------------------
+# command line
+# --------------------------------------------------------------------------------------------------
+def main(argv=None, engine: Optional[Engine] = None):
+    ap = argparse.ArgumentParser(prog="python -m nice_slam_amd.imgeval",
+                                 description="PSNR, SSIM and depth L1 of rendered frames against input frames on the GPU.")
+    ap.add_argument("rendered", type=str, help=".npz with the rendered frames: color [B, H, W, 3] (or [H, W, 3]) and depth [B, H, W]")
+    ap.add_argument("gt", type=str, help=".npz with the input frames: color and depth of the same shapes")
+    args = ap.parse_args(argv)
+    r, g = np.load(args.rendered), np.load(args.gt)
+    m = image_metrics(r["color"], g["color"], r["depth"], g["depth"], engine=engine)
+    rows = [{k: float(v) for k, v in zip(METRICS, vals)}
+            for vals in zip(*(m[k].reshape(-1).cpu().tolist() for k in METRICS))]
+    mean = _means(rows)
+    print("PSNR: ", mean["psnr"])
+    print("SSIM: ", mean["ssim"])
+    print("Depth L1: ", mean["depth_l1_cm"])
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -722,6 +722,22 @@ class MiniSLAM:
         return res
 
 
+def eval_render(ops, seq, est, every):
+    """PSNR / SSIM / depth L1 of every ``every``-th frame re-rendered at its estimated pose (nice_slam_amd.evaluate_rendering)"""
+    def frames():
+        for k in range(0, seq.n, every):
+            color, depth, _ = seq.frame(k)
+            yield k, color, depth, est[k].to(ops.device).float()
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        ev = ops.nsa.evaluate_rendering(ops.renderer, ops.c, ops.decoders, frames(), stage="color", device=ops.device)
+    torch.cuda.synchronize()
+    out = {"every": every, "n_frames": ev["n_frames"], "n_no_depth": ev["n_no_depth"], "seconds": round(time.perf_counter() - t0, 3),
+           "psnr": ev["mean"]["psnr"], "ssim": ev["mean"]["ssim"], "depth_l1_cm": ev["mean"]["depth_l1_cm"]}
+    print(f"PSNR: {out['psnr']:.3f} dB  SSIM: {out['ssim']:.4f}  Depth L1: {out['depth_l1_cm']:.3f} cm  ({out['n_frames']} frames)", file=sys.stderr)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=100)
@@ -742,6 +758,9 @@ def main():
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--unfused", action="store_true", help="mapping through get_samples / render_batch_ray / torch losses, eagerly (default: "
                                                             "nice_slam_amd.mapping_loss + capturable optimisers, replayed from hipGraphs)")
+    ap.add_argument("--eval-render", type=int, default=0, metavar="N",
+                    help="after the run, re-render every N-th frame at its estimated pose and report PSNR, SSIM and depth L1 "
+                         "(nice_slam_amd.evaluate_rendering); 0: off")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     import copy
@@ -768,6 +787,8 @@ def main():
     res["coarse_ms_per_iter"] = round(1e3 * res["coarse_s"] / max(1, res["coarse_iters"]), 4)
     res["metric"] = "ATE RMSE [cm] on a synthetic RGB-D sequence"
     res["value"] = res["ate"]["rmse"] * 100
+    if args.eval_render > 0:
+        res["render_eval"] = eval_render(ops, seq, slam.est, args.eval_render)
     print(json.dumps(res))
 
 
