@@ -435,7 +435,9 @@ class ShardedMapping:
 
     def mapping_loss(self, c, decoders, frames, pixs_per_image, stage, w_color: float = 0.2, indices=None, out=None):
         """This rank's share of one mapping iteration (``pixs_per_image`` pixels per frame HERE); returns the rank's partial
-        loss -- ``backward()`` leaves the all-rank gradients on every rank (and the all-rank loss in ``last_total_loss``)."""
+        loss -- ``backward()`` leaves the all-rank gradients on every rank (and the all-rank loss in ``last_total_loss``).
+        Every rank must pass the same ``pixs_per_image``, the same number of frames and the same crop: the window kernel re-draws
+        its peers' pixels with the LOCAL values, so ranks that differ in them would disagree on the batch-global depth cap."""
         from . import mapping
         state, peers = None, None
         if indices is None:                  # this rank's own draw (see __init__): never the global generator / the device's state

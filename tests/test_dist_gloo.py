@@ -1,12 +1,14 @@
-"""CPU, world_size 2, gloo: the ray-sharding logic of nice_slam_amd.parallel.
+"""CPU, world sizes 2 to 8, gloo: the ray-sharding logic of nice_slam_amd.parallel.
 
 The inner renderer is an oracle-backed stand-in with the same ``render_batch_ray`` / ``_gt_max`` protocol
 (the HIP renderer needs a GPU); what is under test is the distributed plumbing: contiguous sharding, the
 batch-global max(gt_depth) taken before slicing, all-gather of outputs, all-gather of ray gradients and the
 SUM all-reduce of the replicated feature-grid gradients.  Result must equal the single-process result."""
 import os
+import queue
 import socket
 import sys
+import time
 
 import pytest
 import torch
@@ -80,24 +82,66 @@ def _worker(rank, world, port, stage, q, masked=False):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("stage", ["color", "coarse"])
-def test_two_rank_sharding_matches_single_process(stage):
-    from scene_util import make_scene, oracle_render, rel_err
+def _run_workers(target, world, args, timeout=120):
+    """``target(rank, world, port, *args(q))`` in ``world`` spawned processes -> {rank: what it put on the queue}.  A worker that
+    dies, or a queue that stays empty for ``timeout`` seconds, fails the test at once; whatever happens, no worker outlives this call
+    (the survivors of a failed worker sit in a collective that never completes)."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, stage, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = dict(q.get(timeout=120) for _ in range(2))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    ref = oracle_render(make_scene(seed=5, n_rays=23, small=True), stage, backward=True)
-    assert res[0]["shard"].tolist() == [0, 12] and res[1]["shard"].tolist() == [12, 23]
-    for rank in (0, 1):
+    procs = [ctx.Process(target=target, args=(r, world, port, *args(q))) for r in range(world)]
+    try:
+        for p in procs:
+            p.start()
+        res, deadline = [], time.monotonic() + timeout
+        while len(res) < world:
+            try:
+                res.append(q.get(timeout=0.5))
+            except queue.Empty:
+                failed = [(r, p.exitcode) for r, p in enumerate(procs) if p.exitcode not in (None, 0)]
+                assert not failed, f"workers (rank, exit code) {failed} failed"
+                assert time.monotonic() < deadline, f"only {len(res)} of {world} workers answered within {timeout} s"
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+        return res
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+        for p in procs:
+            if p.pid is not None:
+                p.join(timeout=10)
+                if p.is_alive():
+                    p.kill()
+                    p.join()
+
+
+@pytest.mark.parametrize("stage,world,masked", [("color", 2, False), ("coarse", 2, False), ("color", 3, False), ("color", 5, False),
+                                                ("color", 8, False), ("color", 8, True)],
+                         ids=["color", "coarse", "color-3", "color-5", "color-8", "color-8-masked"])
+def test_two_rank_sharding_matches_single_process(stage, world, masked):
+    """2, 3, 5 and 8 ranks over 23 rays: contiguous, disjoint shards that cover the batch and differ in length by at most one, and
+    on EVERY rank the single-process result (masked: the grid gradients inside the voxel masks, which is what travels)."""
+    from scene_util import make_scene, oracle_render, rel_err
+    res = dict(_run_workers(_worker, world, lambda q: (stage, q, masked)))
+    sc = make_scene(seed=5, n_rays=23, small=True)
+    ref = oracle_render(sc, stage, backward=True)
+    shards = [res[r]["shard"].tolist() for r in range(world)]
+    if world == 2:
+        assert shards == [[0, 12], [12, 23]]
+    assert shards[0][0] == 0 and shards[-1][1] == 23
+    assert all(a[1] == b[0] for a, b in zip(shards, shards[1:]))                 # contiguous and disjoint
+    sizes = [b - a for a, b in shards]
+    assert min(sizes) >= 1 and max(sizes) - min(sizes) <= 1
+    masks = _voxel_masks(sc) if masked else None
+    for rank in range(world):
         for k, v in ref.items():
-            assert rel_err(res[rank][k], v) < 2e-5, (rank, k)
+            got, want = res[rank][k], v.numpy() if hasattr(v, "numpy") else v
+            if masked and k.startswith("d_grid"):
+                m = masks[k[2:]].numpy()[None, None].repeat(32, 1)
+                got, want = got[m], want[m]
+            assert rel_err(got, want) < 2e-5, (world, rank, k)
 
 
 def test_two_rank_masked_gradient_exchange():

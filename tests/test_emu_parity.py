@@ -10,6 +10,7 @@ import torch
 
 from conftest import golden_scene, rel_err
 from scene_util import make_scene, oracle_render
+from window_reference import _philox_word
 
 STAGES = ("coarse", "middle", "fine", "color")
 TOL = 1e-4
@@ -426,21 +427,6 @@ def test_get_samples_window_and_pose_grad(emu):
         ref = c2ws[k].grad.numpy()
         assert rel_err(out[k, :3], ref[:3]) < 1e-5, k
         assert np.all(out[k, 3] == 0)
-
-
-def _philox_word(c, key):
-    """philox4x32-10, first output word, restated from Salmon et al. (SC'11) -- the test's own copy, vectorised over counters
-    c [n, 4] uint32; key (k0, k1)."""
-    c = c.astype(np.uint64).copy()
-    k0, k1 = np.uint64(key[0]), np.uint64(key[1])
-    M0, M1, m32 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = M0 * c[:, 0], M1 * c[:, 2]
-        n0 = ((p1 >> np.uint64(32)) ^ c[:, 1] ^ k0) & m32
-        n2 = ((p0 >> np.uint64(32)) ^ c[:, 3] ^ k1) & m32
-        c = np.stack([n0, p1 & m32, n2, p0 & m32], 1)
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
-    return c[:, 0]
 
 
 def test_window_kernel_draws_its_own_pixels(emu):

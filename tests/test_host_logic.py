@@ -204,3 +204,40 @@ def test_tile_liveness_reciprocal_is_an_exact_division():
         q = (x * np.uint64(magic & 0xFFFFFFFF if S > 1 else 0)) >> np.uint64(32)
         if S > 1:
             assert np.array_equal(q, x // np.uint64(S)), S
+
+
+def test_sharded_mapping_rank_and_peer_seeds(monkeypatch):
+    """ShardedMapping.rank_seed / peer_seeds (the seeds the sharded window kernel re-draws its peers from): every other rank in rank
+    order, without the caller; no list (the MAX all-reduce instead) for one rank, for more than 16 and with peer_draw=False; and on
+    the CPU path a torch draw, no device draw state."""
+    import types
+    import torch.distributed as dist
+    from nice_slam_amd import mapping
+    from nice_slam_amd.parallel import ShardedMapping
+    renderer = types.SimpleNamespace(H=48, W=64)
+    where = {}
+    monkeypatch.setattr(dist, "get_rank", lambda group=None: where["rank"])
+    monkeypatch.setattr(dist, "get_world_size", lambda group=None: where["world"])
+    sh = ShardedMapping(renderer, group=None, seed=11)
+    seeds = [sh.rank_seed(r) for r in range(16)]
+    assert len(set(seeds)) == 16 and all(0 <= s < (1 << 63) for s in seeds)
+    assert all(0 <= ShardedMapping(renderer, seed=(1 << 62) + 12345).rank_seed(r) < (1 << 63) for r in range(16))
+    assert seeds != [ShardedMapping(renderer, seed=12).rank_seed(r) for r in range(16)]
+    for world in range(2, 17):
+        for rank in range(world):
+            where.update(rank=rank, world=world)
+            peers = sh.peer_seeds()
+            assert peers == [seeds[r] for r in range(world) if r != rank], (world, rank)      # rank order, own rank left out
+            assert len(peers) == world - 1 and seeds[rank] not in peers
+            assert ShardedMapping(renderer, seed=11, peer_draw=False).peer_seeds() is None
+    for world in (1, 17):
+        where.update(rank=0, world=world)
+        assert sh.peer_seeds() is None, world
+    # CPU frames: the pixels come from the rank's torch generator; no in-kernel draw state is made, no peers are passed
+    seen = {}
+    monkeypatch.setattr(mapping, "mapping_loss", lambda *a, **kw: seen.update(kw) or torch.zeros(()))
+    where.update(rank=1, world=4)
+    frames = [(torch.eye(4), torch.ones((48, 64)), torch.zeros((48, 64, 3)))] * 3
+    sh.mapping_loss({}, None, frames, 25, "color")
+    assert sh._draw_state is None and seen["draw_state"] is None and seen["peer_seeds"] is None and seen["sharder"] is sh
+    assert seen["indices"].shape == (75,) and int(seen["indices"].min()) >= 0 and int(seen["indices"].max()) < 48 * 64
