@@ -28,6 +28,8 @@
  *                        <- src/tools/eval_recon.py:24-59,91-117, src/tools/cull_mesh.py:45-75  reconstruction evaluation
  *   nsr_raster_* / nsr_depth_error / nsr_view_unseen
  *                        <- src/tools/eval_recon.py:131-211  depth rendering and the 2-D depth metric
+ *   nsr_frame_out_size / nsr_frame_workspace_bytes / nsr_frame_prepare
+ *                        <- src/utils/datasets.py:77-113  BaseDataset.__getitem__ between the decoded files and the tensors
  *
  * Conventions
  *   - all pointers are DEVICE pointers owned by the caller (PyTorch); the library never frees or
@@ -580,6 +582,36 @@ int nsr_points_visible(const void *pts, int64_t n, int32_t fp64, const float *w2
 int64_t nsr_image_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int nsr_image_metrics(const float *color, const float *gt_color, const float *depth, const float *gt_depth, int32_t B, int32_t H, int32_t W,
                       double *result, float *depth_residual, float *color_residual, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* --- Frame preparation (src/utils/datasets.py:77-113, BaseDataset.__getitem__ after the files are decoded) ---------------------
+ * The raw bytes of B frames of one geometry in, the tensors the tracker and the mapper read out: undistortion of the colour image
+ * (its own launch, only with distortion coefficients), then ONE launch for the channel order, / 255, the resize of the colour
+ * image to the depth image's size, the depth scale, the crop_size resize, crop_edge and the cast.  The numerical contract is
+ * written out in nice_slam_amd/csrc/nsr_frame.h.
+ *   color_raw u8 [B][color_h][color_w][3], channels BGR (color_bgr = 1: cv2.imread) or RGB (0: PIL)
+ *   depth_raw [B][depth_h][depth_w], uint16 (depth_type NSR_DEPTH_U16) or fp32 (NSR_DEPTH_F32)
+ *   color fp32 [B][H][W][3] RGB, depth fp32 [B][H][W] = ((float)raw / (float)png_depth_scale) * (float)scale, where
+ *   (Hs, Ws) = (crop_h, crop_w) if both are > 0 (both 0: (depth_h, depth_w)) and H = Hs - 2 crop_edge, W = Ws - 2 crop_edge.
+ * Every size is in [1, 32768], 0 <= 2 crop_edge < min(Hs, Ws), png_depth_scale is positive and finite as a float; with
+ * has_distortion, fx and fy are not 0 and dist = [k1, k2, p1, p2, k3] (the intrinsics are those of the RAW colour image, read
+ * only then).  B = 0 succeeds and launches nothing.
+ *   nsr_frame_out_size         H, W of the description
+ *   nsr_frame_workspace_bytes  device workspace of nsr_frame_prepare: 3 B color_h color_w with distortion, else 0 (-1: invalid)
+ *   nsr_frame_prepare          workspace may be null when none is needed.  No atomics, nothing synchronises; a frame's result
+ *                              does not depend on its place in the batch. */
+enum { NSR_DEPTH_U16 = 0, NSR_DEPTH_F32 = 1 };
+typedef struct nsr_frame_desc {
+    int32_t color_h, color_w, depth_h, depth_w;
+    int32_t depth_type, color_bgr;
+    int32_t crop_h, crop_w, crop_edge, has_distortion;
+    double fx, fy, cx, cy;
+    double dist[5];
+    double png_depth_scale, scale;
+} nsr_frame_desc;
+int nsr_frame_out_size(const nsr_frame_desc *desc, int32_t *H, int32_t *W);
+int64_t nsr_frame_workspace_bytes(const nsr_frame_desc *desc, int32_t B);
+int nsr_frame_prepare(const void *color_raw, const void *depth_raw, const nsr_frame_desc *desc, int32_t B, float *color, float *depth,
+                      void *workspace, int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@ path, drop-in behind the reference's Renderer / decoder / get_samples call surfa
     from nice_slam_amd import bound_from_frames, ConvexBound     # Mesher.get_bound_from_frames: TSDF fusion + convex hull
     from nice_slam_amd import KeyframeSelector                   # Mapper.keyframe_selection_overlap
     from nice_slam_amd import imgeval      # Visualizer.vis: image_metrics (PSNR, SSIM, depth L1, residual maps), evaluate_rendering
+    from nice_slam_amd import get_dataset, FramePreparer         # src/utils/datasets.py: the sequence readers, frames prepared on the GPU
 
 No CPU / PyTorch fallback exists: every arithmetic entry point goes through libnsr.so.
 """
@@ -25,10 +26,13 @@ from . import bound  # noqa: F401
 from .bound import ConvexBound, bound_from_frames, surface_points, tsdf_fuse  # noqa: F401
 from . import imgeval  # noqa: F401
 from .imgeval import evaluate_rendering, image_metrics  # noqa: F401
+from . import datasets  # noqa: F401
+from .datasets import FramePreparer, get_dataset  # noqa: F401
 
 __all__ = ["Renderer", "NICE", "MLP", "MLP_no_xyz", "get_samples", "get_rays", "grid_init", "load_bound",
            "to_channels_last", "MaskedGridAdam", "FlatAdam", "FrustumSelector", "KeyframeSelector", "aabb_keep", "get_samples_window", "mapping_loss", "tracking_loss", "seed_pixel_draws", "get_camera_from_tensor", "backward",
            "Mesher", "marching_cubes",
            "recon", "nearest", "sample_surface", "align_icp", "calc_3d_metric", "cull_mesh",
            "bound", "bound_from_frames", "ConvexBound", "tsdf_fuse", "surface_points",
-           "imgeval", "image_metrics", "evaluate_rendering"]
+           "imgeval", "image_metrics", "evaluate_rendering",
+           "datasets", "get_dataset", "FramePreparer"]

@@ -68,6 +68,14 @@ class NsrSpan(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("n", C.c_int64)]
 
 
+class NsrFrameDesc(C.Structure):
+    _fields_ = [("color_h", C.c_int32), ("color_w", C.c_int32), ("depth_h", C.c_int32), ("depth_w", C.c_int32),
+                ("depth_type", C.c_int32), ("color_bgr", C.c_int32),
+                ("crop_h", C.c_int32), ("crop_w", C.c_int32), ("crop_edge", C.c_int32), ("has_distortion", C.c_int32),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("dist", C.c_double * 5), ("png_depth_scale", C.c_double), ("scale", C.c_double)]
+
+
 class NsrAdamSpan(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("step", C.c_void_p),
                 ("lr", C.c_float), ("pad_", C.c_int32)]
@@ -196,6 +204,10 @@ SYMBOLS = (
     ("nsr_image_metrics_workspace_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     ("nsr_image_metrics", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("nsr_frame_out_size", C.c_int, [C.POINTER(NsrFrameDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("nsr_frame_workspace_bytes", C.c_int64, [C.POINTER(NsrFrameDesc), C.c_int32]),
+    ("nsr_frame_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NsrFrameDesc), C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int64, C.c_void_p]),
 )
 
 

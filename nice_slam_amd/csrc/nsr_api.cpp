@@ -16,6 +16,7 @@
 #include "../../nice_slam_amd/csrc/nsr_bound.h"
 #include "../../nice_slam_amd/csrc/nsr_raster.h"
 #include "../../nice_slam_amd/csrc/nsr_imgmetrics.h"
+#include "../../nice_slam_amd/csrc/nsr_frame.h"
 
 namespace {
 
@@ -1680,6 +1681,109 @@ int nsr_image_metrics(const float *color, const float *gt_color, const float *de
     NSR_LAUNCH(nsr::imgmetrics_tile_kernel, dim3(P.ntiles, B), dim3(T), nsr::kImLds, stream, P);
     NSR_LAUNCH(nsr::imgmetrics_final_kernel, dim3(B), dim3(T), nsr::kImFinalLds, stream, P);
     return finish("nsr_image_metrics");
+}
+
+}  // extern "C"
+
+// ---- frame preparation (include/nsr.h, "Frame preparation") ----
+namespace {
+
+constexpr int kFrameMaxSide = 32768;
+
+struct FrameGeometry {
+    int Hs, Ws, H, W;
+    bool crop, resize;
+    float png_depth_scale;
+};
+
+// nullptr: the description is valid and G is filled; else what is wrong with it
+const char *frame_geometry(const nsr_frame_desc *d, FrameGeometry &G) {
+    if (!d) return "null pointer";
+    const int32_t sides[4] = {d->color_h, d->color_w, d->depth_h, d->depth_w};
+    for (int32_t s : sides)
+        if (s < 1 || s > kFrameMaxSide) return "image sizes must be in [1, 32768]";
+    if ((d->crop_h == 0) != (d->crop_w == 0) || d->crop_h < 0 || d->crop_w < 0 || d->crop_h > kFrameMaxSide || d->crop_w > kFrameMaxSide)
+        return "crop_h and crop_w must both be 0 (no crop_size) or both in [1, 32768]";
+    if (d->depth_type != NSR_DEPTH_U16 && d->depth_type != NSR_DEPTH_F32) return "depth_type must be NSR_DEPTH_U16 or NSR_DEPTH_F32";
+    G.crop = d->crop_h > 0;
+    G.Hs = G.crop ? d->crop_h : d->depth_h;
+    G.Ws = G.crop ? d->crop_w : d->depth_w;
+    if (d->crop_edge < 0 || 2ll * d->crop_edge >= G.Hs || 2ll * d->crop_edge >= G.Ws) return "crop_edge must be >= 0 and leave at least one pixel";
+    G.H = G.Hs - 2 * d->crop_edge;
+    G.W = G.Ws - 2 * d->crop_edge;
+    G.resize = d->color_h != d->depth_h || d->color_w != d->depth_w;
+    G.png_depth_scale = (float)d->png_depth_scale;
+    if (!(G.png_depth_scale > 0.f) || !std::isfinite(G.png_depth_scale)) return "png_depth_scale must be positive and finite";
+    if (d->has_distortion) {
+        if (!(d->fx != 0.0) || !(d->fy != 0.0) || !std::isfinite(d->fx) || !std::isfinite(d->fy))
+            return "distortion needs fx and fy that are finite and not 0";
+    }
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nsr_frame_out_size(const nsr_frame_desc *desc, int32_t *H, int32_t *W) {
+    FrameGeometry G;
+    if (const char *e = frame_geometry(desc, G)) return fail(std::string("nsr_frame_out_size: ") + e);
+    if (!H || !W) return fail("nsr_frame_out_size: null pointer");
+    *H = G.H;
+    *W = G.W;
+    return 0;
+}
+
+int64_t nsr_frame_workspace_bytes(const nsr_frame_desc *desc, int32_t B) {
+    FrameGeometry G;
+    if (B < 0 || frame_geometry(desc, G)) return -1;
+    return desc->has_distortion ? 3ll * B * desc->color_h * desc->color_w : 0;
+}
+
+int nsr_frame_prepare(const void *color_raw, const void *depth_raw, const nsr_frame_desc *desc, int32_t B, float *color, float *depth,
+                      void *workspace, int64_t workspace_bytes, void *stream) {
+    FrameGeometry G;
+    if (const char *e = frame_geometry(desc, G)) return fail(std::string("nsr_frame_prepare: ") + e);
+    if (B < 0) return fail("nsr_frame_prepare: negative batch size");
+    if (B == 0) return 0;
+    if (!color_raw || !depth_raw || !color || !depth) return fail("nsr_frame_prepare: null pointer");
+    const long long need = desc->has_distortion ? 3ll * B * desc->color_h * desc->color_w : 0;
+    if (need > 0 && !workspace) return fail("nsr_frame_prepare: null pointer (workspace, needed with distortion)");
+    if (workspace_bytes < need) return fail("nsr_frame_prepare: workspace too small (nsr_frame_workspace_bytes)");
+    const int T = nsr::kFrThreads;
+    const long long max_items = 2147483647ll * T;
+
+    nsr::FrameParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.color = static_cast<const unsigned char *>(color_raw);
+    if (desc->has_distortion) {
+        nsr::UndistortParams U;
+        std::memset(&U, 0, sizeof(U));
+        U.src = P.color; U.dst = static_cast<unsigned char *>(workspace);
+        U.H = desc->color_h; U.W = desc->color_w; U.items = (long long)B * U.H * U.W;
+        if (U.items > max_items) return fail("nsr_frame_prepare: too many pixels for one launch");
+        U.fx = desc->fx; U.fy = desc->fy; U.cx = desc->cx; U.cy = desc->cy;
+        U.k1 = desc->dist[0]; U.k2 = desc->dist[1]; U.p1 = desc->dist[2]; U.p2 = desc->dist[3]; U.k3 = desc->dist[4];
+        NSR_LAUNCH(nsr::frame_undistort_kernel, dim3((unsigned)nblk(U.items, T)), dim3(T), 0, stream, U);
+        P.color = U.dst;
+    }
+    P.depth = depth_raw; P.out_color = color; P.out_depth = depth;
+    P.Hc = desc->color_h; P.Wc = desc->color_w; P.Hd = desc->depth_h; P.Wd = desc->depth_w;
+    P.H = G.H; P.W = G.W; P.edge = desc->crop_edge;
+    P.depth_f32 = desc->depth_type == NSR_DEPTH_F32 ? 1 : 0;
+    P.bgr = desc->color_bgr ? 1 : 0;
+    P.resize = G.resize ? 1 : 0; P.crop = G.crop ? 1 : 0;
+    P.stream = (!desc->has_distortion && !G.resize && !G.crop) ? 1 : 0;
+    P.png_depth_scale = G.png_depth_scale; P.scale = (float)desc->scale;
+    P.nn_h = (float)P.Hd / (float)G.Hs; P.nn_w = (float)P.Wd / (float)G.Ws;
+    P.rs_h = (double)P.Hc / (double)P.Hd; P.rs_w = (double)P.Wc / (double)P.Wd;
+    P.ac_h = G.Hs > 1 ? (double)(P.Hd - 1) / (double)(G.Hs - 1) : 0.0;
+    P.ac_w = G.Ws > 1 ? (double)(P.Wd - 1) / (double)(G.Ws - 1) : 0.0;
+    for (int i = 0; i < 256; ++i) P.tab[i] = (float)((double)i / 255.0);
+    P.items = (long long)B * P.H * (P.stream ? (P.W + nsr::kFrLane - 1) / nsr::kFrLane : P.W);
+    if (P.items > max_items) return fail("nsr_frame_prepare: too many pixels for one launch");
+    NSR_LAUNCH(nsr::frame_prepare_kernel, dim3((unsigned)nblk(P.items, T)), dim3(T), 0, stream, P);
+    return finish("nsr_frame_prepare");
 }
 
 }  // extern "C"
