@@ -562,6 +562,40 @@ int nsr_view_unseen(const void *pts, int64_t n, int32_t fp64, const float *w2c, 
 int nsr_points_visible(const void *pts, int64_t n, int32_t fp64, const float *w2c, int32_t K, const float *depth, int32_t H, int32_t W,
                        double fx, double fy, double cx, double cy, double near, double far, double eps, int32_t *count, void *stream);
 
+/* --- Replay view (visualizer.py with src/tools/viz.py: the shaded mesh, camera wireframes and trajectories of a finished run) ---
+ * The colour side of the rasterizer; the numerical contract is written out in nice_slam_amd/csrc/nsr_view.h.  Meshes, poses,
+ * intrinsics, image limits and near / far as in "Depth rasterization".
+ *   nsr_view_workspace_bytes    device workspace of nsr_raster_bin + nsr_view_mesh (nsr_raster_workspace_bytes; -1: invalid sizes)
+ *   nsr_view_normals            area-weighted vertex normals: start [n_verts + 1] int64 and incident [n_incident] int32 are the CSR
+ *                               list of the faces at each vertex, ascending face id per vertex (device); sums [n_verts][3] fp64 out
+ *                               (may be null): the summed face cross products; normals [n_verts][3] fp32 out: the sums normalised,
+ *                               a zero sum stays zero.
+ *   nsr_view_mesh               after nsr_raster_bin on the same arguments and workspace, in the place of nsr_raster_depth: bins
+ *                               [n_entries] int32 of device scratch; normals [n_verts][3] fp32; colors [n_verts][3] uint8 or null
+ *                               (0.8 grey); cull: NSR_CULL_NONE, NSR_CULL_BACK (drop the faces whose normal (V1 - V0) x (V2 - V0)
+ *                               points away from the camera) or NSR_CULL_FRONT (drop the others).  Out: depth [K][H][W] fp32 (with
+ *                               NSR_CULL_NONE what nsr_raster_depth writes, bit for bit), face [K][H][W] int32 (the smallest id
+ *                               among the faces at the winning depth, -1: background), rgb [K][H][W][3] uint8 (headlight shading,
+ *                               white background).
+ *   nsr_view_points             B frames of square points over a base layer: frame b draws pts / colors [offsets[b] ..
+ *                               offsets[b + 1]) (offsets [B + 1] int64, device; n: the length of pts / colors) with w2c [b] over
+ *                               base_rgb / base_depth [b] (base_per_frame != 0) or [0] (shared) into rgb [b]; a point pixel is
+ *                               drawn iff the base depth there is 0 or the point is not behind it; the nearest point wins, then
+ *                               the smallest index.  owner [B][H][W] int32 out (may be null): the index in its frame of the
+ *                               point drawn, -1 where the base shows.  1 <= size <= 64, B <= 65535.
+ * All bit-identical run to run. */
+enum { NSR_CULL_NONE = 0, NSR_CULL_BACK = 1, NSR_CULL_FRONT = 2 };
+int64_t nsr_view_workspace_bytes(int64_t n_verts, int64_t n_faces, int32_t K, int32_t H, int32_t W);
+int nsr_view_normals(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const int64_t *start,
+                     const int32_t *incident, int64_t n_incident, double *sums, float *normals, void *stream);
+int nsr_view_mesh(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *w2c, int32_t K, int32_t H,
+                  int32_t W, double fx, double fy, double cx, double cy, double near, double far, void *workspace, int32_t *bins,
+                  int64_t n_entries, const float *normals, const uint8_t *colors, int32_t cull, float *depth, int32_t *face,
+                  uint8_t *rgb, void *stream);
+int nsr_view_points(const float *pts, const uint8_t *colors, int64_t n, const int64_t *offsets, const float *w2c, int32_t B, int32_t H,
+                    int32_t W, double fx, double fy, double cx, double cy, double near, double far, int32_t size,
+                    const uint8_t *base_rgb, const float *base_depth, int32_t base_per_frame, uint8_t *rgb, int32_t *owner, void *stream);
+
 /* --- Rendering evaluation (src/utils/Visualizer.py:53-65, with PSNR / SSIM / depth L1 of the re-rendered frames) ------------
  * One launch pair evaluates B frame pairs; the numerical contract is written out in nice_slam_amd/csrc/nsr_imgmetrics.h.
  * color / gt_color [B][H][W][3] fp32 (rendered / input), depth / gt_depth [B][H][W] fp32; a pixel is valid iff its input depth

@@ -15,6 +15,7 @@
 #include "../../nice_slam_amd/csrc/nsr_recon.h"
 #include "../../nice_slam_amd/csrc/nsr_bound.h"
 #include "../../nice_slam_amd/csrc/nsr_raster.h"
+#include "../../nice_slam_amd/csrc/nsr_view.h"
 #include "../../nice_slam_amd/csrc/nsr_imgmetrics.h"
 #include "../../nice_slam_amd/csrc/nsr_frame.h"
 
@@ -1628,6 +1629,77 @@ int nsr_points_visible(const void *pts, int64_t n, int32_t fp64, const float *w2
     const int T = nsr::kRasterThreads;
     NSR_LAUNCH(nsr::points_visible_kernel, dim3(nblk(n, T)), dim3(T), nsr::kRasterViewChunk * 12 * 4, stream, P);
     return finish("nsr_points_visible");
+}
+
+}  // extern "C"
+
+// ---- replay view: vertex normals, the shaded mesh layer and the point layer (include/nsr.h, "Replay view") ----
+extern "C" {
+
+int64_t nsr_view_workspace_bytes(int64_t n_verts, int64_t n_faces, int32_t K, int32_t H, int32_t W) {
+    return nsr_raster_workspace_bytes(n_verts, n_faces, K, H, W);      // the mesh layer draws from nsr_raster_bin's workspace
+}
+
+int nsr_view_normals(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const int64_t *start,
+                     const int32_t *incident, int64_t n_incident, double *sums, float *normals, void *stream) {
+    if (n_verts < 1 || n_faces < 1) return fail("nsr_view_normals: empty mesh");
+    if (n_verts > 2147483647ll || n_faces > 2147483647ll) return fail("nsr_view_normals: more than 2^31 - 1 vertices or faces");
+    if (n_incident < 0 || n_incident > 3 * n_faces) return fail("nsr_view_normals: the incidence list holds 0 .. 3 n_faces entries");
+    if (!verts || !faces || !start || !normals || (n_incident > 0 && !incident)) return fail("nsr_view_normals: null pointer");
+    nsr::NormalParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.verts = verts; P.faces = faces; P.nv = n_verts; P.nf = n_faces;
+    P.start = reinterpret_cast<const long long *>(start); P.incident = incident; P.n_incident = n_incident;
+    P.sums = sums; P.normals = normals;
+    const int T = nsr::kRasterThreads;
+    NSR_LAUNCH(nsr::view_normals_kernel, dim3(nblk(n_verts, T)), dim3(T), 0, stream, P);
+    return finish("nsr_view_normals");
+}
+
+int nsr_view_mesh(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *w2c, int32_t K, int32_t H,
+                  int32_t W, double fx, double fy, double cx, double cy, double near, double far, void *workspace, int32_t *bins,
+                  int64_t n_entries, const float *normals, const uint8_t *colors, int32_t cull, float *depth, int32_t *face,
+                  uint8_t *rgb, void *stream) {
+    nsr::MeshViewParams M;
+    std::memset(&M, 0, sizeof(M));
+    nsr::RasterParams &P = M.R;
+    if (int rc = raster_setup(P, verts, n_verts, faces, n_faces, w2c, K, H, W, fx, fy, cx, cy, near, far, workspace, "nsr_view_mesh")) return rc;
+    if (cull != nsr::kViewCullNone && cull != nsr::kViewCullBack && cull != nsr::kViewCullFront)
+        return fail("nsr_view_mesh: bad cull mode (NSR_CULL_NONE, NSR_CULL_BACK or NSR_CULL_FRONT)");
+    if (n_entries < 0) return fail("nsr_view_mesh: negative entry count");
+    if (!normals || !depth || !face || !rgb || (n_entries > 0 && !bins)) return fail("nsr_view_mesh: null pointer");
+    P.bins = bins; P.depth = depth; P.cap = n_entries;
+    M.normals = normals; M.colors = colors; M.cull = cull; M.face = face; M.rgb = rgb;
+    const int T = nsr::kRasterThreads;
+    if (n_entries > 0) NSR_LAUNCH(nsr::raster_emit_kernel, dim3((unsigned)P.nchunks, K), dim3(T), 4 * 4 * P.ntiles, stream, P);
+    NSR_LAUNCH(nsr::view_resolve_kernel, dim3(P.ntiles, K), dim3(T), nsr::kViewResolveLds, stream, M);
+    return finish("nsr_view_mesh");
+}
+
+int nsr_view_points(const float *pts, const uint8_t *colors, int64_t n, const int64_t *offsets, const float *w2c, int32_t B, int32_t H,
+                    int32_t W, double fx, double fy, double cx, double cy, double near, double far, int32_t size,
+                    const uint8_t *base_rgb, const float *base_depth, int32_t base_per_frame, uint8_t *rgb, int32_t *owner, void *stream) {
+    if (B < 1) return fail("nsr_view_points: no views");
+    if (B > 65535) return fail("nsr_view_points: more than 65535 frames in one call");
+    if (H < 1 || W < 1 || H > nsr::kRasterMaxTiles || W > nsr::kRasterMaxTiles) return fail("nsr_view_points: image sizes must be 1..1024");
+    if (n < 0 || n > 2147483647ll) return fail("nsr_view_points: 0 .. 2^31 - 1 points");
+    if (size < 1 || size > nsr::kViewMaxPointSize) return fail("nsr_view_points: point size must be 1..64");
+    if (!(near > 0.0) || !(far > near) || !std::isfinite(far)) return fail("nsr_view_points: need 0 < near < far (finite)");
+    if (!(fx != 0.0) || !(fy != 0.0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail("nsr_view_points: focal lengths must be finite and non-zero");
+    if (!offsets || !w2c || !base_rgb || !base_depth || !rgb || (n > 0 && (!pts || !colors))) return fail("nsr_view_points: null pointer");
+    nsr::PointViewParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.pts = pts; P.colors = colors; P.offsets = reinterpret_cast<const long long *>(offsets); P.n = n; P.w2c = w2c;
+    P.B = B; P.H = H; P.W = W; P.size = size; P.base_per_frame = base_per_frame ? 1 : 0;
+    P.tx = (W + nsr::kRasterTile - 1) / nsr::kRasterTile;
+    P.ty = (H + nsr::kRasterTile - 1) / nsr::kRasterTile;
+    P.ntiles = P.tx * P.ty;
+    P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.near = near; P.far = far;
+    P.base_rgb = base_rgb; P.base_depth = base_depth; P.rgb = rgb; P.owner = owner;
+    const int T = nsr::kRasterThreads;
+    NSR_LAUNCH(nsr::view_points_kernel, dim3(P.ntiles, B), dim3(T), 8 * nsr::kRasterTile * nsr::kRasterTile, stream, P);
+    return finish("nsr_view_points");
 }
 
 }  // extern "C"
