@@ -9,6 +9,7 @@ path, drop-in behind the reference's Renderer / decoder / get_samples call surfa
     from nice_slam_amd import imgeval      # Visualizer.vis: image_metrics (PSNR, SSIM, depth L1, residual maps), evaluate_rendering
     from nice_slam_amd import get_dataset, FramePreparer         # src/utils/datasets.py: the sequence readers, frames prepared on the GPU
     from nice_slam_amd import viewer       # visualizer.py / src/tools/viz.py: Replay, render_mesh, draw_points (headless replay)
+    from nice_slam_amd.slam import NICE_SLAM, load_config        # run.py: the run from its config; poses on the device (Trajectory)
 
 No CPU / PyTorch fallback exists: every arithmetic entry point goes through libnsr.so.
 """
@@ -30,6 +31,8 @@ from .imgeval import evaluate_rendering, image_metrics  # noqa: F401
 from . import datasets  # noqa: F401
 from .datasets import FramePreparer, get_dataset  # noqa: F401
 from . import viewer  # noqa: F401
+from . import poses  # noqa: F401
+from .poses import Trajectory, get_tensor_from_camera  # noqa: F401
 
 __all__ = ["Renderer", "NICE", "MLP", "MLP_no_xyz", "get_samples", "get_rays", "grid_init", "load_bound",
            "to_channels_last", "MaskedGridAdam", "FlatAdam", "FrustumSelector", "KeyframeSelector", "aabb_keep", "get_samples_window", "mapping_loss", "tracking_loss", "seed_pixel_draws", "get_camera_from_tensor", "backward",
@@ -38,4 +41,5 @@ __all__ = ["Renderer", "NICE", "MLP", "MLP_no_xyz", "get_samples", "get_rays", "
            "bound", "bound_from_frames", "ConvexBound", "tsdf_fuse", "surface_points",
            "imgeval", "image_metrics", "evaluate_rendering",
            "datasets", "get_dataset", "FramePreparer",
-           "viewer"]
+           "viewer",
+           "poses", "Trajectory", "get_tensor_from_camera"]

@@ -217,6 +217,10 @@ SYMBOLS = (
     ("nsr_frame_workspace_bytes", C.c_int64, [C.POINTER(NsrFrameDesc), C.c_int32]),
     ("nsr_frame_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NsrFrameDesc), C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_int64, C.c_void_p]),
+    ("nsr_tensor_from_camera", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("nsr_pose_predict", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("nsr_pose_commit", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_pose_store", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 )
 
 

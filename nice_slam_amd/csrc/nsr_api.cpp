@@ -18,6 +18,7 @@
 #include "../../nice_slam_amd/csrc/nsr_view.h"
 #include "../../nice_slam_amd/csrc/nsr_imgmetrics.h"
 #include "../../nice_slam_amd/csrc/nsr_frame.h"
+#include "../../nice_slam_amd/csrc/nsr_pose.h"
 
 namespace {
 
@@ -1856,6 +1857,53 @@ int nsr_frame_prepare(const void *color_raw, const void *depth_raw, const nsr_fr
     if (P.items > max_items) return fail("nsr_frame_prepare: too many pixels for one launch");
     NSR_LAUNCH(nsr::frame_prepare_kernel, dim3((unsigned)nblk(P.items, T)), dim3(T), 0, stream, P);
     return finish("nsr_frame_prepare");
+}
+
+}  // extern "C"
+
+// ---- pose algebra (include/nsr.h, "Pose algebra") ----
+extern "C" {
+
+int nsr_tensor_from_camera(const float *rt, int64_t n, int32_t row_floats, float *cam, void *stream) {
+    if (n < 0) return fail("nsr_tensor_from_camera: negative count");
+    if (row_floats != 12 && row_floats != 16) return fail("nsr_tensor_from_camera: row_floats must be 12 (3x4) or 16 (4x4)");
+    if (n == 0) return 0;
+    if (!rt || !cam) return fail("nsr_tensor_from_camera: null pointer");
+    nsr::PoseFromParams P;
+    P.rt = rt; P.n = n; P.row_floats = row_floats; P.cam = cam;
+    NSR_LAUNCH(nsr::pose_tensor_from_camera_kernel, dim3(1), dim3(nsr::kPoseThreads), 0, stream, P);
+    return finish("nsr_tensor_from_camera");
+}
+
+int nsr_pose_predict(float *traj, int64_t n_frames, const int64_t *idx, int32_t const_speed, float *cam, void *stream) {
+    if (n_frames < 1) return fail("nsr_pose_predict: the trajectory is empty");
+    if (!traj || !idx || !cam) return fail("nsr_pose_predict: null pointer");
+    nsr::PosePredictParams P;
+    P.traj = traj; P.n_frames = n_frames; P.idx = reinterpret_cast<const long long *>(idx); P.const_speed = const_speed ? 1 : 0; P.cam = cam;
+    NSR_LAUNCH(nsr::pose_predict_kernel, dim3(1), dim3(nsr::kPoseThreads), 0, stream, P);
+    return finish("nsr_pose_predict");
+}
+
+int nsr_pose_commit(const float *hist, int32_t n_iters, float *traj, int64_t n_frames, const int64_t *idx, float *best, void *stream) {
+    if (n_iters < 0) return fail("nsr_pose_commit: negative iteration count");
+    if (n_frames < 1) return fail("nsr_pose_commit: the trajectory is empty");
+    if (n_iters == 0) return 0;
+    if (!hist || !traj || !idx) return fail("nsr_pose_commit: null pointer");
+    nsr::PoseCommitParams P;
+    P.hist = hist; P.n_iters = n_iters; P.traj = traj; P.n_frames = n_frames; P.idx = reinterpret_cast<const long long *>(idx); P.best = best;
+    NSR_LAUNCH(nsr::pose_commit_kernel, dim3(1), dim3(nsr::kPoseThreads), 0, stream, P);
+    return finish("nsr_pose_commit");
+}
+
+int nsr_pose_store(const float *cams, int32_t m, const int64_t *index, float *dst, int64_t n_dst, void *stream) {
+    if (m < 0) return fail("nsr_pose_store: negative count");
+    if (m == 0) return 0;
+    if (n_dst < 1) return fail("nsr_pose_store: the pose table is empty");
+    if (!cams || !index || !dst) return fail("nsr_pose_store: null pointer");
+    nsr::PoseStoreParams P;
+    P.cams = cams; P.m = m; P.index = reinterpret_cast<const long long *>(index); P.dst = dst; P.n_dst = n_dst;
+    NSR_LAUNCH(nsr::pose_store_kernel, dim3(1), dim3(nsr::kPoseThreads), 0, stream, P);
+    return finish("nsr_pose_store");
 }
 
 }  // extern "C"
