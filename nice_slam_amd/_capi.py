@@ -228,16 +228,12 @@ class NsrError(RuntimeError):
     pass
 
 
-import threading
-
-restore_device = threading.local()      # .idx: the device common._stream() switched away from for the launch in flight
-
-
 class on_device:
-    """Device guard around an operation that makes SEVERAL library calls (a forward with its packing and window kernels, a
-    backward): the tensors' device is current from entry to exit -- for every launch, the per-device LDS-attribute cache and the
-    event records -- and the caller's device is restored on exit, exceptions included.  Inside the guard ``common._stream`` finds
-    the device already current and arms no restore of its own."""
+    """The one device switch of the package.  The library launches on the CURRENT device (its kernels carry no device guard,
+    and the per-device LDS-attribute cache and the event records follow it): the tensors' device is current from entry to exit
+    and the caller's device is restored on exit, exceptions included.  ``Engine.call`` guards each library call with it; an
+    operation that makes SEVERAL calls (a forward with its packing and window kernels, a backward) wraps them all in one, which
+    also covers the torch calls in between, and ``Engine.call`` then finds the device already current."""
 
     def __init__(self, device):
         self.idx = torch.device(device).index if device is not None else None
@@ -259,7 +255,7 @@ class on_device:
 
 
 class Lib:
-    """A loaded libnsr with typed entry points; ``check`` turns error codes into exceptions."""
+    """A loaded libnsr with typed entry points; ``call`` runs one by name and turns its error code into an exception."""
 
     def __init__(self, path: str):
         if not os.path.exists(path):
@@ -277,13 +273,12 @@ class Lib:
             raise NsrError(f"{path}: ABI version {self.nsr_version()} != {ABI_VERSION}")
 
     def check(self, rc: int, what: str = "nsr"):
-        prev = getattr(restore_device, "idx", None)
-        if prev is not None:                 # the launch is enqueued: back to the caller's current device (common._stream)
-            restore_device.idx = None
-            torch.cuda.set_device(prev)
         if rc != 0:
             msg = self.nsr_last_error()
             raise NsrError(f"{what} failed: {msg.decode() if msg else rc}")
+
+    def call(self, name: str, *args):
+        self.check(getattr(self, name)(*args), name)
 
 
 _lib = None

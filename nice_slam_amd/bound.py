@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from .engine import Engine, c_doubles, c_int32s, gpu, pose_stack, w2c_rows
+from .engine import Engine, c_doubles, c_int32s, gpu, on, pose_stack, w2c_rows
 from .ply import write_ply
 
 UNIT = 16                        # voxels per unit edge (Open3D's volume_unit_resolution)
@@ -66,7 +66,7 @@ def tsdf_fuse(keyframes, H, W, fx, fy, cx, cy, scale=1.0, engine: Optional[Engin
         w2c_d = torch.from_numpy(w2c).to(dev)
         args = (depth.data_ptr(), K, int(H), int(W), c2w_d.data_ptr(), float(fx), float(fy), float(cx), float(cy), vl, trunc)
         box_d = torch.empty(6, dtype=torch.int32, device=dev)
-        lib.check(lib.nsr_tsdf_unit_box(*args, box_d.data_ptr(), E.stream()), "nsr_tsdf_unit_box")
+        E.call("nsr_tsdf_unit_box", *args, box_d.data_ptr())
         box = box_d.cpu().numpy()
         tw = (K + 31) // 32
         if box[3] < box[0]:                                           # no valid depth in any keyframe
@@ -78,18 +78,16 @@ def tsdf_fuse(keyframes, H, W, fx, fy, cx, cy, scale=1.0, engine: Optional[Engin
             raise _capi.NsrError(f"tsdf_fuse: the touched units span {box[3:] - box[:3] + 1} units: more than 2^31")
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
         nu_d = torch.empty(1, dtype=torch.int64, device=dev)
-        lib.check(lib.nsr_tsdf_touch_count(*args, c_int32s(box), ws.data_ptr(), nu_d.data_ptr(), E.stream()), "nsr_tsdf_touch_count")
+        E.call("nsr_tsdf_touch_count", *args, c_int32s(box), ws.data_ptr(), nu_d.data_ptr())
         nu = int(nu_d.cpu()[0])
         units = torch.empty((nu, 3), dtype=torch.int32, device=dev)
         touch = torch.empty((nu, tw), dtype=torch.int32, device=dev)     # uint32 bits (torch has no uint32 arithmetic)
-        lib.check(lib.nsr_tsdf_touch_emit(*args, c_int32s(box), ws.data_ptr(), nu, units.data_ptr(), touch.data_ptr(), E.stream()),
-                  "nsr_tsdf_touch_emit")
+        E.call("nsr_tsdf_touch_emit", *args, c_int32s(box), ws.data_ptr(), nu, units.data_ptr(), touch.data_ptr())
         tick("touch")
         tsdf = torch.empty((nu, UNIT, UNIT, UNIT), dtype=torch.float32, device=dev)
         weight = torch.empty_like(tsdf)
-        lib.check(lib.nsr_tsdf_integrate(depth.data_ptr(), K, int(H), int(W), w2c_d.data_ptr(), float(fx), float(fy), float(cx), float(cy),
-                                         vl, trunc, units.data_ptr(), touch.data_ptr(), nu, tsdf.data_ptr(), weight.data_ptr(), E.stream()),
-                  "nsr_tsdf_integrate")
+        E.call("nsr_tsdf_integrate", depth.data_ptr(), K, int(H), int(W), w2c_d.data_ptr(), float(fx), float(fy), float(cx), float(cy), vl,
+               trunc, units.data_ptr(), touch.data_ptr(), nu, tsdf.data_ptr(), weight.data_ptr())
         tick("integrate")
     return TSDFVolume(E, box, ws, units, touch, tsdf, weight, vl, trunc, cams)
 
@@ -99,19 +97,18 @@ def surface_points(vol: TSDFVolume) -> torch.Tensor:
     every sign-changing voxel edge of a cube whose 8 corners have weight > 0), units in list order, voxels x-slowest, axes
     x, y, z."""
     E = vol.engine
-    lib, dev = E.lib, E.device
+    dev = E.device
     nu = vol.units.shape[0]
     if nu == 0:
         return torch.zeros((0, 3), dtype=torch.float64, device=dev)
     with torch.no_grad(), E.guard():
         counts = torch.empty(nu + 1, dtype=torch.int64, device=dev)
-        lib.check(lib.nsr_tsdf_surface_count(c_int32s(vol.box), vol.workspace.data_ptr(), vol.units.data_ptr(), nu, vol.tsdf.data_ptr(),
-                                             vol.weight.data_ptr(), counts.data_ptr(), E.stream()), "nsr_tsdf_surface_count")
+        E.call("nsr_tsdf_surface_count", c_int32s(vol.box), vol.workspace.data_ptr(), vol.units.data_ptr(), nu, vol.tsdf.data_ptr(),
+               vol.weight.data_ptr(), counts.data_ptr())
         n = int(counts[nu].cpu())
         pts = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        lib.check(lib.nsr_tsdf_surface_emit(c_int32s(vol.box), vol.workspace.data_ptr(), vol.units.data_ptr(), nu, vol.tsdf.data_ptr(),
-                                            vol.weight.data_ptr(), float(vol.voxel_length), counts.data_ptr(), n, pts.data_ptr(),
-                                            E.stream()), "nsr_tsdf_surface_emit")
+        E.call("nsr_tsdf_surface_emit", c_int32s(vol.box), vol.workspace.data_ptr(), vol.units.data_ptr(), nu, vol.tsdf.data_ptr(),
+               vol.weight.data_ptr(), float(vol.voxel_length), counts.data_ptr(), n, pts.data_ptr())
     return pts
 
 
@@ -123,7 +120,7 @@ def convex_hull(points, bound_scale=1.0, tol=None, lib=None):
     """Exact fp64 quickhull of host points [N,3] (nsr_convex_hull), scaled by ``bound_scale`` about the mean of its vertices
     -> (vertices fp64 [V,3], vertex_index int64 [V] into points (ascending), faces int32 [F,3] outward, planes fp64 [F,4]
     (unit normal, offset) of the scaled faces)."""
-    lib = lib or _capi.get_lib()
+    lib = lib or gpu().lib
     p = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
     n = len(p)
     if tol is None:
@@ -133,8 +130,8 @@ def convex_hull(points, bound_scale=1.0, tol=None, lib=None):
     vidx = np.zeros(max(n, 1), np.int64)
     faces = np.zeros((max(2 * n, 1), 3), np.int32)
     planes = np.zeros((max(2 * n, 1), 4), np.float64)
-    lib.check(lib.nsr_convex_hull(p.ctypes, n, float(tol), float(bound_scale), counts.ctypes, verts.ctypes, vidx.ctypes, faces.ctypes,
-                                  planes.ctypes), "nsr_convex_hull")
+    lib.call("nsr_convex_hull", p.ctypes, n, float(tol), float(bound_scale), counts.ctypes, verts.ctypes, vidx.ctypes, faces.ctypes,
+             planes.ctypes)
     nv, nf = int(counts[0]), int(counts[1])
     return verts[:nv].copy(), vidx[:nv].copy(), faces[:nf].copy(), planes[:nf].copy()
 
@@ -151,7 +148,7 @@ def prefilter(points: torch.Tensor, engine: Optional[Engine] = None) -> torch.Te
     with torch.no_grad(), E.guard():
         partial = torch.empty(int(lib.nsr_hull_partial_doubles()), dtype=torch.float64, device=dev)
         ext = torch.empty(26, dtype=torch.int64, device=dev)
-        lib.check(lib.nsr_hull_extremes(pts.data_ptr(), n, partial.data_ptr(), ext.data_ptr(), E.stream()), "nsr_hull_extremes")
+        E.call("nsr_hull_extremes", pts.data_ptr(), n, partial.data_ptr(), ext.data_ptr())
         idx = np.unique(ext.cpu().numpy())
         ep = pts[torch.from_numpy(idx).to(dev)].cpu().numpy()
         try:
@@ -160,8 +157,7 @@ def prefilter(points: torch.Tensor, engine: Optional[Engine] = None) -> torch.Te
             return pts
         margin = PREFILTER_MARGIN_REL * _tol_scale(ep)
         keep = torch.empty(n, dtype=torch.uint8, device=dev)
-        lib.check(lib.nsr_hull_prefilter(pts.data_ptr(), n, c_doubles(planes), planes.shape[0], margin, keep.data_ptr(), E.stream()),
-                  "nsr_hull_prefilter")
+        E.call("nsr_hull_prefilter", pts.data_ptr(), n, c_doubles(planes), planes.shape[0], margin, keep.data_ptr())
     return pts[keep.bool()]
 
 
@@ -189,15 +185,14 @@ class ConvexBound:
         as_np = not isinstance(points, torch.Tensor)
         E = self.engine or gpu()
         if not as_np and points.device.type == E.device.type and points.device != E.device:
-            E = Engine(E.lib, points.device)                          # a tensor on another GPU is tested there
+            E = on(points.device)                                     # a tensor on another GPU is tested there
         t = E.tensor(np.reshape(points, (-1, 3)) if as_np else points.reshape(-1, 3), what="contains: points")
         n = t.shape[0]
         out = torch.empty(n, dtype=torch.uint8, device=E.device)
         if n:
             pl = self._planes_on(E.device)
             with torch.no_grad(), E.guard():
-                E.lib.check(E.lib.nsr_hull_contains(t.data_ptr(), n, int(t.dtype == torch.float64), pl.data_ptr(), pl.shape[0],
-                                                    out.data_ptr(), E.stream()), "nsr_hull_contains")
+                E.call("nsr_hull_contains", t.data_ptr(), n, int(t.dtype == torch.float64), pl.data_ptr(), pl.shape[0], out.data_ptr())
         res = out.bool()
         return res.cpu().numpy() if as_np else res
 

@@ -13,23 +13,12 @@ import numpy as np
 
 import torch
 
-from . import _capi
+from . import _capi, engine
 
 
 def _stream(device) -> int:
-    """HIP stream handle for the next libnsr launch on `device`.  The library launches on the CURRENT device (its kernels
-    carry no device guard): a caller working on tensors of another GPU of the same process (the reference lets tracking and
-    mapping name different devices, configs/nice_slam.yaml:31,44) gets that device made current here, like every torch
-    operator does for the duration of its launch."""
-    device = torch.device(device)
-    idx = device.index
-    cur = torch.cuda.current_device()
-    if idx is not None and idx != cur:
-        # restored by Lib.check(), which every launch site calls right after the library call (`lib.check(lib.nsr_x(...,
-        # _stream(dev)), ...)`): the caller's current device is the same before and after, like around a torch operator
-        if getattr(_capi.restore_device, "idx", None) is None:
-            _capi.restore_device.idx = cur
-        torch.cuda.set_device(idx)
+    """HIP stream handle of `device`'s current stream, for a raw ABI call (the package itself launches through
+    ``engine.on(device).call``, which also makes the device current: the library launches on the CURRENT device)."""
     return torch.cuda.current_stream(device).cuda_stream
 
 
@@ -120,17 +109,15 @@ class _GetSamplesFn(torch.autograd.Function):
 
     @staticmethod
     def run(c2w, indices, depth, color, H0, H1, W0, W1, fx, fy, cx, cy):
-        lib = _capi.get_lib()
         n = indices.shape[0]
         dev = depth.device
         buf = torch.empty((10 * n,), dtype=torch.float32, device=dev)       # one allocation: o | d | depth | colour
         rays_o, rays_d = buf[:3 * n].view(n, 3), buf[3 * n:6 * n].view(n, 3)
         s_depth, s_color = buf[6 * n:7 * n], buf[7 * n:].view(n, 3)
         c2w_c = _as_f32c(c2w.detach(), dev)
-        lib.check(lib.nsr_get_samples(indices.data_ptr(), n, H0, H1, W0, W1, depth.shape[1], fx, fy, cx, cy,
-                                      c2w_c.data_ptr(), c2w_c.stride(0), depth.data_ptr(), color.data_ptr(),
-                                      rays_o.data_ptr(), rays_d.data_ptr(), s_depth.data_ptr(), s_color.data_ptr(),
-                                      _stream(dev)), "nsr_get_samples")
+        engine.on(dev).call("nsr_get_samples", indices.data_ptr(), n, H0, H1, W0, W1, depth.shape[1], fx, fy, cx, cy, c2w_c.data_ptr(),
+                            c2w_c.stride(0), depth.data_ptr(), color.data_ptr(), rays_o.data_ptr(), rays_d.data_ptr(), s_depth.data_ptr(),
+                            s_color.data_ptr())
         return rays_o, rays_d, s_depth, s_color
 
     @staticmethod
@@ -195,19 +182,16 @@ def aabb_keep(rays_o: torch.Tensor, rays_d: torch.Tensor, gt_depth: torch.Tensor
     kmax = torch.zeros((1,), dtype=torch.float32, device=dev)
     lo = (C.c_double * 3)(*[float(bound[a][0]) for a in range(3)])
     hi = (C.c_double * 3)(*[float(bound[a][1]) for a in range(3)])
-    lib = _capi.get_lib()
-    lib.check(lib.nsr_aabb_keep(o.data_ptr(), d.data_ptr(), gd.data_ptr(), n, lo, hi, keep.data_ptr(), kmax.data_ptr(),
-                                _stream(dev)), "nsr_aabb_keep")
+    engine.on(dev).call("nsr_aabb_keep", o.data_ptr(), d.data_ptr(), gd.data_ptr(), n, lo, hi, keep.data_ptr(), kmax.data_ptr())
     return keep.bool(), kmax
 
 
 class _CameraFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cam):
-        lib = _capi.get_lib()
         c = cam.detach().reshape(-1, 7).to(torch.float32).contiguous()
         rt = torch.empty((c.shape[0], 3, 4), dtype=torch.float32, device=c.device)
-        lib.check(lib.nsr_camera_from_tensor(c.data_ptr(), c.shape[0], rt.data_ptr(), None, None, _stream(c.device)), "nsr_camera_from_tensor")
+        engine.on(c.device).call("nsr_camera_from_tensor", c.data_ptr(), c.shape[0], rt.data_ptr(), None, None)
         ctx.save_for_backward(c)
         ctx.meta = (cam.shape, cam.dtype)
         return rt[0] if cam.dim() == 1 else rt
@@ -215,11 +199,10 @@ class _CameraFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _capi.get_lib()
         (c,) = ctx.saved_tensors
         g = g.reshape(-1, 3, 4).to(torch.float32).contiguous()
         d = torch.empty_like(c)
-        lib.check(lib.nsr_camera_from_tensor(c.data_ptr(), c.shape[0], None, g.data_ptr(), d.data_ptr(), _stream(c.device)), "nsr_camera_from_tensor")
+        engine.on(c.device).call("nsr_camera_from_tensor", c.data_ptr(), c.shape[0], None, g.data_ptr(), d.data_ptr())
         shape, dtype = ctx.meta
         return d.reshape(shape).to(dtype)
 

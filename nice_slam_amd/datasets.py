@@ -31,18 +31,13 @@ import numpy as np
 import torch
 
 from . import _capi
-from .engine import Engine
+from .engine import Engine, on
 
 __all__ = ["FramePreparer", "get_dataset", "BaseDataset", "Replica", "ScanNet", "Azure", "CoFusion", "TUM_RGBD", "dataset_dict"]
 
 
 def _engine(engine: Optional[Engine], device=None) -> Engine:
-    if engine is not None:
-        return engine
-    dev = torch.device("cuda:0" if device is None else device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise _capi.NsrError("nice_slam_amd needs the AMD GPU; there is no CPU path")
-    return Engine(_capi.get_lib(), torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device()))
+    return engine if engine is not None else on("cuda:0" if device is None else device)
 
 
 class FramePreparer:
@@ -137,14 +132,14 @@ class FramePreparer:
         B = c.shape[0]
         desc = self.desc(c.shape[1:3], d.shape[1:3], d.dtype == torch.float32, bgr)
         H, W = C.c_int32(), C.c_int32()
-        lib.check(lib.nsr_frame_out_size(C.byref(desc), C.byref(H), C.byref(W)), "nsr_frame_out_size")
+        lib.call("nsr_frame_out_size", C.byref(desc), C.byref(H), C.byref(W))
         color = torch.empty((B, H.value, W.value, 3), dtype=torch.float32, device=E.device)
         depth = torch.empty((B, H.value, W.value), dtype=torch.float32, device=E.device)
         with torch.no_grad(), E.guard():
             nbytes = int(lib.nsr_frame_workspace_bytes(C.byref(desc), B))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device) if nbytes > 0 else None
-            lib.check(lib.nsr_frame_prepare(c.data_ptr(), d.data_ptr(), C.byref(desc), B, color.data_ptr(), depth.data_ptr(),
-                                            ws.data_ptr() if ws is not None else None, max(nbytes, 0), E.stream()), "nsr_frame_prepare")
+            E.call("nsr_frame_prepare", c.data_ptr(), d.data_ptr(), C.byref(desc), B, color.data_ptr(), depth.data_ptr(),
+                   ws.data_ptr() if ws is not None else None, max(nbytes, 0))
         return (color[0], depth[0]) if single else (color, depth)
 
 

@@ -12,7 +12,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
-from . import _capi
+from . import _capi, engine
 from .layout import param_spec
 
 
@@ -116,7 +116,7 @@ class _FlatDecoder(nn.Module):
         # is the tuple of all of them
         return (f.data_ptr(), f.device, f._version, tuple(p._version for p in self._views))
 
-    def packed_params(self, lib, stream) -> torch.Tensor:
+    def packed_params(self, E) -> torch.Tensor:
         f = self.flat_params()
         key = self._pack_key()
         # a decoder shared with other processes (share_memory(), or unpickled into a spawned process: the reference's
@@ -128,8 +128,8 @@ class _FlatDecoder(nn.Module):
             # (the pack launch is then either part of the graph -- parameters stepped inside it -- or issued by the caller
             # between replays: NICE.repack())
             pk = self._packed[1] if (self._packed is not None and self._packed[1].device == f.device) else \
-                torch.empty(lib.nsr_packed_count(slot), dtype=torch.float32, device=f.device)
-            lib.check(lib.nsr_pack_params(slot, f.data_ptr(), pk.data_ptr(), stream), "nsr_pack_params")
+                torch.empty(E.lib.nsr_packed_count(slot), dtype=torch.float32, device=f.device)
+            E.call("nsr_pack_params", slot, f.data_ptr(), pk.data_ptr())
             self._packed = (key, pk)
         return self._packed[1]
 
@@ -277,12 +277,9 @@ class NICE(nn.Module):
         """Refresh the packed operand streams after the parameters were written by something the version counters of this
         process do not see, or between replays of a captured graph that does not contain the pack launch (a tracker-side
         copy refreshed from the mapper's decoders, src/Tracker.py:130-142).  In place: captured graphs stay valid."""
-        from .common import _stream
-        lib = _capi.get_lib()
         for m in self.children():
             if isinstance(m, _FlatDecoder) and m.flat_params().is_cuda:
-                with _capi.on_device(m.flat_params().device):   # (a cached pack makes no library call: nothing else would restore the device)
-                    m.packed_params(lib, _stream(m.flat_params().device))
+                m.packed_params(engine.on(m.flat_params().device))
 
     def share_memory(self):                                  # src/NICE_SLAM.py:88-90
         for m in self.children():

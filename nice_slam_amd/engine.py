@@ -1,9 +1,9 @@
 """Host glue shared by the post-render modules (mesher, recon, bound, raster): the engine that drives libnsr.so on tensors of
 one device, and the small conversions their entry points share (ctypes arrays, meshes, compaction, camera poses).
 
-An ``Engine`` pairs a loaded library with a device.  The product runs the library on the GPU (``gpu()``); the CPU tests
-build an engine on the emulator library (tests/emu/), which takes host pointers, and call the same module functions
-with ``engine=``.
+An ``Engine`` pairs a loaded library with a device, and ``Engine.call`` is how the package runs a library entry: on that
+device, on its current stream.  The product runs the library on the GPU (``on(device)``, ``gpu()``); the CPU tests build an
+engine on the emulator library (tests/emu/), which takes host pointers, and call the same module functions with ``engine=``.
 """
 from __future__ import annotations
 
@@ -14,7 +14,6 @@ import numpy as np
 import torch
 
 from . import _capi
-from .common import _stream
 from .ply import read_mesh
 
 
@@ -24,9 +23,23 @@ class Engine:
     def __init__(self, lib, device):
         self.lib = lib
         self.device = torch.device(device)
+        self.index = self.device.index if self.device.type == "cuda" else None     # None: nothing to switch (the CPU emulator)
 
     def stream(self):
-        return _stream(self.device) if self.device.type == "cuda" else None
+        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
+
+    def call(self, name, *args):
+        """Run the entry point ``name`` on this device: ``args`` plus the device's current stream as the last argument, an error
+        code raised as NsrError.  The library launches on the CURRENT device, so a caller working on tensors of another GPU of
+        the process (the reference lets tracking and mapping name different devices, configs/nice_slam.yaml:31,44) gets the
+        engine's made current for the call and its own back afterwards, exceptions included, like around a torch operator."""
+        if self.index is None:
+            self.lib.call(name, *args, self.stream())
+        elif self.index == torch.cuda.current_device():
+            self.lib.call(name, *args, torch.cuda.current_stream(self.device).cuda_stream)
+        else:
+            with self.guard():
+                self.lib.call(name, *args, torch.cuda.current_stream(self.device).cuda_stream)
 
     def guard(self):
         return _capi.on_device(self.device if self.device.type == "cuda" else None)
@@ -56,21 +69,33 @@ class Engine:
 
     def transform(self, pts: torch.Tensor, T):
         """pts fp64 [N, 3] on this device := R pts + t in place, (R | t) the top 3 x 4 of the pose T (nsr_transform_points)."""
-        with self.guard():
-            self.lib.check(self.lib.nsr_transform_points(pts.data_ptr(), pts.shape[0], c_doubles(np.asarray(T, np.float64)[:3, :4]),
-                                                         self.stream()), "nsr_transform_points")
+        self.call("nsr_transform_points", pts.data_ptr(), pts.shape[0], c_doubles(np.asarray(T, np.float64)[:3, :4]))
 
 
+_engines = {}
 _gpu_engine = None
 
 
+def on(device) -> Engine:
+    """The product's engine of a CUDA device: libnsr.so there, one Engine per device ("cuda" without an index: the current one)."""
+    E = _engines.get(device)
+    if E is None:
+        device = torch.device(device)
+        if device.type != "cuda" or not torch.cuda.is_available():
+            raise _capi.NsrError(f"nice_slam_amd needs the AMD GPU (got {device}); there is no CPU path")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        E = _engines.get(device)
+        if E is None:
+            E = _engines[device] = Engine(_capi.get_lib(), device)
+    return E
+
+
 def gpu() -> Engine:
-    """The product's engine: libnsr.so on the device current at the first call."""
+    """The product's engine on the device current at the first call."""
     global _gpu_engine
     if _gpu_engine is None:
-        if not torch.cuda.is_available():
-            raise _capi.NsrError("nice_slam_amd needs the AMD GPU; there is no CPU path")
-        _gpu_engine = Engine(_capi.get_lib(), torch.device("cuda", torch.cuda.current_device()))
+        _gpu_engine = on("cuda")
     return _gpu_engine
 
 

@@ -13,8 +13,8 @@ from typing import Dict, Tuple
 import numpy as np
 import torch
 
-from . import _capi
-from .common import _require_cuda, _stream
+from . import _capi, engine
+from .common import _require_cuda
 
 
 class FrustumSelector:
@@ -54,15 +54,14 @@ class FrustumSelector:
         w2c = np.ascontiguousarray(np.linalg.inv(c2w)[:3], dtype=np.float32)         # Mapper.py:119-120
         o = np.ascontiguousarray(c2w[:3, 3], dtype=np.float32)
         ax = self._voxel_axes((nz, ny, nx), dev)
-        lib = _capi.get_lib()
+        E = engine.on(dev)
         n = nx * ny * nz
-        ws = torch.empty((lib.nsr_frustum_workspace_floats(n),), dtype=torch.float32, device=dev)
+        ws = torch.empty((E.lib.nsr_frustum_workspace_floats(n),), dtype=torch.float32, device=dev)
         mask = torch.empty((nz, ny, nx), dtype=torch.uint8, device=dev)
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
         p0 = ax.data_ptr()
-        lib.check(lib.nsr_frustum_mask(fp(w2c), fp(o), self.fx, self.fy, self.cx, self.cy, self.H, self.W, depth.data_ptr(),
-                                       p0, p0 + 4 * nx, p0 + 4 * (nx + ny), nx, ny, nz, ws.data_ptr(), mask.data_ptr(),
-                                       _stream(dev)), "nsr_frustum_mask")
+        E.call("nsr_frustum_mask", fp(w2c), fp(o), self.fx, self.fy, self.cx, self.cy, self.H, self.W, depth.data_ptr(), p0, p0 + 4 * nx,
+               p0 + 4 * (nx + ny), nx, ny, nz, ws.data_ptr(), mask.data_ptr())
         return mask
 
     def get_mask_from_c2w(self, c2w, key: str, val_shape, depth: torch.Tensor) -> torch.Tensor:

@@ -84,10 +84,9 @@ def image_metrics(color, gt_color, depth, gt_depth, residuals: bool = False, eng
                 raise _capi.NsrError(f"image_metrics: unsupported sizes ({kb} frames of {H} x {W})")
             ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=E.device)
             sl = slice(k0, k0 + kb)
-            lib.check(lib.nsr_image_metrics(a[sl].data_ptr(), b[sl].data_ptr(), d[sl].data_ptr(), g[sl].data_ptr(), kb, H, W,
-                                            res[sl].data_ptr(), dres[sl].data_ptr() if residuals else None,
-                                            cres[sl].data_ptr() if residuals else None, ws.data_ptr(), nbytes, E.stream()),
-                      "nsr_image_metrics")
+            E.call("nsr_image_metrics", a[sl].data_ptr(), b[sl].data_ptr(), d[sl].data_ptr(), g[sl].data_ptr(), kb, H, W,
+                   res[sl].data_ptr(), dres[sl].data_ptr() if residuals else None, cres[sl].data_ptr() if residuals else None,
+                   ws.data_ptr(), nbytes)
     se_all, n_all, se_valid, n_valid, ssim, l1, dmax = (res[:, i] for i in range(7))
     out = {"psnr": -10.0 * torch.log10(se_all / (3.0 * n_all)),
            "psnr_valid": -10.0 * torch.log10(se_valid / (3.0 * n_valid)),        # 0 / 0: NaN for a frame without valid depth

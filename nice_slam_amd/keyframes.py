@@ -22,8 +22,8 @@ from typing import Dict, List, Sequence
 import numpy as np
 import torch
 
-from . import _capi
-from .common import _require_cuda, _stream
+from . import _capi, engine
+from .common import _require_cuda
 from .engine import w2c_rows
 
 EDGE = 20                                          # Mapper.py:213
@@ -128,12 +128,9 @@ class KeyframeSelector:
         depth = gt_depth.detach().to(torch.float32).contiguous()
         w2c_dev = torch.from_numpy(w2c).to(dev)
         tv = self._t_vals(int(N_samples))
-        lib = _capi.get_lib()
-        lib.check(lib.nsr_keyframe_overlap(indices.data_ptr(), int(indices.shape[0]), int(N_samples),
-                                           tv.ctypes.data_as(C.POINTER(C.c_float)), self.H, self.W,
-                                           self.fx, self.fy, self.cx, self.cy, EDGE, c2w.data_ptr(), c2w.stride(0),
-                                           depth.data_ptr(), w2c_dev.data_ptr(), K, counts.data_ptr(), _stream(dev)),
-                  "nsr_keyframe_overlap")
+        engine.on(dev).call("nsr_keyframe_overlap", indices.data_ptr(), int(indices.shape[0]), int(N_samples),
+                            tv.ctypes.data_as(C.POINTER(C.c_float)), self.H, self.W, self.fx, self.fy, self.cx, self.cy, EDGE,
+                            c2w.data_ptr(), c2w.stride(0), depth.data_ptr(), w2c_dev.data_ptr(), K, counts.data_ptr())
         return counts
 
     def keyframe_selection_overlap(self, gt_color, gt_depth, c2w, keyframe_dict, k, N_samples=16, pixels=100) -> list:

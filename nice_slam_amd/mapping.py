@@ -22,8 +22,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _capi
-from .common import _as_f32c, _require_cuda, _stream
+from . import _capi, engine
+from .common import _as_f32c, _require_cuda
 from .layout import param_count, stage_slots
 from .renderer import RenderCall, _bound6, _gates, _prep_grids, forward_args, render_backward
 
@@ -157,29 +157,26 @@ def _launch_window(win: _Window, frames, rays, kmax_ptr, fused=None):
     """One of the four window kernels over the sampled-ray views ``rays`` (``_ray_buffer``).  ``fused``: None, or (header tensor [4]
     fp32, zero span tensor) of a fused iteration -- the launch then also zero-fills the span and writes the header {loss = 0 (fp64),
     kept max, 0} itself (nsr_get_samples_window_fused): no fill launch before it."""
-    lib = _capi.get_lib()
+    E = engine.on(win.dev)
     o, d, gd, gc, keep = rays
     common = (win.K, win.n, *win.crop, *win.intr, frames, o.data_ptr(), d.data_ptr(), gd.data_ptr(), gc.data_ptr(),
               *_bound_arrays(win.bound), keep.data_ptr())
     draw, win.draw = win.draw, False                         # a kernel draw is used once: the pixels are in `indices` from now on
     state = (win.state if win.state is not None else _draw_state(win.dev)) if (draw or fused is not None) else None
     ind = win.indices.data_ptr()
-    stream = _stream(win.dev)
     if fused is None and draw:                               # drawn by the kernel, written to `indices` for the backward / the caller
-        lib.check(lib.nsr_get_samples_window_draw(ind, state.data_ptr(), *common, kmax_ptr, stream), "nsr_get_samples_window_draw")
+        E.call("nsr_get_samples_window_draw", ind, state.data_ptr(), *common, kmax_ptr)
     elif fused is None:
-        lib.check(lib.nsr_get_samples_window(ind, *common, kmax_ptr, stream), "nsr_get_samples_window")
+        E.call("nsr_get_samples_window", ind, *common, kmax_ptr)
     else:
         hdr, zero = fused
-        tail = (hdr.data_ptr(), zero.data_ptr() if zero.numel() else None, zero.numel(), stream)
+        tail = (hdr.data_ptr(), zero.data_ptr() if zero.numel() else None, zero.numel())
         if win.peers and draw:
             # one rank of a ray-sharded iteration: the other ranks' draws are repeated for the batch-global depth cap (no collective)
             seeds = (C.c_uint64 * len(win.peers))(*[int(v) for v in win.peers])
-            lib.check(lib.nsr_get_samples_window_sharded(ind, state.data_ptr(), seeds, len(win.peers), *common, *tail),
-                      "nsr_get_samples_window_sharded")
+            E.call("nsr_get_samples_window_sharded", ind, state.data_ptr(), seeds, len(win.peers), *common, *tail)
         else:
-            lib.check(lib.nsr_get_samples_window_fused(None if draw else ind, ind if draw else None, state.data_ptr(), *common, *tail),
-                      "nsr_get_samples_window_fused")
+            E.call("nsr_get_samples_window_fused", None if draw else ind, ind if draw else None, state.data_ptr(), *common, *tail)
 
 
 class _WindowFn(torch.autograd.Function):
@@ -206,13 +203,12 @@ class _WindowFn(torch.autograd.Function):
 def pose_grads(win: _Window, g_o, g_d, out=None) -> List[torch.Tensor]:
     """d c2w[k] (shape of the pose, rows 0..2 filled) from the gradients of the window's rays: one launch.  ``out``: an already
     zero-filled [K, 4, 4] fp32 tensor (the fused iteration's one zero-filled buffer has room for it), else allocated here."""
-    lib = _capi.get_lib()
     dev = g_o.device
     H0, H1, W0, W1, _ = win.crop
     if out is None:
         out = torch.zeros((win.K, 4, 4), dtype=torch.float32, device=dev)
-    lib.check(lib.nsr_pose_grad(win.indices.data_ptr(), win.K, win.n, H0, H1, W0, W1, *win.intr, g_o.data_ptr(), g_d.data_ptr(),
-                                out.data_ptr(), 16, _stream(dev)), "nsr_pose_grad")
+    engine.on(dev).call("nsr_pose_grad", win.indices.data_ptr(), win.K, win.n, H0, H1, W0, W1, *win.intr, g_o.data_ptr(), g_d.data_ptr(),
+                        out.data_ptr(), 16)
     return [out[k, :c.shape[0], :] for k, c in enumerate(win.c2ws)], out
 
 
@@ -253,10 +249,9 @@ class _MappingLossFn(torch.autograd.Function):
     def _forward_impl(ctx, renderer, decoders, stage, win, w_color, sharder, out, track, *tensors):
         # track: None | (handle_dynamic, use_color)
         K, N, dev = win.K, win.K * win.n, win.dev
-        lib = _capi.get_lib()
+        E = engine.on(dev)
         slots = stage_slots(stage)
         grids = dict(zip(slots, tensors[K:]))
-        stream = _stream(dev)
         guided = stage != "coarse"
         S = renderer.N_samples + (renderer.N_surface if guided else 0)
         need = ctx.needs_input_grad[8:]
@@ -318,11 +313,10 @@ class _MappingLossFn(torch.autograd.Function):
         if need_bwd and acts is None:
             raise _capi.NsrError("nice_slam_amd: the activation buffer of a %d-ray fused iteration does not fit (Renderer."
                                  "max_saved_activation_bytes / free device memory); use smaller batches or render_batch_ray" % N)
-        lib.check(lib.nsr_render_fwd(C.byref(a), stream), "nsr_render_fwd")
+        E.call("nsr_render_fwd", C.byref(a))
         if track is not None:                                   # the tracker's loss needs the batch median of the rendered outputs
-            lib.check(lib.nsr_tracking_loss(N, gt_depth.data_ptr(), gt_color.data_ptr(), keep.data_ptr(), depth.data_ptr(), var.data_ptr(),
-                                            rgb.data_ptr(), int(track[0]), int(track[1]), float(w_color), loss.data_ptr(),
-                                            dl_depth.data_ptr(), dl_rgb.data_ptr(), stream), "nsr_tracking_loss")
+            E.call("nsr_tracking_loss", N, gt_depth.data_ptr(), gt_color.data_ptr(), keep.data_ptr(), depth.data_ptr(), var.data_ptr(),
+                   rgb.data_ptr(), int(track[0]), int(track[1]), float(w_color), loss.data_ptr(), dl_depth.data_ptr(), dl_rgb.data_ptr())
         if out is not None:
             out.update(rays_o=rays_o, rays_d=rays_d, gt_depth=gt_depth, gt_color=gt_color, keep=keep, kept_max=kmax, depth=depth,
                        uncertainty=var, color=rgb, indices=win.indices)

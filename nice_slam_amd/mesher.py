@@ -28,7 +28,7 @@ import torch
 from . import _capi
 from .bound import ConvexBound, bound_from_frames
 from .common import _require_cuda
-from .engine import Engine, c_doubles, compact, w2c_rows
+from .engine import Engine, c_doubles, compact, on, w2c_rows
 from .ply import read_mesh, write_ply
 from .renderer import eval_points_raw
 
@@ -38,7 +38,7 @@ def _engine(engine: Optional[Engine], t: torch.Tensor, what: str) -> Engine:
     if engine is not None:
         return engine
     _require_cuda(t, what)
-    return Engine(_capi.get_lib(), t.device)
+    return on(t.device)
 
 
 def marching_cubes(volume: torch.Tensor, level: float = 0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0),
@@ -58,12 +58,12 @@ def marching_cubes(volume: torch.Tensor, level: float = 0.0, spacing=(1.0, 1.0, 
             raise _capi.NsrError(f"marching_cubes: lattice {tuple(vol.shape)} not supported (every dimension >= 2, <= 2^31 points)")
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
-        lib.check(lib.nsr_mc_count(vol.data_ptr(), nx, ny, nz, float(level), ws.data_ptr(), counts.data_ptr(), E.stream()), "nsr_mc_count")
+        E.call("nsr_mc_count", vol.data_ptr(), nx, ny, nz, float(level), ws.data_ptr(), counts.data_ptr())
         n_v, n_f = (int(x) for x in counts.cpu())
         verts = torch.empty((n_v, 3), dtype=torch.float64, device=dev)
         faces = torch.empty((n_f, 3), dtype=torch.int32, device=dev)
-        lib.check(lib.nsr_mc_emit(vol.data_ptr(), nx, ny, nz, float(level), c_doubles(origin, 3), c_doubles(spacing, 3), ws.data_ptr(),
-                                  n_v, n_f, verts.data_ptr(), faces.data_ptr(), E.stream()), "nsr_mc_emit")
+        E.call("nsr_mc_emit", vol.data_ptr(), nx, ny, nz, float(level), c_doubles(origin, 3), c_doubles(spacing, 3), ws.data_ptr(), n_v,
+               n_f, verts.data_ptr(), faces.data_ptr())
     return verts, faces
 
 
@@ -87,10 +87,9 @@ def point_masks_raw(points: torch.Tensor, c2ws, depths, H, W, fx, fy, cx, cy, mo
     elif mode == 1 and K:
         limit = torch.stack([torch.max(d.detach().to(dev, torch.float32)) * 1.1 for d in depths]).contiguous()   # :179
     with E.guard():
-        lib.check(lib.nsr_point_masks(pts.data_ptr(), n, int(chunk), int(mode), K, w2c_d.data_ptr(),
-                                      None if depth is None else depth.data_ptr(), None if limit is None else limit.data_ptr(),
-                                      int(H), int(W), float(fx), float(fy), float(cx), float(cy),
-                                      None if ws is None else ws.data_ptr(), out.data_ptr(), E.stream()), "nsr_point_masks")
+        E.call("nsr_point_masks", pts.data_ptr(), n, int(chunk), int(mode), K, w2c_d.data_ptr(),
+               None if depth is None else depth.data_ptr(), None if limit is None else limit.data_ptr(), int(H), int(W), float(fx),
+               float(fy), float(cx), float(cy), None if ws is None else ws.data_ptr(), out.data_ptr())
     return out
 
 
@@ -116,23 +115,22 @@ def face_components(verts: torch.Tensor, faces: torch.Tensor, engine: Optional[E
         z = torch.zeros(0, dtype=torch.int64, device=faces.device)
         return z, torch.zeros(0, dtype=torch.float64, device=faces.device), z, z
     E = _engine(engine, faces, "face_components: faces")
-    lib, dev = E.lib, E.device
+    dev = E.device
     vv = verts.detach().to(dev, torch.float64).contiguous()
     ff = faces.to(dev, torch.int32).contiguous()
     pairs = face_adjacency(ff, vv.shape[0])
     parent = torch.empty(F, dtype=torch.int32, device=dev)
     changed = torch.empty(1, dtype=torch.int32, device=dev)
     with E.guard():
-        lib.check(lib.nsr_cc_init(F, parent.data_ptr(), changed.data_ptr(), E.stream()), "nsr_cc_init")
+        E.call("nsr_cc_init", F, parent.data_ptr(), changed.data_ptr())
         r = 0
         while True:
-            lib.check(lib.nsr_cc_round(pairs.data_ptr(), pairs.shape[0], F, parent.data_ptr(), changed.data_ptr(), r, E.stream()),
-                      "nsr_cc_round")
+            E.call("nsr_cc_round", pairs.data_ptr(), pairs.shape[0], F, parent.data_ptr(), changed.data_ptr(), r)
             if int(changed.item()) != r + 1:
                 break
             r += 1
         area = torch.empty(F, dtype=torch.float64, device=dev)
-        lib.check(lib.nsr_face_areas(vv.data_ptr(), ff.data_ptr(), F, area.data_ptr(), E.stream()), "nsr_face_areas")
+        E.call("nsr_face_areas", vv.data_ptr(), ff.data_ptr(), F, area.data_ptr())
         label = parent.long()
         ls, order = torch.sort(label, stable=True)
         start = torch.ones(F, dtype=torch.bool, device=dev)
@@ -142,8 +140,8 @@ def face_components(verts: torch.Tensor, faces: torch.Tensor, engine: Optional[E
         comp_area = torch.empty(n_seg, dtype=torch.float64, device=dev)
         order, ls = order.contiguous(), ls.contiguous()
         partial = torch.empty(F, dtype=torch.float64, device=dev)
-        lib.check(lib.nsr_segment_sums(area.data_ptr(), order.data_ptr(), ls.data_ptr(), F, seg.data_ptr(), n_seg, partial.data_ptr(),
-                                       comp_area.data_ptr(), E.stream()), "nsr_segment_sums")
+        E.call("nsr_segment_sums", area.data_ptr(), order.data_ptr(), ls.data_ptr(), F, seg.data_ptr(), n_seg, partial.data_ptr(),
+               comp_area.data_ptr())
     comp_of = torch.empty(F, dtype=torch.int64, device=dev)
     comp_of[order] = torch.cumsum(start.long(), 0) - 1
     first = order[seg[:-1]]

@@ -12,8 +12,8 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _capi
-from .common import _require_cuda, _stream, to_channels_last
+from . import _capi, engine
+from .common import _require_cuda, to_channels_last
 
 
 class MaskedGridAdam:
@@ -79,7 +79,6 @@ class MaskedGridAdam:
             self.reset_state()
 
     def _step_multi(self, lrs, grads, zero_grad):
-        lib = _capi.get_lib()
         keys = list(self.grids)
         dev = self.grids[keys[0]].device
         if self._dev_steps is None:
@@ -104,8 +103,8 @@ class MaskedGridAdam:
                 arr[j].n_voxels = g.shape[2] * g.shape[3] * g.shape[4]
                 arr[j].step = self._dev_steps.data_ptr() + 4 * i
                 arr[j].lr = float(lrs.get(k, 0.0))
-            lib.check(lib.nsr_masked_adam_multi(arr, len(part), self.betas[0], self.betas[1], self.eps, 1 if zero_grad else 0,
-                                                self._scratch.data_ptr(), _stream(dev)), "nsr_masked_adam_multi")
+            engine.on(dev).call("nsr_masked_adam_multi", arr, len(part), self.betas[0], self.betas[1], self.eps, 1 if zero_grad else 0,
+                                self._scratch.data_ptr())
 
     def step(self, lrs: Dict[str, float], grads: Optional[Dict[str, Optional[torch.Tensor]]] = None, zero_grad: bool = False):
         """One Adam step for every grid that has a gradient (``grads[key]`` or ``grid.grad``); grids without one are
@@ -113,7 +112,6 @@ class MaskedGridAdam:
         also clear the gradient of the voxels that were updated."""
         if self.capturable:
             return self._step_multi(lrs, grads, zero_grad)
-        lib = _capi.get_lib()
         b1, b2 = self.betas
         for k, g in self.grids.items():
             grad = (grads or {}).get(k) if grads is not None else g.grad
@@ -125,10 +123,9 @@ class MaskedGridAdam:
             t = st["step"]
             mask = self.masks[k]
             n_vox = g.shape[2] * g.shape[3] * g.shape[4]
-            lib.check(lib.nsr_masked_adam(g.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                                          None if mask is None else mask.data_ptr(), n_vox,
-                                          float(lrs.get(k, 0.0)) / (1.0 - b1 ** t), b1, b2, self.eps, (1.0 - b2 ** t) ** 0.5,
-                                          _stream(g.device)), "nsr_masked_adam")
+            engine.on(g.device).call("nsr_masked_adam", g.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(),
+                                     st["exp_avg_sq"].data_ptr(), None if mask is None else mask.data_ptr(), n_vox,
+                                     float(lrs.get(k, 0.0)) / (1.0 - b1 ** t), b1, b2, self.eps, (1.0 - b2 ** t) ** 0.5)
 
 
 class FlatAdam:
@@ -194,7 +191,6 @@ class FlatAdam:
         return torch.cat([g.reshape(-1) for g in gs])
 
     def step(self, lr=None, zero_grad: bool = False):
-        lib = _capi.get_lib()
         lrs = self.lr if lr is None else self._lrs(lr)
         arr = (_capi.NsrAdamSpan * len(self.entries))()
         hold, n = [], 0
@@ -229,9 +225,8 @@ class FlatAdam:
             if self._is_dec[i]:
                 e.mark_dirty()                       # the packed operand streams are re-packed before the next render
         if n:
-            with _capi.on_device(dev):
-                lib.check(lib.nsr_flat_adam(arr, n, self.betas[0], self.betas[1], self.eps, 1 if zero_grad else 0,
-                                            self._scratch.data_ptr(), _stream(dev)), "nsr_flat_adam")
+            engine.on(dev).call("nsr_flat_adam", arr, n, self.betas[0], self.betas[1], self.eps, 1 if zero_grad else 0,
+                                self._scratch.data_ptr())
             if zero_grad and foreign:                # the kernel cleared the concatenated COPY: clear what the caller holds
                 torch._foreach_zero_(foreign)
 

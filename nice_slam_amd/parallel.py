@@ -325,11 +325,9 @@ class ShardedMapping:
         unless ``split_exchange`` is set (and the iteration qualifies, see ``finish_exchange``): then this call only PACKS, and the
         caller runs the collective and the scatter after ``backward()`` has returned."""
         from . import _capi
-        from .common import _stream
         gflat, publish = self._pending if self._pending is not None else (None, None)
         self._pending = None
         self._deferred = None                 # (a record of an earlier split iteration -- e.g. one a graph segment keeps -- is not THIS backward's)
-        lib = _capi.get_lib()
         dev = loss32.device
         leafs, self._leafs = self._leafs, None
         split = self.split_exchange and pose_base is None and leafs is not None and \
@@ -353,19 +351,19 @@ class ShardedMapping:
         rec = {"keys": keys, "rows": [r for _, r in rows_of], "spans": spans, "buf": buf, "dense": dense, "publish": publish,
                "leafs": leafs if split else None, "loss32": loss32, "dev": dev}
         with _capi.on_device(dev):                               # two launches + a collective on the gradients' device
-            self._pack_rows(lib, rec, [g for g, _ in rows_of], 0, _stream(dev))
+            self._pack_rows(rec, [g for g, _ in rows_of], 0)
             if split:
                 # the kernels up to here and the scatter behind the collective can be two captured graph segments with the
                 # collective eager between them (bench.py NSR_DIST_GRAPH=segments): finish_exchange() = reduce_deferred() + scatter_deferred()
                 self._deferred = rec
                 return
             self._reduce(rec, [g for _, g in dense])
-            self._pack_rows(lib, rec, [g for g, _ in rows_of], 1, _stream(dev))
+            self._pack_rows(rec, [g for g, _ in rows_of], 1)
         self._finish(rec)
 
     @staticmethod
-    def _pack_rows(lib, rec, grid_tensors, mode, stream):
-        from . import _capi
+    def _pack_rows(rec, grid_tensors, mode):
+        from . import _capi, engine
         ng = len(grid_tensors)
         rows_arr = (_capi.NsrRows * max(1, ng))()
         for i, (g, rows) in enumerate(zip(grid_tensors, rec["rows"])):
@@ -373,7 +371,7 @@ class ShardedMapping:
         span_arr = (_capi.NsrSpan * len(rec["spans"]))()
         for i, t in enumerate(rec["spans"]):
             span_arr[i].ptr, span_arr[i].n = t.data_ptr(), t.numel()
-        lib.check(lib.nsr_pack_rows(rows_arr, ng, span_arr, len(rec["spans"]), rec["buf"].data_ptr(), mode, stream), "nsr_pack_rows")
+        engine.on(rec["dev"]).call("nsr_pack_rows", rows_arr, ng, span_arr, len(rec["spans"]), rec["buf"].data_ptr(), mode)
 
     def _reduce(self, rec, dense_tensors):
         self.sum_collectives += 1
@@ -417,13 +415,10 @@ class ShardedMapping:
             self._reduce(rec, self._grad_targets(rec, [k for k, _ in rec["dense"]]))
 
     def scatter_deferred(self, rec=None):
-        from . import _capi
-        from .common import _stream
         rec = rec if rec is not None else self._deferred
         if rec is None:
             return
-        with _capi.on_device(rec["dev"]):
-            self._pack_rows(_capi.get_lib(), rec, self._grad_targets(rec, rec["keys"]), 1, _stream(rec["dev"]))
+        self._pack_rows(rec, self._grad_targets(rec, rec["keys"]), 1)
         self._finish(rec)
 
     def finish_exchange(self):

@@ -36,8 +36,7 @@ def get_tensor_from_camera(RT, Tquad: bool = False, engine: Optional[Engine] = N
     rt = _f32(E, src).reshape(-1, src.shape[-2] * 4)
     cam = torch.empty((rt.shape[0], 7), dtype=torch.float32, device=E.device)
     with E.guard():
-        E.lib.check(E.lib.nsr_tensor_from_camera(rt.data_ptr(), rt.shape[0], rt.shape[1], cam.data_ptr(), E.stream()),
-                    "nsr_tensor_from_camera")
+        E.call("nsr_tensor_from_camera", rt.data_ptr(), rt.shape[0], rt.shape[1], cam.data_ptr())
     if Tquad:
         cam = torch.cat([cam[:, 4:], cam[:, :4]], 1)
     cam = cam[0] if src.dim() == 2 else cam
@@ -85,8 +84,7 @@ class Trajectory:
         E = self.E
         self._cam(cam)
         with torch.no_grad(), E.guard():
-            E.lib.check(E.lib.nsr_pose_predict(self.est.data_ptr(), self.n, self.idx.data_ptr(), 1 if const_speed else 0,
-                                               cam.data_ptr(), E.stream()), "nsr_pose_predict")
+            E.call("nsr_pose_predict", self.est.data_ptr(), self.n, self.idx.data_ptr(), 1 if const_speed else 0, cam.data_ptr())
 
     def commit(self, hist: torch.Tensor, best: Optional[torch.Tensor] = None):
         """est[idx] := the pose of the row of ``hist`` [n_iters, 8] (loss | cam) with the smallest loss (src/Tracker.py:224,
@@ -97,8 +95,8 @@ class Trajectory:
         if best is not None and (best.dtype is not torch.float32 or best.numel() != 8 or not best.is_contiguous() or best.device != E.device):
             raise _capi.NsrError("Trajectory.commit: best is contiguous fp32 [8] on the trajectory's device")
         with torch.no_grad(), E.guard():
-            E.lib.check(E.lib.nsr_pose_commit(hist.data_ptr(), hist.shape[0], self.est.data_ptr(), self.n, self.idx.data_ptr(),
-                                              best.data_ptr() if best is not None else None, E.stream()), "nsr_pose_commit")
+            E.call("nsr_pose_commit", hist.data_ptr(), hist.shape[0], self.est.data_ptr(), self.n, self.idx.data_ptr(),
+                   best.data_ptr() if best is not None else None)
 
     def store(self, cams: torch.Tensor, index: torch.Tensor, dst: Optional[torch.Tensor] = None):
         """dst[index[i]] := the 4x4 pose of cams[i] (src/Mapper.py:527-541); ``dst``: a [K,4,4] fp32 pose table on the
@@ -111,5 +109,4 @@ class Trajectory:
         if dst.dtype is not torch.float32 or dst.dim() != 3 or tuple(dst.shape[1:]) != (4, 4) or not dst.is_contiguous() or dst.device != E.device:
             raise _capi.NsrError("Trajectory.store: dst is contiguous fp32 [K, 4, 4] on the trajectory's device")
         with torch.no_grad(), E.guard():
-            E.lib.check(E.lib.nsr_pose_store(cams.data_ptr(), cams.shape[0], index.data_ptr(), dst.data_ptr(), dst.shape[0],
-                                             E.stream()), "nsr_pose_store")
+            E.call("nsr_pose_store", cams.data_ptr(), cams.shape[0], index.data_ptr(), dst.data_ptr(), dst.shape[0])

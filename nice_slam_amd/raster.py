@@ -113,12 +113,11 @@ def render_depth(vertices, faces, c2w, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_
             ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)
             n_ent = torch.zeros(1, dtype=torch.int64, device=E.device)
             wk = w2c[k0:k0 + kb]
-            lib.check(lib.nsr_raster_bin(v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), n_ent.data_ptr(),
-                                         E.stream()), "nsr_raster_bin")
+            E.call("nsr_raster_bin", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), n_ent.data_ptr())
             n = int(n_ent.item())
             bins = torch.empty(max(n, 1), dtype=torch.int32, device=E.device)
-            lib.check(lib.nsr_raster_depth(v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), bins.data_ptr(), n,
-                                           out[k0:k0 + kb].data_ptr(), E.stream()), "nsr_raster_depth")
+            E.call("nsr_raster_depth", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), bins.data_ptr(), n,
+                   out[k0:k0 + kb].data_ptr())
     return out
 
 
@@ -136,7 +135,7 @@ def depth_l1(a: torch.Tensor, b: torch.Tensor, engine: Optional[Engine] = None) 
     out = torch.empty(K, dtype=torch.float64, device=E.device)
     partial = torch.empty(int(lib.nsr_depth_error_partial_doubles(K, n)), dtype=torch.float64, device=E.device)
     with torch.no_grad(), E.guard():
-        lib.check(lib.nsr_depth_error(a.data_ptr(), b.data_ptr(), K, n, partial.data_ptr(), out.data_ptr(), E.stream()), "nsr_depth_error")
+        E.call("nsr_depth_error", a.data_ptr(), b.data_ptr(), K, n, partial.data_ptr(), out.data_ptr())
     return out
 
 
@@ -284,9 +283,8 @@ def views_unseen(c2w, unseen, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_REF, cx=2
     pts = E.tensor(unseen, what="unseen points")
     sees = torch.empty(len(c2w), dtype=torch.uint8, device=E.device)
     with torch.no_grad(), E.guard():
-        E.lib.check(E.lib.nsr_view_unseen(pts.data_ptr(), pts.shape[0], int(pts.dtype == torch.float64), w2c.data_ptr(), len(c2w), int(H),
-                                          int(W), float(fx), float(fy), float(cx), float(cy), sees.data_ptr(), E.stream()),
-                    "nsr_view_unseen")
+        E.call("nsr_view_unseen", pts.data_ptr(), pts.shape[0], int(pts.dtype == torch.float64), w2c.data_ptr(), len(c2w), int(H), int(W),
+               float(fx), float(fy), float(cx), float(cy), sees.data_ptr())
     return sees.cpu().numpy().astype(bool)
 
 
@@ -414,17 +412,15 @@ def visibility_counts(points, vertices, faces, c2w, H, W, fx, fy, cx, cy, eps=EP
         for k0 in range(0, K, step):
             kb = min(step, K - k0)
             wk = w2c[k0:k0 + kb]
-            lib.check(lib.nsr_raster_bin(v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), n_ent.data_ptr(),
-                                         E.stream()), "nsr_raster_bin")
+            E.call("nsr_raster_bin", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), n_ent.data_ptr())
             n = int(n_ent.item())
             if n > bins.numel():
                 del bins
                 bins = torch.empty(n + n // 4, dtype=torch.int32, device=E.device)
-            lib.check(lib.nsr_raster_depth(v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), bins.data_ptr(), n,
-                                           depth.data_ptr(), E.stream()), "nsr_raster_depth")
-            lib.check(lib.nsr_points_visible(pts.data_ptr(), N, int(pts.dtype == torch.float64), wk.data_ptr(), kb, depth.data_ptr(),
-                                             Hs, Ws, fxs, fys, cxs, cys, float(near), float(far), float(eps), count.data_ptr(),
-                                             E.stream()), "nsr_points_visible")
+            E.call("nsr_raster_depth", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), bins.data_ptr(), n,
+                   depth.data_ptr())
+            E.call("nsr_points_visible", pts.data_ptr(), N, int(pts.dtype == torch.float64), wk.data_ptr(), kb, depth.data_ptr(), Hs, Ws,
+                   fxs, fys, cxs, cys, float(near), float(far), float(eps), count.data_ptr())
     return count
 
 

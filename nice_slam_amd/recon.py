@@ -66,22 +66,21 @@ class NNIndex:
         self.fp64 = int(r.dtype == torch.float64)
         with torch.no_grad(), E.guard():
             bounds = torch.empty(6 * 257, dtype=torch.float64, device=E.device)
-            lib.check(lib.nsr_nn_bounds(r.data_ptr(), M, self.fp64, bounds.data_ptr(), E.stream()), "nsr_nn_bounds")
+            E.call("nsr_nn_bounds", r.data_ptr(), M, self.fp64, bounds.data_ptr())
             b = bounds[:6].cpu().numpy()
             self.plan = (C.c_double * 16)()
-            lib.check(lib.nsr_nn_plan(c_doubles(b), M, self.plan), "nsr_nn_plan")
+            lib.call("nsr_nn_plan", c_doubles(b), M, self.plan)
             nbytes = lib.nsr_nn_workspace_bytes(self.plan, M)
             if nbytes < 0:
                 raise _capi.NsrError("nearest: invalid grid plan")
             self.ws = torch.empty(int(nbytes), dtype=torch.uint8, device=E.device)
             keys = torch.empty(M, dtype=torch.int64, device=E.device)
-            lib.check(lib.nsr_nn_keys(r.data_ptr(), M, self.fp64, self.plan, keys.data_ptr(), E.stream()), "nsr_nn_keys")
+            E.call("nsr_nn_keys", r.data_ptr(), M, self.fp64, self.plan, keys.data_ptr())
             sk, order = torch.sort(keys, stable=True)
-            lib.check(lib.nsr_nn_build(r.data_ptr(), M, self.fp64, self.plan, sk.data_ptr(), order.contiguous().data_ptr(),
-                                       self.ws.data_ptr(), E.stream()), "nsr_nn_build")
+            E.call("nsr_nn_build", r.data_ptr(), M, self.fp64, self.plan, sk.data_ptr(), order.contiguous().data_ptr(), self.ws.data_ptr())
 
     def query(self, q, with_candidates: bool = False):
-        E, lib = self.engine, self.engine.lib
+        E = self.engine
         qt = E.tensor(q, what="nearest: query")
         N = qt.shape[0]
         dist = torch.empty(N, dtype=torch.float64, device=E.device)
@@ -93,11 +92,10 @@ class NNIndex:
             fp64 = int(qt.dtype == torch.float64)
             with torch.no_grad(), E.guard():
                 keys = torch.empty(N, dtype=torch.int64, device=E.device)
-                lib.check(lib.nsr_nn_keys(qt.data_ptr(), N, fp64, self.plan, keys.data_ptr(), E.stream()), "nsr_nn_keys")
+                E.call("nsr_nn_keys", qt.data_ptr(), N, fp64, self.plan, keys.data_ptr())
                 qorder = torch.sort(keys, stable=True)[1].contiguous()
-                lib.check(lib.nsr_nn_query(qt.data_ptr(), N, fp64, qorder.data_ptr(), self.plan, self.ws.data_ptr(), self.m,
-                                           dist.data_ptr(), idx.data_ptr(), None if ncand is None else ncand.data_ptr(),
-                                           E.stream()), "nsr_nn_query")
+                E.call("nsr_nn_query", qt.data_ptr(), N, fp64, qorder.data_ptr(), self.plan, self.ws.data_ptr(), self.m, dist.data_ptr(),
+                       idx.data_ptr(), None if ncand is None else ncand.data_ptr())
         return (dist, idx, ncand) if with_candidates else (dist, idx)
 
 
@@ -115,7 +113,7 @@ def _dist_stats(E: Engine, dist: torch.Tensor, th: float):
     partial = torch.empty(int(lib.nsr_recon_partial_doubles(n)), dtype=torch.float64, device=E.device)
     out = torch.empty(2, dtype=torch.float64, device=E.device)
     with E.guard():
-        lib.check(lib.nsr_dist_stats(dist.data_ptr(), n, float(th), partial.data_ptr(), out.data_ptr(), E.stream()), "nsr_dist_stats")
+        E.call("nsr_dist_stats", dist.data_ptr(), n, float(th), partial.data_ptr(), out.data_ptr())
     s, c = (float(x) for x in out.cpu())
     return s, c
 
@@ -174,9 +172,8 @@ def sample_surface(vertices, faces, count: int, seed: int = 0, uniforms=None, en
             raise ValueError("sample_surface: uniforms must be [count, 3]")
     ws = torch.empty(int(lib.nsr_sample_workspace_bytes(f.shape[0])), dtype=torch.uint8, device=E.device)
     with torch.no_grad(), E.guard():
-        lib.check(lib.nsr_sample_surface(v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], n, None if u is None else u.data_ptr(),
-                                         int(seed) & 0xFFFFFFFFFFFFFFFF, ws.data_ptr(), pts.data_ptr(), fi.data_ptr(), E.stream()),
-                  "nsr_sample_surface")
+        E.call("nsr_sample_surface", v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], n, None if u is None else u.data_ptr(),
+               int(seed) & 0xFFFFFFFFFFFFFFFF, ws.data_ptr(), pts.data_ptr(), fi.data_ptr())
     return pts, fi
 
 
@@ -217,8 +214,8 @@ def _icp(E: Engine, source, target, threshold=0.1, init=None, max_iteration=30, 
     def evaluate():
         d, idx = index.query(pcd)
         with E.guard():
-            lib.check(lib.nsr_icp_stats(pcd.data_ptr(), tgt.data_ptr(), idx.data_ptr(), d.data_ptr(), n, tgt.shape[0], float(threshold),
-                                        partial.data_ptr(), out.data_ptr(), E.stream()), "nsr_icp_stats")
+            E.call("nsr_icp_stats", pcd.data_ptr(), tgt.data_ptr(), idx.data_ptr(), d.data_ptr(), n, tgt.shape[0], float(threshold),
+                   partial.data_ptr(), out.data_ptr())
         s = out.cpu().numpy().copy()
         fitness = s[0] / n if n else 0.0
         rmse = float(np.sqrt(s[1] / s[0])) if s[0] > 0 else 0.0
@@ -299,7 +296,6 @@ def cull_masks(vertices, faces, c2w_list, H=680, W=1200, fx=600., fy=600., cx=59
     rendered from that pose (raster.visibility_counts), and seen at all if at least ``min_views`` of every ``stride``-th pose
     see it.  The poses are those ``load_poses`` returns (y and z axes flipped) either way."""
     E = engine or gpu()
-    lib = E.lib
     v = E.tensor(vertices, what="cull_mesh: vertices")
     f = E.faces(faces)
     if occlusion:
@@ -312,9 +308,8 @@ def cull_masks(vertices, faces, c2w_list, H=680, W=1200, fx=600., fy=600., cx=59
     seen = torch.empty(v.shape[0], dtype=torch.uint8, device=E.device)
     keep = torch.empty(f.shape[0], dtype=torch.uint8, device=E.device)
     with torch.no_grad(), E.guard():
-        lib.check(lib.nsr_cull_vertices(v.data_ptr(), v.shape[0], int(v.dtype == torch.float64), w2c.data_ptr(), K, int(H), int(W),
-                                        float(fx), float(fy), float(cx), float(cy), f.data_ptr(), f.shape[0], seen.data_ptr(),
-                                        keep.data_ptr(), E.stream()), "nsr_cull_vertices")
+        E.call("nsr_cull_vertices", v.data_ptr(), v.shape[0], int(v.dtype == torch.float64), w2c.data_ptr(), K, int(H), int(W), float(fx),
+               float(fy), float(cx), float(cy), f.data_ptr(), f.shape[0], seen.data_ptr(), keep.data_ptr())
     return seen.bool(), keep.bool()
 
 

@@ -12,8 +12,8 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _capi
-from .common import _as_f32c, _require_cuda, _stream, get_rays, to_channels_last, warn_ncdhw_once
+from . import _capi, engine
+from .common import _as_f32c, _require_cuda, get_rays, to_channels_last, warn_ncdhw_once
 from .layout import param_count, stage_slots
 
 _SLOT_IDX = {s: i for i, s in enumerate(_capi.SLOT_NAMES)}
@@ -75,14 +75,13 @@ def _prep_grids(c: Dict[str, torch.Tensor], stage: str, device) -> Dict[str, tor
 
 def _decoder_params(decoders, slots, dev):
     """({slot: flat parameter blob}, {slot: packed operand stream}) of the stage's decoders (a changed decoder is re-packed: one launch)"""
-    lib, stream = _capi.get_lib(), _stream(dev)
-    return {s: decoders.sub(s).flat_params() for s in slots}, {s: decoders.sub(s).packed_params(lib, stream) for s in slots}
+    E = engine.on(dev)
+    return {s: decoders.sub(s).flat_params() for s in slots}, {s: decoders.sub(s).packed_params(E) for s in slots}
 
 
 def eval_points_raw(p: torch.Tensor, decoders, c: Dict[str, torch.Tensor], stage: str, bound: Optional[torch.Tensor]):
     """Forward-only point query: (M,3) world points -> (M,4) fp32 [r,g,b,occ]; occ := 100 outside the open
     ``bound`` box when ``bound`` is given (src/utils/Renderer.py:43-46,57)."""
-    lib = _capi.get_lib()
     _require_cuda(p, "eval_points: points")
     dev = p.device
     with torch.no_grad(), _capi.on_device(dev):
@@ -93,7 +92,7 @@ def eval_points_raw(p: torch.Tensor, decoders, c: Dict[str, torch.Tensor], stage
         a.n_samples, a.n_surface, a.n_rays = 1, 0, 0
         _fill_common(a, stage, bound, decoders, grids, packed, flats)
         out = torch.empty((pts.shape[0], 4), dtype=torch.float32, device=dev)
-        lib.check(lib.nsr_eval_points_fwd(C.byref(a), pts.data_ptr(), pts.shape[0], out.data_ptr(), _stream(dev)), "nsr_eval_points_fwd")
+        engine.on(dev).call("nsr_eval_points_fwd", C.byref(a), pts.data_ptr(), pts.shape[0], out.data_ptr())
     return out
 
 
@@ -167,7 +166,6 @@ class _RenderFn(torch.autograd.Function):
 
     @staticmethod
     def _forward_impl(ctx, renderer, decoders, stage, gt_depth, gt_max, hook, rays_o, rays_d, *tensors):
-        lib = _capi.get_lib()
         slots = stage_slots(stage)
         call = RenderCall(renderer, decoders, stage, dict(zip(slots, tensors)), rays_o, rays_d, gt_depth, hook)
         dev = rays_o.device
@@ -193,7 +191,7 @@ class _RenderFn(torch.autograd.Function):
             ctx.chunk = renderer.acts_chunk_rays(stage, S, dev)
             call.args.raw = call.args.zvals = None
             call.raw = zsave = None
-        lib.check(lib.nsr_render_fwd(C.byref(call.args), _stream(dev)), "nsr_render_fwd")
+        engine.on(dev).call("nsr_render_fwd", C.byref(call.args))
         ctx.call = None
         if need_bwd:
             # `depth` is an OUTPUT: kept as a detached alias (same storage, different tensor object), so that no reference
@@ -229,12 +227,11 @@ def _chunked_backward(call: RenderCall, need, g_depth, g_var, g_rgb, chunk):
     """Backward of a batch whose activation buffer was too large to keep: per chunk of ``chunk`` rays the forward is run again
     with an activation buffer (same kernels, same batch-global depth cap) and the split backward follows; grid and decoder
     gradients accumulate over the chunks, the ray gradients are written per chunk."""
-    lib = _capi.get_lib()
     if call.hook is not None:
         raise _capi.NsrError("nice_slam_amd: a sharded render call whose activation buffer does not fit is not supported (use smaller batches)")
     renderer, S = call.renderer, call.S
     dev = call.rays_o.device
-    stream = _stream(dev)
+    E = engine.on(dev)
     n = call.rays_o.shape[0]
     need_o, need_d, _, need_par = need
     d_o = torch.zeros_like(call.rays_o) if (need_o or need_d) else None
@@ -254,7 +251,7 @@ def _chunked_backward(call: RenderCall, need, g_depth, g_var, g_rgb, chunk):
         acts = forward_args(cc, renderer.N_surface, call.gt_max, (depth, var, rgb, raw, zs), [not g_ for g_ in need_par])
         if acts is None:
             raise _capi.NsrError("nice_slam_amd: no room for the activation buffer of a %d-ray chunk" % m)
-        lib.check(lib.nsr_render_fwd(C.byref(cc.args), stream), "nsr_render_fwd(chunk)")
+        E.call("nsr_render_fwd", C.byref(cc.args))
         cc.hold += [acts, zs]
         co, cd, cg = render_backward(cc, need, g_depth[i0:i1].contiguous(), g_var[i0:i1].contiguous(), g_rgb[i0:i1].contiguous())
         if co is not None:
@@ -276,10 +273,9 @@ def render_backward(call: RenderCall, need, g_depth, g_var, g_rgb, zero_buf=None
     ``loss_grads_from_forward``: ``g_depth`` / ``g_rgb`` are the forward's own ``dl_depth`` / ``dl_rgb``, untouched (the backward
     then starts from the ``d raw`` the forward's loss epilogue precomputed, nsr_bwd_args.loss_grads_from_forward).
     -> (d_rays_o, d_rays_d, [d_grid ...])."""
-    lib = _capi.get_lib()
     a, renderer, decoders, stage, slots, grids = call.args, call.renderer, call.decoders, call.stage, call.slots, call.grids
     dev = call.rays_o.device
-    stream = _stream(dev)
+    E = engine.on(dev)
     n = call.rays_o.shape[0]
     need_o, need_d, need_grid, need_par = need
     b = _capi.NsrBwdArgs()
@@ -348,7 +344,7 @@ def render_backward(call: RenderCall, need, g_depth, g_var, g_rgb, zero_buf=None
                 poff += cnt
             else:
                 a.dec[i].dparams = None
-        nws = lib.nsr_bwd_workspace_floats(_capi.STAGE_ID[stage], n, call.S, renderer.bwd_max_blocks)
+        nws = E.lib.nsr_bwd_workspace_floats(_capi.STAGE_ID[stage], n, call.S, renderer.bwd_max_blocks)
         ws = renderer._workspace(nws, dev)
         b.workspace, b.workspace_floats = ws.data_ptr(), nws
     else:
@@ -360,7 +356,7 @@ def render_backward(call: RenderCall, need, g_depth, g_var, g_rgb, zero_buf=None
         b.ev_start, b.ev_stop = evs[0], evs[1]
         if len(evs) >= 4:
             b.ev_dx_done, b.ev_dw_done = evs[2], evs[3]
-    lib.check(lib.nsr_render_bwd(C.byref(a), C.byref(b), stream), "nsr_render_bwd")
+    E.call("nsr_render_bwd", C.byref(a), C.byref(b))
 
     def publish():
         for s, nd in zip(slots, need_par):
@@ -508,7 +504,7 @@ class Renderer(object):
 
     def acts_chunk_rays(self, stage, S, dev) -> int:
         """rays per chunk of a batch whose activation buffer does not fit: the budget and the 2^25-point limit of one call"""
-        per_ray = 4 * max(1, _capi.get_lib().nsr_acts_floats(_capi.STAGE_ID[stage], 1024, S)) / 1024.0
+        per_ray = 4 * max(1, engine.on(dev).lib.nsr_acts_floats(_capi.STAGE_ID[stage], 1024, S)) / 1024.0
         rays = int(min(self._acts_budget(dev) / per_ray, ((1 << 25) - 16) // S))
         rays -= rays % 64
         if rays < 64:
@@ -520,7 +516,7 @@ class Renderer(object):
         fit (budget, 2^25 sample points per call, or the allocation fails): the caller then differentiates in chunks.
         ``masks_only``: one bool per decoder pass of the stage, in slot order -- True: that decoder will want no parameter
         gradients, its pass only saves the relu masks (nsr_render_args.acts_masks_only)"""
-        nfl = _capi.get_lib().nsr_acts_floats(_capi.STAGE_ID[stage], n, S)
+        nfl = engine.on(dev).lib.nsr_acts_floats(_capi.STAGE_ID[stage], n, S)
         if nfl <= 0:
             raise _capi.NsrError("nsr_acts_floats: bad arguments")
         if n * S > (1 << 25) - 16 or 4 * nfl > self.max_saved_activation_bytes:

@@ -47,7 +47,7 @@ from . import _capi
 from .common import get_camera_from_tensor, grid_init, load_bound, set_decoder_bounds
 from .datasets import get_dataset
 from .decoders import NICE
-from .engine import Engine
+from .engine import on
 from .frustum import FrustumSelector
 from .keyframes import KeyframeSelector
 from .mapping import backward, mapping_loss, tracking_loss
@@ -488,7 +488,7 @@ class NICE_SLAM:
             dataset = get_dataset(cfg, folder, self.scale, device=self.device)
         self.frame_reader = dataset
         self.n_img = len(dataset) if frames is None else max(1, min(int(frames), len(dataset)))
-        self.traj = Trajectory(self.n_img, Engine(_capi.get_lib(), self.device))
+        self.traj = Trajectory(self.n_img, on(self.device))
         self.traj.gt.copy_(torch.stack([torch.as_tensor(p).float() for p in dataset.poses[:self.n_img]]))      # one upload for the run
         self.keyframe_list, self.keyframe_dict = [], []
         n_kf = self.n_img // max(1, int(mc["keyframe_every"])) + 3

@@ -82,8 +82,8 @@ def vertex_normals(vertices, faces, return_sums: bool = False, engine: Optional[
     sums = torch.empty((nv, 3), dtype=torch.float64, device=E.device)
     out = torch.empty((nv, 3), dtype=torch.float32, device=E.device)
     with torch.no_grad(), E.guard():
-        E.lib.check(E.lib.nsr_view_normals(v.data_ptr(), nv, f.data_ptr(), nf, start.data_ptr(), incident.data_ptr(), incident.numel(),
-                                           sums.data_ptr(), out.data_ptr(), E.stream()), "nsr_view_normals")
+        E.call("nsr_view_normals", v.data_ptr(), nv, f.data_ptr(), nf, start.data_ptr(), incident.data_ptr(), incident.numel(),
+               sums.data_ptr(), out.data_ptr())
     return (out, sums) if return_sums else out
 
 
@@ -128,14 +128,12 @@ def render_mesh(vertices, faces, c2w, H=HEIGHT, W=WIDTH, fx=None, fy=None, cx=No
             ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)
             n_ent = torch.zeros(1, dtype=torch.int64, device=E.device)
             wk = w2c[k0:k0 + kb]
-            lib.check(lib.nsr_raster_bin(v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), n_ent.data_ptr(),
-                                         E.stream()), "nsr_raster_bin")
+            E.call("nsr_raster_bin", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), n_ent.data_ptr())
             n = int(n_ent.item())
             bins = torch.empty(max(n, 1), dtype=torch.int32, device=E.device)
-            lib.check(lib.nsr_view_mesh(v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), bins.data_ptr(), n,
-                                        nrm.data_ptr(), None if col is None else col.data_ptr(), CULL[cull],
-                                        depth[k0:k0 + kb].data_ptr(), face[k0:k0 + kb].data_ptr(), rgb[k0:k0 + kb].data_ptr(),
-                                        E.stream()), "nsr_view_mesh")
+            E.call("nsr_view_mesh", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), bins.data_ptr(), n,
+                   nrm.data_ptr(), None if col is None else col.data_ptr(), CULL[cull], depth[k0:k0 + kb].data_ptr(),
+                   face[k0:k0 + kb].data_ptr(), rgb[k0:k0 + kb].data_ptr())
     return rgb, depth, face
 
 
@@ -175,10 +173,9 @@ def draw_points(rgb, depth, points, colors, offsets, c2w, fx=None, fy=None, cx=N
     out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=E.device)
     owner = torch.empty((B, H, W), dtype=torch.int32, device=E.device) if return_owner else None
     with torch.no_grad(), E.guard():
-        E.lib.check(E.lib.nsr_view_points(pts.data_ptr() if N else None, col.data_ptr() if N else None, N, off.data_ptr(), w2c.data_ptr(), B,
-                                          H, W, fx, fy, cx, cy, float(near), float(far), int(size), base_rgb.data_ptr(), base_d.data_ptr(),
-                                          int(per_frame), out.data_ptr(), None if owner is None else owner.data_ptr(), E.stream()),
-                    "nsr_view_points")
+        E.call("nsr_view_points", pts.data_ptr() if N else None, col.data_ptr() if N else None, N, off.data_ptr(), w2c.data_ptr(), B, H, W,
+               fx, fy, cx, cy, float(near), float(far), int(size), base_rgb.data_ptr(), base_d.data_ptr(), int(per_frame), out.data_ptr(),
+               None if owner is None else owner.data_ptr())
     return (out, owner) if return_owner else out
 
 

@@ -241,3 +241,78 @@ def test_sharded_mapping_rank_and_peer_seeds(monkeypatch):
     sh.mapping_loss({}, None, frames, 25, "color")
     assert sh._draw_state is None and seen["draw_state"] is None and seen["peer_seeds"] is None and seen["sharder"] is sh
     assert seen["indices"].shape == (75,) and int(seen["indices"].min()) >= 0 and int(seen["indices"].max()) < 48 * 64
+
+
+def test_engine_call_switches_and_restores_the_device(monkeypatch):
+    """``Engine.call`` on a fake device layer: the entry runs with the engine's device current, on that device's stream, and the
+    caller's device is back afterwards -- also when the entry fails or ctypes rejects an argument.  ``_capi.on_device`` is the only
+    switch: ``common._stream`` and ``Lib.check`` touch no device."""
+    import ctypes
+    from nice_slam_amd import _capi
+    from nice_slam_amd.common import _stream
+    from nice_slam_amd.engine import Engine
+
+    class Stream:
+        def __init__(self, idx):
+            self.cuda_stream = 1000 + idx
+
+    state = {"cur": 0}
+    sets, asked = [], []
+
+    def set_device(d):
+        state["cur"] = torch.device("cuda", d).index if isinstance(d, int) else torch.device(d).index
+        sets.append(state["cur"])
+
+    def current_stream(device=None):
+        asked.append(torch.device(device).index)
+        return Stream(asked[-1])
+
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: state["cur"])
+    monkeypatch.setattr(torch.cuda, "set_device", set_device)
+    monkeypatch.setattr(torch.cuda, "current_stream", current_stream)
+
+    class Stub(_capi.Lib):
+        def __init__(self):
+            self.seen, self.rc, self.exc = [], 0, None
+
+        def nsr_last_error(self):
+            return b"stub says no"
+
+        def nsr_x(self, *args):
+            self.seen.append((state["cur"], args))
+            if self.exc is not None:
+                raise self.exc
+            return self.rc
+
+    stub = Stub()
+    E = Engine(stub, torch.device("cuda", 1))
+    E.call("nsr_x", 7, 8)
+    assert stub.seen == [(1, (7, 8, 1001))] and asked == [1]           # device 1 current, its stream the last argument
+    assert state["cur"] == 0 and sets == [1, 0]
+    stub.rc = 1
+    with pytest.raises(_capi.NsrError, match="nsr_x failed: stub says no"):
+        E.call("nsr_x")
+    assert stub.seen[-1][0] == 1 and state["cur"] == 0
+    stub.rc, stub.exc = 0, ctypes.ArgumentError("argument 1: wrong type")
+    with pytest.raises(ctypes.ArgumentError):
+        E.call("nsr_x", object())
+    assert stub.seen[-1][0] == 1 and state["cur"] == 0
+    stub.exc = None
+    del sets[:]
+    with E.guard():                                                      # a multi-call operation: the guard's own two switches only
+        for _ in range(3):
+            E.call("nsr_x")
+            assert stub.seen[-1] == (1, (1001,))
+    assert sets == [1, 0] and state["cur"] == 0
+    del sets[:]
+    state["cur"] = 1                                                     # the device already current: no switch at all
+    E.call("nsr_x")
+    assert stub.seen[-1] == (1, (1001,)) and sets == [] and state["cur"] == 1
+    state["cur"] = 0
+    del asked[:]
+    assert _stream(torch.device("cuda", 1)) == 1001 and asked == [1] and sets == []
+    stub.check(0, "nsr_x")
+    with pytest.raises(_capi.NsrError, match="nsr_x failed"):
+        stub.check(1, "nsr_x")
+    assert sets == [] and state["cur"] == 0
