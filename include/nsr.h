@@ -617,6 +617,26 @@ int64_t nsr_image_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int nsr_image_metrics(const float *color, const float *gt_color, const float *depth, const float *gt_depth, int32_t B, int32_t H, int32_t W,
                       double *result, float *depth_residual, float *color_residual, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* --- Rendering figures (src/utils/Visualizer.py:24-107: the sheet the tracker and the mapper save while they run) -------------
+ * B frame pairs in, B sheets of bytes out; the numerical contract is written out in nice_slam_amd/csrc/nsr_figure.h.
+ * color / gt_color [B][H][W][3] fp32 (rendered / input), depth / gt_depth [B][H][W] fp32; H, W in [1, 32768], stride in
+ * [1, 32768], margin and gap in [0, 32768], B <= 65535; B = 0 succeeds and launches nothing.
+ *   nsr_figure_sheet_size   SH = 2 margin + 2 h + gap, SW = 2 margin + 3 w + 2 gap with h = ceil(H / stride), w = ceil(W / stride);
+ *                           3 SH SW must stay below 2^31.
+ *   nsr_figure_sheet        sheet u8 [B][SH][SW][3], 4-byte aligned: panel (r, c) at row margin + r (h + gap), column margin + c (w + gap)
+ *                           shows every stride-th pixel of, in row 0, gt_depth, depth and |gt_depth - depth| through matplotlib's
+ *                           Normalize(0, vmax) and plasma map (a NaN is white), in row 1 gt_color, color and |gt_color - color| as
+ *                           (uint8)(clip(v, 0, 1) 255); the residuals are 0 where gt_depth is 0; everything else is 255.  vmax is
+ *                           the frame's largest gt_depth over all pixels (nsr_image_metrics' [6]); vmax_out [B] fp32 (may be null)
+ *                           receives it.  The sheet's memory holds intermediate values until the call's last launch has run.
+ *   nsr_depth_colorize      the colour map alone: rgb u8 [B][H][W][3], 4-byte aligned, of depth with vmax [B] fp32 (device), or,
+ *                           vmax null, with each image's own maximum.
+ * No atomics: bit-identical run to run and independent of a frame's place in the batch. */
+int nsr_figure_sheet_size(int32_t H, int32_t W, int32_t stride, int32_t margin, int32_t gap, int32_t *SH, int32_t *SW);
+int nsr_figure_sheet(const float *color, const float *gt_color, const float *depth, const float *gt_depth, int32_t B, int32_t H, int32_t W,
+                     int32_t stride, int32_t margin, int32_t gap, float *vmax_out, uint8_t *sheet, void *stream);
+int nsr_depth_colorize(const float *depth, int32_t B, int32_t H, int32_t W, const float *vmax, uint8_t *rgb, void *stream);
+
 /* --- Frame preparation (src/utils/datasets.py:77-113, BaseDataset.__getitem__ after the files are decoded) ---------------------
  * The raw bytes of B frames of one geometry in, the tensors the tracker and the mapper read out: undistortion of the colour image
  * (its own launch, only with distortion coefficients), then ONE launch for the channel order, / 255, the resize of the colour

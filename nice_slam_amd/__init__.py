@@ -6,7 +6,8 @@ path, drop-in behind the reference's Renderer / decoder / get_samples call surfa
     from nice_slam_amd import recon        # eval_recon.py / cull_mesh.py: calc_3d_metric, calc_2d_metric, render_depth, cull_mesh, ...
     from nice_slam_amd import bound_from_frames, ConvexBound     # Mesher.get_bound_from_frames: TSDF fusion + convex hull
     from nice_slam_amd import KeyframeSelector                   # Mapper.keyframe_selection_overlap
-    from nice_slam_amd import imgeval      # Visualizer.vis: image_metrics (PSNR, SSIM, depth L1, residual maps), evaluate_rendering
+    from nice_slam_amd import imgeval      # Visualizer.vis: image_metrics (PSNR, SSIM, depth L1, residual maps), evaluate_rendering,
+                                           # figure_sheet and Visualizer (the 2 x 3 tracking / mapping figure), colorize_depth
     from nice_slam_amd import get_dataset, FramePreparer         # src/utils/datasets.py: the sequence readers, frames prepared on the GPU
     from nice_slam_amd import viewer       # visualizer.py / src/tools/viz.py: Replay, render_mesh, draw_points (headless replay)
     from nice_slam_amd.slam import NICE_SLAM, load_config        # run.py: the run from its config; poses on the device (Trajectory)
@@ -27,7 +28,7 @@ from .recon import align_icp, calc_3d_metric, cull_mesh, nearest, sample_surface
 from . import bound  # noqa: F401
 from .bound import ConvexBound, bound_from_frames, surface_points, tsdf_fuse  # noqa: F401
 from . import imgeval  # noqa: F401
-from .imgeval import evaluate_rendering, image_metrics  # noqa: F401
+from .imgeval import Visualizer, colorize_depth, evaluate_rendering, figure_sheet, image_metrics  # noqa: F401
 from . import datasets  # noqa: F401
 from .datasets import FramePreparer, get_dataset  # noqa: F401
 from . import viewer  # noqa: F401
@@ -39,7 +40,7 @@ __all__ = ["Renderer", "NICE", "MLP", "MLP_no_xyz", "get_samples", "get_rays", "
            "Mesher", "marching_cubes",
            "recon", "nearest", "sample_surface", "align_icp", "calc_3d_metric", "cull_mesh",
            "bound", "bound_from_frames", "ConvexBound", "tsdf_fuse", "surface_points",
-           "imgeval", "image_metrics", "evaluate_rendering",
+           "imgeval", "image_metrics", "evaluate_rendering", "figure_sheet", "colorize_depth", "Visualizer",
            "datasets", "get_dataset", "FramePreparer",
            "viewer",
            "poses", "Trajectory", "get_tensor_from_camera"]

@@ -213,6 +213,10 @@ SYMBOLS = (
     ("nsr_image_metrics_workspace_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     ("nsr_image_metrics", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("nsr_figure_sheet_size", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("nsr_figure_sheet", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_depth_colorize", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("nsr_frame_out_size", C.c_int, [C.POINTER(NsrFrameDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("nsr_frame_workspace_bytes", C.c_int64, [C.POINTER(NsrFrameDesc), C.c_int32]),
     ("nsr_frame_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NsrFrameDesc), C.c_int32, C.c_void_p, C.c_void_p,

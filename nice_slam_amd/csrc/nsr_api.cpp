@@ -17,6 +17,7 @@
 #include "../../nice_slam_amd/csrc/nsr_raster.h"
 #include "../../nice_slam_amd/csrc/nsr_view.h"
 #include "../../nice_slam_amd/csrc/nsr_imgmetrics.h"
+#include "../../nice_slam_amd/csrc/nsr_figure.h"
 #include "../../nice_slam_amd/csrc/nsr_frame.h"
 #include "../../nice_slam_amd/csrc/nsr_pose.h"
 
@@ -1754,6 +1755,90 @@ int nsr_image_metrics(const float *color, const float *gt_color, const float *de
     NSR_LAUNCH(nsr::imgmetrics_tile_kernel, dim3(P.ntiles, B), dim3(T), nsr::kImLds, stream, P);
     NSR_LAUNCH(nsr::imgmetrics_final_kernel, dim3(B), dim3(T), nsr::kImFinalLds, stream, P);
     return finish("nsr_image_metrics");
+}
+
+}  // extern "C"
+
+// ---- rendering figures (include/nsr.h, "Rendering figures") ----
+namespace {
+
+constexpr int kFigMaxSide = 32768;
+
+// nullptr: the sizes are valid and P's layout fields are filled; else what is wrong with them
+const char *figure_geometry(int32_t H, int32_t W, int32_t stride, int32_t margin, int32_t gap, nsr::FigureParams &P) {
+    if (H < 1 || W < 1 || H > kFigMaxSide || W > kFigMaxSide) return "image sizes must be in [1, 32768]";
+    if (stride < 1 || stride > kFigMaxSide) return "stride must be in [1, 32768]";
+    if (margin < 0 || gap < 0 || margin > kFigMaxSide || gap > kFigMaxSide) return "margin and gap must be in [0, 32768]";
+    P.H = H; P.W = W; P.stride = stride; P.margin = margin; P.gap = gap;
+    P.h = (H + stride - 1) / stride;
+    P.w = (W + stride - 1) / stride;
+    P.SH = 2 * margin + 2 * P.h + gap;
+    P.SW = 2 * margin + 3 * P.w + 2 * gap;
+    if (3ll * P.SH * P.SW >= (1ll << 31)) return "the sheet must stay below 2^31 bytes per frame";
+    return nullptr;
+}
+
+// launches 1 and 2 of nsr_figure.h (the frames' maxima, into P.vmax_out or the slots), then 3 and, without a buffer, 4
+int figure_launch(nsr::FigureParams &P, bool own_max, void *stream, const char *what) {
+    const int T = nsr::kFigThreads;
+    const long long frame_bytes = 3ll * P.SH * P.SW, groups = (P.npix + nsr::kFigLane - 1) / nsr::kFigLane;
+    if (nblk(groups, T) > 2147483647ll) return fail(std::string(what) + ": too many pixels for one launch");
+    if (reinterpret_cast<uintptr_t>(P.out) & 3) return fail(std::string(what) + ": the output must be 4-byte aligned");
+    P.skip_slot = 0;
+    if (own_max && !P.tiny) {
+        long long np = ((long long)P.H * P.W + nsr::kFigMaxChunk - 1) / nsr::kFigMaxChunk;
+        if (np > (frame_bytes - 8) / 4) np = (frame_bytes - 8) / 4;                 // slot + partials + 3 bytes of alignment fit the frame
+        P.np = (int)np;
+        NSR_LAUNCH(nsr::figure_max_partial_kernel, dim3(P.np, P.B), dim3(T), 4 * T, stream, P);
+        NSR_LAUNCH(nsr::figure_max_final_kernel, dim3(P.B), dim3(T), 4 * T, stream, P);
+        P.vmax = P.vmax_out;
+        P.skip_slot = P.vmax_out ? 0 : 1;
+    }
+    NSR_LAUNCH(nsr::figure_sheet_kernel, dim3((unsigned)nblk(groups, T)), dim3(T), nsr::kFigLds, stream, P);
+    if (P.skip_slot) NSR_LAUNCH(nsr::figure_slot_kernel, dim3((unsigned)nblk(P.B, T)), dim3(T), nsr::kFigLds, stream, P);
+    return finish(what);
+}
+
+}  // namespace
+
+extern "C" {
+
+int nsr_figure_sheet_size(int32_t H, int32_t W, int32_t stride, int32_t margin, int32_t gap, int32_t *SH, int32_t *SW) {
+    nsr::FigureParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (const char *e = figure_geometry(H, W, stride, margin, gap, P)) return fail(std::string("nsr_figure_sheet_size: ") + e);
+    if (!SH || !SW) return fail("nsr_figure_sheet_size: null pointer");
+    *SH = P.SH;
+    *SW = P.SW;
+    return 0;
+}
+
+int nsr_figure_sheet(const float *color, const float *gt_color, const float *depth, const float *gt_depth, int32_t B, int32_t H, int32_t W,
+                     int32_t stride, int32_t margin, int32_t gap, float *vmax_out, uint8_t *sheet, void *stream) {
+    nsr::FigureParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (const char *e = figure_geometry(H, W, stride, margin, gap, P)) return fail(std::string("nsr_figure_sheet: ") + e);
+    if (B < 0 || B > 65535) return fail("nsr_figure_sheet: the batch size must be in [0, 65535]");
+    if (B == 0) return 0;
+    if (!color || !gt_color || !depth || !gt_depth || !sheet) return fail("nsr_figure_sheet: null pointer");
+    P.color = color; P.gt_color = gt_color; P.depth = depth; P.gt_depth = gt_depth;
+    P.vmax_out = vmax_out; P.out = sheet; P.B = B; P.sheet = 1;
+    P.npix = (long long)B * P.SH * P.SW;
+    return figure_launch(P, true, stream, "nsr_figure_sheet");
+}
+
+int nsr_depth_colorize(const float *depth, int32_t B, int32_t H, int32_t W, const float *vmax, uint8_t *rgb, void *stream) {
+    nsr::FigureParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (H < 1 || W < 1 || H > kFigMaxSide || W > kFigMaxSide) return fail("nsr_depth_colorize: image sizes must be in [1, 32768]");
+    if (3ll * H * W >= (1ll << 31)) return fail("nsr_depth_colorize: the image must stay below 2^31 bytes");
+    if (B < 0 || B > 65535) return fail("nsr_depth_colorize: the batch size must be in [0, 65535]");
+    if (B == 0) return 0;
+    if (!depth || !rgb) return fail("nsr_depth_colorize: null pointer");
+    P.depth = depth; P.vmax = vmax; P.out = rgb; P.B = B; P.H = H; P.W = W; P.stride = 1; P.h = H; P.w = W; P.SH = H; P.SW = W;
+    P.npix = (long long)B * H * W;
+    P.tiny = !vmax && (long long)H * W < nsr::kFigTinyPixels ? 1 : 0;
+    return figure_launch(P, vmax == nullptr, stream, "nsr_depth_colorize");
 }
 
 }  // extern "C"

@@ -6,10 +6,14 @@ rendered-depth L1 against the input frames, with the residual maps of the refere
     m = imgeval.image_metrics(color, gt_color, depth, gt_depth)            # {"psnr", "psnr_valid", "ssim", "depth_l1_cm", ...}
     r = imgeval.evaluate_rendering(renderer, c, decoders, frames)          # {"frames": [...], "mean": {...}, ...}
 
-    python -m nice_slam_amd.imgeval RENDERED.npz GT.npz                    # each file: arrays ``color`` and ``depth``
+    s = imgeval.figure_sheet(color, gt_color, depth, gt_depth)             # u8 [SH, SW, 3]: the Visualizer's 2 x 3 figure
+    vis = imgeval.Visualizer(freq, inside_freq, vis_dir, renderer, verbose, device)       # Visualizer.py:8-107
+    vis.vis(idx, it, gt_depth, gt_color, c2w_or_camera_tensor, c, decoders)               # -> {vis_dir}/{idx:05d}_{it:04d}.jpg
 
-Every per-pixel and per-window loop runs in libnsr.so (include/nsr.h, "Rendering evaluation"; the definitions are written out
-in csrc/nsr_imgmetrics.h): one launch evaluates a whole batch of frame pairs.
+    python -m nice_slam_amd.imgeval RENDERED.npz GT.npz [--figures DIR]    # each file: arrays ``color`` and ``depth``
+
+Every per-pixel and per-window loop runs in libnsr.so (include/nsr.h, "Rendering evaluation" and "Rendering figures"; the
+definitions are written out in csrc/nsr_imgmetrics.h and csrc/nsr_figure.h): one launch evaluates a whole batch of frame pairs.
 
   * PSNR: ``-10 log10(mean((clip(a, 0, 1) - clip(b, 0, 1))^2))``, data range 1, over all pixels (``psnr``) and over the pixels
     with an input depth (``psnr_valid``); the clip is the Visualizer's (:85-87).
@@ -17,13 +21,18 @@ in csrc/nsr_imgmetrics.h): one launch evaluates a whole batch of frame pairs.
     11 x 11 Gaussian (sigma 1.5), windows wholly inside the image, biased moments, C1 = 0.01^2, C2 = 0.03^2, the mean over
     windows and channels; not masked by depth.
   * Depth L1: ``100 mean |gt - rendered|`` (cm) over the pixels whose input depth is not 0; NaN for a frame without one.
+  * Figure: the sheet of Visualizer.py:67-102 as bytes -- input depth, generated depth and depth residual over input RGB,
+    generated RGB and RGB residual; the depths through matplotlib's ``Normalize(0, max input depth)`` and plasma map, the
+    colours clipped to [0, 1] -- point-sampled, without titles.
 
-Not here: the matplotlib figure of the Visualizer, and LPIPS (it needs trained network weights).
+Not here: LPIPS (it needs trained network weights).
 """
 from __future__ import annotations
 
 import argparse
+import ctypes as C
 import math
+import os
 import sys
 from typing import Optional
 
@@ -34,11 +43,12 @@ from . import _capi
 from .common import get_camera_from_tensor
 from .engine import Engine, gpu
 
-__all__ = ["image_metrics", "evaluate_rendering", "RESULT_DOUBLES"]
+__all__ = ["image_metrics", "evaluate_rendering", "figure_sheet", "figure_sheet_size", "colorize_depth", "Visualizer", "RESULT_DOUBLES"]
 
 RESULT_DOUBLES = 8               # per frame, include/nsr.h
 MIN_SIDE = 11                    # one SSIM window
 MAX_FRAMES_PER_LAUNCH = 65535
+FIGURE_FRAMES_PER_LAUNCH = 65532  # a multiple of 4: every launch's part of the output starts on a dword
 
 
 def _images(E: Engine, x, channels: bool, what: str) -> torch.Tensor:
@@ -102,6 +112,141 @@ def image_metrics(color, gt_color, depth, gt_depth, residuals: bool = False, eng
     return out
 
 
+# --------------------------------------------------------------------------------------------------
+# the figure (src/utils/Visualizer.py:67-102)
+# --------------------------------------------------------------------------------------------------
+def figure_sheet_size(H: int, W: int, stride: int = 1, margin: int = 8, gap: int = 8, engine: Optional[Engine] = None):
+    """(SH, SW) of the sheet of an H x W frame: 2 margin + 2 ceil(H / stride) + gap by 2 margin + 3 ceil(W / stride) + 2 gap"""
+    lib = (engine or gpu()).lib
+    sh, sw = C.c_int32(0), C.c_int32(0)
+    lib.call("nsr_figure_sheet_size", int(H), int(W), int(stride), int(margin), int(gap), C.byref(sh), C.byref(sw))
+    return sh.value, sw.value
+
+
+def figure_sheet(color, gt_color, depth, gt_depth, stride: int = 1, margin: int = 8, gap: int = 8, engine: Optional[Engine] = None,
+                 return_vmax: bool = False):
+    """The Visualizer's figure of rendered images against the input frames as bytes: u8 [B, SH, SW, 3] on the engine's device
+    ([SH, SW, 3] for one frame), inputs as for ``image_metrics`` (any size from 1 x 1).  Row 0 shows the input depth, the
+    generated depth and their residual through the plasma map with ``vmax`` = the frame's largest input depth, row 1 the input
+    colour, the generated colour and their residual clipped to [0, 1]; every ``stride``-th pixel, ``margin`` white pixels around
+    and ``gap`` between the panels.  One ``nsr_figure_sheet`` call for the batch.  ``return_vmax``: also the [B] fp32 maxima."""
+    E = engine or gpu()
+    single = (color.ndim if hasattr(color, "ndim") else np.asarray(color).ndim) == 3
+    a, b = _images(E, color, True, "color"), _images(E, gt_color, True, "gt_color")
+    d, g = _images(E, depth, False, "depth"), _images(E, gt_depth, False, "gt_depth")
+    if a.shape != b.shape or d.shape != g.shape or a.shape[:3] != d.shape:
+        raise ValueError(f"figure_sheet: shapes differ (color {tuple(a.shape)}, gt_color {tuple(b.shape)}, depth {tuple(d.shape)}, "
+                         f"gt_depth {tuple(g.shape)})")
+    B, H, W = d.shape
+    SH, SW = figure_sheet_size(H, W, stride, margin, gap, E)
+    sheet = torch.empty((B, SH, SW, 3), dtype=torch.uint8, device=E.device)
+    vmax = torch.empty((B,), dtype=torch.float32, device=E.device)
+    with torch.no_grad(), E.guard():
+        for k0 in range(0, B, FIGURE_FRAMES_PER_LAUNCH):
+            sl = slice(k0, min(B, k0 + FIGURE_FRAMES_PER_LAUNCH))
+            E.call("nsr_figure_sheet", a[sl].data_ptr(), b[sl].data_ptr(), d[sl].data_ptr(), g[sl].data_ptr(), sl.stop - k0, H, W,
+                   int(stride), int(margin), int(gap), vmax[sl].data_ptr(), sheet[sl].data_ptr())
+    if single:
+        sheet, vmax = sheet[0], vmax[0]
+    return (sheet, vmax) if return_vmax else sheet
+
+
+def colorize_depth(depth, vmax=None, engine: Optional[Engine] = None) -> torch.Tensor:
+    """Depth image(s) [H, W] or [B, H, W] through the figure's colour map -- matplotlib's ``plasma(Normalize(0, vmax)(depth))``
+    as bytes, a NaN white -- u8 [B, H, W, 3] ([H, W, 3] for one image) on the engine's device.  ``vmax``: a number, a [B]
+    tensor or array, or None: each image's own maximum."""
+    E = engine or gpu()
+    single = (depth.ndim if hasattr(depth, "ndim") else np.asarray(depth).ndim) == 2
+    d = _images(E, depth, False, "depth")
+    B, H, W = d.shape
+    vm = None
+    if vmax is not None:
+        vm = torch.as_tensor(vmax).detach().to(E.device, torch.float32).reshape(-1)
+        vm = (vm.expand(B) if vm.numel() == 1 else vm).contiguous()
+        if vm.shape != (B,):
+            raise ValueError(f"colorize_depth: vmax must be one number or one per image (got {tuple(vm.shape)} for {B} images)")
+    rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=E.device)
+    with torch.no_grad(), E.guard():
+        for k0 in range(0, B, FIGURE_FRAMES_PER_LAUNCH):
+            sl = slice(k0, min(B, k0 + FIGURE_FRAMES_PER_LAUNCH))
+            E.call("nsr_depth_colorize", d[sl].data_ptr(), sl.stop - k0, H, W, None if vm is None else vm[sl].data_ptr(), rgb[sl].data_ptr())
+    return rgb[0] if single else rgb
+
+
+def save_sheet(sheet: torch.Tensor, path: str, quality: int = 90):
+    """one u8 [SH, SW, 3] sheet as an image file (``viewer.save_image``)"""
+    from .viewer import save_image
+    save_image(sheet, path, quality=quality)
+
+
+class Visualizer:
+    """src/utils/Visualizer.py:8-107 on the GPU: ``vis`` renders the frame at a pose and saves the 2 x 3 figure when
+    ``idx % freq == 0 and iter % inside_freq == 0``.  ``freq <= 0`` or ``inside_freq <= 0``: off, nothing is ever drawn (the
+    reference would divide by zero) and the directory is not created.  ``stride`` / ``margin`` / ``gap``: the sheet's layout
+    (``figure_sheet``); ``engine``: where the sheet is built (default: the product's engine of ``device``)."""
+
+    def __init__(self, freq, inside_freq, vis_dir, renderer, verbose, device="cuda:0", stride: int = 1, margin: int = 8, gap: int = 8,
+                 engine: Optional[Engine] = None):
+        self.freq, self.inside_freq = int(freq), int(inside_freq)
+        self.device, self.vis_dir, self.verbose, self.renderer = device, vis_dir, verbose, renderer
+        self.stride, self.margin, self.gap, self.engine = stride, margin, gap, engine
+        self.on = self.freq > 0 and self.inside_freq > 0
+        self.drawn = 0
+        if self.on:
+            os.makedirs(f"{vis_dir}", exist_ok=True)
+
+    def due(self, idx, iter) -> bool:
+        return self.on and int(idx) % self.freq == 0 and int(iter) % self.inside_freq == 0
+
+    def due_iters(self, idx, n_iters: int) -> list:
+        """the iterations of ``range(n_iters)`` on which frame ``idx`` has a figure due"""
+        if not self.on or int(idx) % self.freq != 0:
+            return []
+        return list(range(0, int(n_iters), self.inside_freq))
+
+    def _c2w(self, pose):
+        if len(pose.shape) == 1:                                                   # Visualizer.py:43-49
+            bottom = torch.tensor([[0.0, 0.0, 0.0, 1.0]], dtype=torch.float32, device=pose.device)
+            return torch.cat([get_camera_from_tensor(pose.clone().detach()), bottom], dim=0)
+        return pose
+
+    def vis_many(self, idx, iters, poses, gt_depth, gt_color, c, decoders):
+        """Several poses of ONE frame (``poses[i]`` belongs to iteration ``iters[i]``; 4x4 poses or 7-float camera tensors):
+        those that are due are rendered, their sheets are built by one ``nsr_figure_sheet`` launch and saved as
+        ``{vis_dir}/{idx:05d}_{iter:04d}.jpg``.  Returns the sheets u8 [n, SH, SW, 3] in the order given, None when none is due."""
+        todo = [(int(it), p) for it, p in zip(iters, poses) if self.due(idx, it)]
+        if not todo:
+            return None
+        E = self.engine or _engine_of(self.device)
+        with torch.no_grad():
+            depths, colors = [], []
+            for _, pose in todo:
+                depth, _, color = self.renderer.render_img(c, decoders, self._c2w(pose), self.device, stage="color", gt_depth=gt_depth)
+                depths.append(depth.detach().to(E.device, torch.float32))
+                colors.append(color.detach().to(E.device, torch.float32))
+            n = len(todo)
+            gd = torch.as_tensor(gt_depth).detach().to(E.device, torch.float32)
+            gc = torch.as_tensor(gt_color).detach().to(E.device, torch.float32)
+            sheets = figure_sheet(torch.stack(colors), gc[None].expand(n, *gc.shape), torch.stack(depths), gd[None].expand(n, *gd.shape),
+                                  stride=self.stride, margin=self.margin, gap=self.gap, engine=E)
+        for (it, _), sheet in zip(todo, sheets):
+            path = f"{self.vis_dir}/{int(idx):05d}_{it:04d}.jpg"
+            save_sheet(sheet, path)
+            self.drawn += 1
+            if self.verbose:
+                print(f"Saved rendering visualization of color/depth image at {path}")
+        return sheets
+
+    def vis(self, idx, iter, gt_depth, gt_color, c2w_or_camera_tensor, c, decoders):
+        """Visualizer.py:24-107"""
+        return self.vis_many(idx, [iter], [c2w_or_camera_tensor], gt_depth, gt_color, c, decoders)
+
+
+def _engine_of(device) -> Engine:
+    from .engine import on
+    return on(device)
+
+
 METRICS = ("psnr", "psnr_valid", "ssim", "depth_l1_cm")
 
 
@@ -116,7 +261,7 @@ def _means(rows) -> dict:
 
 
 def evaluate_rendering(renderer, c, decoders, frames, stage: str = "color", device="cuda:0", batch: int = 8, residuals: bool = False,
-                       engine: Optional[Engine] = None) -> dict:
+                       engine: Optional[Engine] = None, figures: Optional[str] = None) -> dict:
     """Re-render frames and measure them: ``frames`` is an iterable of ``(idx, gt_color [H, W, 3], gt_depth [H, W],
     c2w_or_camera_tensor)``; a 7-float camera tensor (quaternion, translation) goes through ``get_camera_from_tensor`` as in
     Visualizer.py:43-51.  Each frame is rendered with ``renderer.render_img(c, decoders, c2w, device, stage, gt_depth=gt_depth)``
@@ -127,10 +272,13 @@ def evaluate_rendering(renderer, c, decoders, frames, stage: str = "color", devi
          "n_frames": int, "n_no_depth": int}                          # frames without any valid depth: not in the depth mean
 
     With ``residuals`` every frame's row also holds the rendered ``depth`` and ``color`` and the two residual maps (fp32, on
-    the engine's device)."""
+    the engine's device).  ``figures``: a directory that receives each frame's figure (``figure_sheet``) as ``{idx:05d}.jpg``,
+    one launch per ``batch`` frames."""
     E = engine or gpu()
     batch = max(1, int(batch))
     rows, pending = [], []
+    if figures is not None:
+        os.makedirs(figures, exist_ok=True)
 
     def flush():
         if not pending:
@@ -138,6 +286,11 @@ def evaluate_rendering(renderer, c, decoders, frames, stage: str = "color", devi
         m = image_metrics(torch.stack([p[1] for p in pending]), torch.stack([p[2] for p in pending]),
                           torch.stack([p[3] for p in pending]), torch.stack([p[4] for p in pending]), residuals=residuals, engine=E)
         host = {k: m[k].cpu() for k in METRICS + ("n_valid", "depth_max")}
+        if figures is not None:
+            sheets = figure_sheet(torch.stack([p[1] for p in pending]), torch.stack([p[2] for p in pending]),
+                                  torch.stack([p[3] for p in pending]), torch.stack([p[4] for p in pending]), engine=E)
+            for p_, sheet in zip(pending, sheets):
+                save_sheet(sheet, os.path.join(figures, f"{int(p_[0]):05d}.jpg"))
         for i, p in enumerate(pending):
             row = {"idx": p[0]}
             row.update({k: float(host[k][i]) for k in METRICS})
@@ -168,12 +321,18 @@ def evaluate_rendering(renderer, c, decoders, frames, stage: str = "color", devi
 # --------------------------------------------------------------------------------------------------
 def main(argv=None, engine: Optional[Engine] = None):
     ap = argparse.ArgumentParser(prog="python -m nice_slam_amd.imgeval",
-                                 description="PSNR, SSIM and depth L1 of rendered frames against input frames on the GPU.")
+                                 description="PSNR, SSIM and depth L1 of rendered frames against input frames on the GPU, and their figures.")
     ap.add_argument("rendered", type=str, help=".npz with the rendered frames: color [B, H, W, 3] (or [H, W, 3]) and depth [B, H, W]")
     ap.add_argument("gt", type=str, help=".npz with the input frames: color and depth of the same shapes")
+    ap.add_argument("--figures", type=str, default=None, help="a directory for one figure per frame, {frame:05d}.jpg (Visualizer.py:67-102)")
     args = ap.parse_args(argv)
     r, g = np.load(args.rendered), np.load(args.gt)
     m = image_metrics(r["color"], g["color"], r["depth"], g["depth"], engine=engine)
+    if args.figures is not None:
+        os.makedirs(args.figures, exist_ok=True)
+        sheets = figure_sheet(r["color"], g["color"], r["depth"], g["depth"], engine=engine)
+        for k, sheet in enumerate(sheets if sheets.dim() == 4 else sheets[None]):
+            save_sheet(sheet, os.path.join(args.figures, f"{k:05d}.jpg"))
     rows = [{k: float(v) for k, v in zip(METRICS, vals)}
             for vals in zip(*(m[k].reshape(-1).cpu().tolist() for k in METRICS))]
     mean = _means(rows)

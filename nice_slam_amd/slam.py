@@ -18,10 +18,18 @@ iterations and the choice of the best one (``nsr_pose_commit``) -- nothing is re
 poses on the device (``get_tensor_from_camera``) and writes them back with ``Trajectory.store``; it does synchronise, because
 ``FrustumSelector`` and ``KeyframeSelector`` read poses and counts on the host.
 
+The figures of the reference's ``Visualizer`` (``tracking_vis/``, ``mapping_vis/``: ``vis_freq``, ``vis_inside_freq``,
+``no_vis_on_first_frame``) are drawn by ``imgeval.Visualizer``.  The tracked frame stays one replay: its figures are drawn
+after it, from the pose BEFORE each due iteration -- the motion model's 7-vector, which the frame copies into a ``start``
+buffer, then ``hist[j - 1, 1:]`` -- all of one frame in one ``nsr_figure_sheet`` launch.  The copy is recorded only when some
+tracked frame of the sequence can have a figure due; a frame (and a mapping call) without one executes what it did before.
+
 Deviations from the reference, all deliberate:
   * ``sync_method`` 'loose' and 'free' run as 'strict' (one notice); the run is one process, not three, on ``mapping.device``;
   * the coarse mapper shares the mapper's keyframe list (in the reference it keeps a copy that misses the bundle-adjusted poses);
-  * ``vis_freq`` / ``vis_inside_freq`` figures are not drawn (``nice_slam_amd.imgeval`` gives the numbers);
+  * the figures are sheets of pixels without titles; the coarse mapper draws none (in the reference
+    it overwrites the mapper's files of the same name); the tracker reads ``tracking.no_vis_on_first_frame`` (the reference's
+    reads the mapping section's, Tracker.py:58);
   * ``low_gpu_mem`` is accepted and ignored: keyframe colour and depth stay on the device;
   * a frame none of whose iterations has a loss below 1e10 keeps the motion model's pose (the reference fails on ``None`` there,
     Tracker.py:250-251);
@@ -49,6 +57,7 @@ from .datasets import get_dataset
 from .decoders import NICE
 from .engine import on
 from .frustum import FrustumSelector
+from .imgeval import Visualizer
 from .keyframes import KeyframeSelector
 from .mapping import backward, mapping_loss, tracking_loss
 from .mesher import Mesher
@@ -171,7 +180,8 @@ def load_pretrained(decoders: NICE, cfg: dict, device="cpu"):
 # --------------------------------------------------------------------------------------------------
 class Tracker:
     """One frame: ``update_para_from_mapping``, then one replay of the frame's graph.  ``slam`` provides cfg, device, renderer,
-    shared_c, shared_decoders, traj, counters and timers (NICE_SLAM below; a test may pass a namespace)."""
+    shared_c, shared_decoders, traj, counters and timers, and output, verbose and n_img for the figures (NICE_SLAM below; a
+    test may pass a namespace)."""
 
     def __init__(self, slam):
         tc = slam.cfg["tracking"]
@@ -184,6 +194,13 @@ class Tracker:
         self.prev_map_version = None
         self.c, self.decoders = None, None
         self._ft = None
+        self.no_vis_on_first_frame = tc["no_vis_on_first_frame"]
+        self.visualizer = Visualizer(tc["vis_freq"], tc["vis_inside_freq"],                # Tracker.py:66-68
+                                     os.path.join(slam.output, "vis" if "Demo" in slam.output else "tracking_vis"), slam.renderer,
+                                     slam.verbose, self.device)
+        # a tracked frame (idx >= 1) of this sequence can have a figure due: only then does the frame keep the motion model's pose
+        self.keep_start = self.visualizer.on and self.num_cam_iters > 0 and any(
+            self.visualizer.due(i, 0) for i in range(1, slam.n_img))
 
     slam = property(lambda self: self._slam())
 
@@ -217,7 +234,8 @@ class Tracker:
         self._ft = {"buf": buf, "quad": quad, "T": T, "params": params, "opt": FlatAdam(params, lr=lrs),
                     "depth": depth.clone(), "color": color.clone(), "i": torch.zeros(1, dtype=torch.long, device=dev),
                     "hist": torch.zeros((max(n_it, 1), 8), dtype=torch.float32, device=dev),       # loss | pose per iteration
-                    "best": torch.zeros(8, dtype=torch.float32, device=dev), "graph": None}
+                    "best": torch.zeros(8, dtype=torch.float32, device=dev), "graph": None,
+                    "start": torch.zeros(7, dtype=torch.float32, device=dev) if self.keep_start else None}
         return self._ft
 
     def _iteration(self):
@@ -240,6 +258,8 @@ class Tracker:
         ft = self._ft
         self.traj.predict(ft["buf"], const_speed=self.const_speed_assumption)
         with torch.no_grad():
+            if ft["start"] is not None:
+                ft["start"].copy_(ft["buf"])                        # the pose before iteration 0, for the frame's figures
             ft["opt"].reset_state()
             ft["i"].zero_()
         for _ in range(iters):
@@ -253,8 +273,10 @@ class Tracker:
         slam = self.slam
         self.update_para_from_mapping()
         self.traj.set_index(idx)
-        if idx == 0 or self.gt_camera:                              # Tracker.py:184-185
+        if idx == 0 or self.gt_camera:                              # Tracker.py:184-188
             self.traj.est[idx].copy_(self.traj.gt[idx])
+            if not self.no_vis_on_first_frame:
+                self.visualizer.vis(idx, 0, depth, color, self.traj.gt[idx], self.c, self.decoders)
             return
         ft = self._ft
         if ft is None:
@@ -278,6 +300,14 @@ class Tracker:
             ft["graph"].replay()
         slam.counters["tracking_iters"] += self.num_cam_iters
         slam.counters["tracking_rays"] += self.num_cam_iters * self.pixels
+        due = self.visualizer.due_iters(idx, self.num_cam_iters) if self.keep_start else []
+        if due:                                                     # Tracker.py:229-230, after the replay
+            self.visualizer.vis_many(idx, due, self.figure_poses(due), depth, color, self.c, self.decoders)
+
+    def figure_poses(self, iters) -> list:
+        """the camera tensors the frame's iterations ``iters`` started from: ``start``, then the pose after iteration j - 1"""
+        ft = self._ft
+        return [ft["start"] if j == 0 else ft["hist"][j - 1, 1:] for j in iters]
 
 
 # --------------------------------------------------------------------------------------------------
@@ -309,6 +339,11 @@ class Mapper:
         self.BA = False
         self.rng = np.random.RandomState(slam.seed + 1) if coarse_mapper else np.random     # (its own process in the reference)
         self.last_loss = float("nan")
+        self.no_vis_on_first_frame = mc["no_vis_on_first_frame"]
+        self.visualizer = None                                      # Mapper.py:88-90; the coarse mapper draws nothing
+        if not coarse_mapper and "Demo" not in slam.output:
+            self.visualizer = Visualizer(mc["vis_freq"], mc["vis_inside_freq"], os.path.join(slam.output, "mapping_vis"), slam.renderer,
+                                         slam.verbose, self.device)
 
     slam = property(lambda self: self._slam())
 
@@ -392,7 +427,14 @@ class Mapper:
                 gopt.step({k: st[k[len("grid_"):] + "_lr"] * lr_factor for k in keys})
             loss_buf.copy_(loss.detach().reshape(1))
 
-        n = int(num_joint_iters)
+        vis = self.visualizer                                                           # Mapper.py:426-428, before joint_iter's step
+        draws = vis is not None and not (idx == 0 and self.no_vis_on_first_frame) and bool(vis.due_iters(idx, num_joint_iters))
+
+        def figure(joint_iter):
+            if draws:
+                vis.vis(idx, joint_iter, cur_gt_depth, cur_gt_color, cur_c2w, c, slam.shared_decoders)
+
+        n, done = int(num_joint_iters), 0
         if self.coarse_mapper:                                                          # Mapper.py:403-410
             plan = (("coarse", n),)
         else:
@@ -406,18 +448,22 @@ class Mapper:
                 lrs[i] = mc["stage"][stage]["decoders_lr"] * lr_factor                  # Mapper.py:412
             if BA:
                 lrs[-1] = self.BA_cam_lr if stage == "color" else 0.0                   # Mapper.py:417-419
+            figure(done)
             iteration(stage)                                                            # eager: also initialises optimiser state
             if cnt > 3:                                                                 # one graph per stage, the rest are replays
                 torch.cuda.synchronize(dev)
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
                     iteration(stage)
-                for _ in range(cnt - 1):
+                for j in range(1, cnt):
+                    figure(done + j)
                     graph.replay()
                 del graph
             else:
-                for _ in range(cnt - 1):
+                for j in range(1, cnt):
+                    figure(done + j)
                     iteration(stage)
+            done += cnt
             slam.counters["coarse_iters" if self.coarse_mapper else "mapping_iters"] += cnt
             if not self.coarse_mapper:
                 slam.counters["mapping_rays"] += cnt * pixs_per_image * len(optimize_frame)
