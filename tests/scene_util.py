@@ -25,6 +25,10 @@ SCENES = {
     "synthetic": ([[-5.12, 5.11], [-5.12, 5.11], [-5.12, 5.11]], GRID_LEN, (1024, 1024, 512.0, 512.0, 511.5, 511.5)),
     # a dense coarse level over a small, cheap scene: 16 x 16 x 12 = 3072 coarse voxels (the coarse stage's gradient grid then cannot sit
     # in a dX block's LDS: 160 KB / 128 B per voxel = 1280), the other levels coarsened to 10 x 10 x 8 and 5 x 5 x 4
+    # the `small` box with fine and colour cells of 8 cm and a 140 x 125 degree camera: within six fine cells of the camera the frustum
+    # holds well over a thousand fine voxels (more than a dX block's hot-voxel table has slots) at coordinates below 1 m, where the
+    # reference's fp32 sines are quiet (tests/local_gate.py)
+    "hot_wide": ([[-0.7, 0.8], [-0.6, 0.7], [-0.5, 0.6]], dict(GRID_LEN, coarse=0.8, fine=0.08, color=0.08), (48, 64, 12.0, 12.0, 31.5, 23.5)),
     "coarse_dense": ([[-1.6, 1.5], [-1.6, 1.5], [-1.2, 1.3]], dict(coarse=0.4, middle=0.64, fine=0.32, color=0.32), (48, 64, 60.0, 60.0, 31.5, 23.5)),
 }
 
