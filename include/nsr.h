@@ -690,6 +690,34 @@ int nsr_pose_predict(float *traj, int64_t n_frames, const int64_t *idx, int32_t 
 int nsr_pose_commit(const float *hist, int32_t n_iters, float *traj, int64_t n_frames, const int64_t *idx, float *best, void *stream);
 int nsr_pose_store(const float *cams, int32_t m, const int64_t *index, float *dst, int64_t n_dst, void *stream);
 
+/* --- Trajectory evaluation (src/tools/eval_ate.py: the absolute trajectory error of a run and its figure) ----------------------
+ * est / gt [n_frames][4][4] fp32 (a checkpoint's estimate_c2w_list / gt_c2w_list), last [B] device int64: problem b evaluates the
+ * frames 0..last[b] (the checkpoint's idx, eval_ate.py:291 and convert_poses' range(0, N + 1)).  n_frames in [1, 2^24], scale
+ * positive and finite.  The numerical contract is written out in nice_slam_amd/csrc/nsr_trajeval.h.
+ *   nsr_ate_eval   B <= 2^20 problems in one launch, one block each; B = 0 succeeds and launches nothing.  A frame is used iff its
+ *                  gt pose is finite (eval_ate.py:247-252); positions are (double)(t / scale) with the division in fp32 (:253,
+ *                  :146-148); Horn's alignment of the estimate to the ground truth in fp64 (align, :44-78); the statistics of
+ *                  the error (:215-223).  rec [B][32] fp64 per problem:
+ *                    [0] compared pose pairs   [1] dropped gt frames   [2] non-finite est poses among the used frames
+ *                    [3] rmse  [4] mean  [5] median (numpy's)  [6] population std  [7] min  [8] max
+ *                    [9..17] rot row-major   [18..20] trans   (aligned = rot est + trans)
+ *                    [21] xmin  [22] xmax  [23] ymin  [24] ymax of the gt positions and the aligned est positions
+ *                    [25] flags: 1 fewer than two pairs, 2 last[b] outside [0, n_frames), 4 a non-finite est pose
+ *                    [26..31] 0
+ *                  [3..24] are NaN with no pair, with flag 2 (then [0..2] are 0 and nothing else is written) and with flag 4.
+ *                  err (may be null) [B][n_frames] fp64: the errors of the used frames in their order in err[b][0 .. pairs);
+ *                  the rest of the row is left as it was.  No global atomics, fixed-order sums: bit-identical run to run and
+ *                  independent of the other problems.  Nothing synchronises, safe to capture.
+ *   nsr_ate_plot   eval_ate_plot.png (:196-204, :213) of ONE problem: last and rec point at that problem's entry and record in
+ *                  device memory.  image u8 [H][W][3] (the reference's figure: H 432, W 576): white, the axes box
+ *                  [0.125 W, 0.9 W] x [0.11 H, 0.88 H] and the gt trajectory's x-y projection in black, the aligned estimate in
+ *                  blue (0, 0, 255) on top; limits = the record's widened by 5 % of the range; hard-edged lines of 1.875 px
+ *                  (1.5 pt at 90 dpi), the box 1 px.  Title, legend, ticks and labels are not drawn. */
+int nsr_ate_eval(const float *est, const float *gt, int64_t n_frames, const int64_t *last, int32_t B, float scale, double *rec, double *err,
+                 void *stream);
+int nsr_ate_plot(const float *est, const float *gt, int64_t n_frames, const int64_t *last, float scale, const double *rec, int32_t H, int32_t W,
+                 uint8_t *image, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ path, drop-in behind the reference's Renderer / decoder / get_samples call surfa
     from nice_slam_amd import get_dataset, FramePreparer         # src/utils/datasets.py: the sequence readers, frames prepared on the GPU
     from nice_slam_amd import viewer       # visualizer.py / src/tools/viz.py: Replay, render_mesh, draw_points (headless replay)
     from nice_slam_amd.slam import NICE_SLAM, load_config        # run.py: the run from its config; poses on the device (Trajectory)
+    from nice_slam_amd import evaluate_ate, ate_curve            # src/tools/eval_ate.py: alignment, error statistics, eval_ate_plot.png
 
 No CPU / PyTorch fallback exists: every arithmetic entry point goes through libnsr.so.
 """
@@ -34,6 +35,8 @@ from .datasets import FramePreparer, get_dataset  # noqa: F401
 from . import viewer  # noqa: F401
 from . import poses  # noqa: F401
 from .poses import Trajectory, get_tensor_from_camera  # noqa: F401
+from . import trajeval  # noqa: F401
+from .trajeval import AteResult, ate_curve, evaluate_ate, plot_trajectories, save_plot  # noqa: F401
 
 __all__ = ["Renderer", "NICE", "MLP", "MLP_no_xyz", "get_samples", "get_rays", "grid_init", "load_bound",
            "to_channels_last", "MaskedGridAdam", "FlatAdam", "FrustumSelector", "KeyframeSelector", "aabb_keep", "get_samples_window", "mapping_loss", "tracking_loss", "seed_pixel_draws", "get_camera_from_tensor", "backward",
@@ -43,4 +46,5 @@ __all__ = ["Renderer", "NICE", "MLP", "MLP_no_xyz", "get_samples", "get_rays", "
            "imgeval", "image_metrics", "evaluate_rendering", "figure_sheet", "colorize_depth", "Visualizer",
            "datasets", "get_dataset", "FramePreparer",
            "viewer",
-           "poses", "Trajectory", "get_tensor_from_camera"]
+           "poses", "Trajectory", "get_tensor_from_camera",
+           "trajeval", "evaluate_ate", "ate_curve", "plot_trajectories", "save_plot", "AteResult"]

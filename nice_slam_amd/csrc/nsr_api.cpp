@@ -20,6 +20,7 @@
 #include "../../nice_slam_amd/csrc/nsr_figure.h"
 #include "../../nice_slam_amd/csrc/nsr_frame.h"
 #include "../../nice_slam_amd/csrc/nsr_pose.h"
+#include "../../nice_slam_amd/csrc/nsr_trajeval.h"
 
 namespace {
 
@@ -1989,6 +1990,37 @@ int nsr_pose_store(const float *cams, int32_t m, const int64_t *index, float *ds
     P.cams = cams; P.m = m; P.index = reinterpret_cast<const long long *>(index); P.dst = dst; P.n_dst = n_dst;
     NSR_LAUNCH(nsr::pose_store_kernel, dim3(1), dim3(nsr::kPoseThreads), 0, stream, P);
     return finish("nsr_pose_store");
+}
+
+}  // extern "C"
+
+// ---- trajectory evaluation (include/nsr.h, "Trajectory evaluation") ----
+extern "C" {
+
+int nsr_ate_eval(const float *est, const float *gt, int64_t n_frames, const int64_t *last, int32_t B, float scale, double *rec, double *err,
+                 void *stream) {
+    if (n_frames < 1 || n_frames > (1ll << 24)) return fail("nsr_ate_eval: n_frames must be in [1, 2^24]");
+    if (B < 0 || B > (1 << 20)) return fail("nsr_ate_eval: the number of problems must be in [0, 2^20]");
+    if (!(scale > 0.f) || scale > 3.0e38f) return fail("nsr_ate_eval: scale must be positive and finite");
+    if (B == 0) return 0;
+    if (!est || !gt || !last || !rec) return fail("nsr_ate_eval: null pointer");
+    nsr::AteParams P;
+    P.est = est; P.gt = gt; P.n_frames = n_frames; P.last = reinterpret_cast<const long long *>(last); P.scale = scale; P.rec = rec; P.err = err;
+    NSR_LAUNCH(nsr::ate_eval_kernel, dim3((unsigned)B), dim3(nsr::kAteThreads), nsr::kAteLds, stream, P);
+    return finish("nsr_ate_eval");
+}
+
+int nsr_ate_plot(const float *est, const float *gt, int64_t n_frames, const int64_t *last, float scale, const double *rec, int32_t H, int32_t W,
+                 uint8_t *image, void *stream) {
+    if (n_frames < 1 || n_frames > (1ll << 24)) return fail("nsr_ate_plot: n_frames must be in [1, 2^24]");
+    if (!(scale > 0.f) || scale > 3.0e38f) return fail("nsr_ate_plot: scale must be positive and finite");
+    if (H < 1 || W < 1 || H > 32768 || W > 32768 || 3ll * H * W >= (1ll << 31)) return fail("nsr_ate_plot: the image size must be in [1, 32768] with 3 H W below 2^31");
+    if (!est || !gt || !last || !rec || !image) return fail("nsr_ate_plot: null pointer");
+    nsr::AtePlotParams P;
+    P.est = est; P.gt = gt; P.n_frames = n_frames; P.last = reinterpret_cast<const long long *>(last); P.scale = scale; P.rec = rec;
+    P.out = image; P.H = H; P.W = W;
+    NSR_LAUNCH(nsr::ate_plot_kernel, dim3((unsigned)nblk((long long)H * W, nsr::kPlotThreads)), dim3(nsr::kPlotThreads), nsr::kPlotLds, stream, P);
+    return finish("nsr_ate_plot");
 }
 
 }  // extern "C"

@@ -98,6 +98,19 @@ class Trajectory:
             E.call("nsr_pose_commit", hist.data_ptr(), hist.shape[0], self.est.data_ptr(), self.n, self.idx.data_ptr(),
                    best.data_ptr() if best is not None else None)
 
+    def ate(self, out: Optional[torch.Tensor] = None, scale: float = 1.0) -> torch.Tensor:
+        """The absolute trajectory error of the frames ``0..idx`` (src/tools/eval_ate.py; ``idx`` is read on the device): the
+        record of 32 doubles of include/nsr.h, rmse at [3].  With ``out`` (contiguous fp64 [32] on the trajectory's device)
+        nothing is allocated and nothing is read back: the call can sit in a captured graph."""
+        from .trajeval import REC, _launch
+        E = self.E
+        if out is None:
+            out = torch.empty((REC,), dtype=torch.float64, device=E.device)
+        elif out.dtype is not torch.float64 or out.numel() != REC or not out.is_contiguous() or out.device != E.device:
+            raise _capi.NsrError("Trajectory.ate: out is contiguous fp64 [32] on the trajectory's device")
+        _launch(E, self.est, self.gt, self.idx, scale, out)
+        return out
+
     def store(self, cams: torch.Tensor, index: torch.Tensor, dst: Optional[torch.Tensor] = None):
         """dst[index[i]] := the 4x4 pose of cams[i] (src/Mapper.py:527-541); ``dst``: a [K,4,4] fp32 pose table on the
         device (default: ``est``); ``index``: int64 [m] on the device."""
