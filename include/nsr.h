@@ -637,6 +637,25 @@ int nsr_figure_sheet(const float *color, const float *gt_color, const float *dep
                      int32_t stride, int32_t margin, int32_t gap, float *vmax_out, uint8_t *sheet, void *stream);
 int nsr_depth_colorize(const float *depth, int32_t B, int32_t H, int32_t W, const float *vmax, uint8_t *rgb, void *stream);
 
+/* --- JPEG encoding (baseline sequential DCT, 8 bit, three components, JFIF YCbCr) ----------------------------------------------
+ * n images that are on the device in, their entropy-coded segments out: what stands between a JPEG file's SOS header and its EOI.
+ * The caller writes the markers around them (nice_slam_amd/jpeg.py); the numerical contract -- integers end to end -- is written
+ * out in nice_slam_amd/csrc/nsr_jpeg.h.  images u8 [n][H][W][3] RGB; H, W in [1, 65535]; n <= 65535, n = 0 succeeds and launches
+ * nothing; subsampling 0 (4:4:4, MCU 8 x 8) or 2 (4:2:0, MCU 16 x 16), the codes of PIL's JpegImagePlugin.get_sampling; quality in
+ * [1, 100]: T.81's tables K.1 / K.2 scaled by the IJG rule; the Huffman tables are K.3 - K.6; the restart interval is one MCU row
+ * (DRI = ceil(W / MCU side)), RSTm stands behind every interval but a frame's last.
+ *   nsr_jpeg_size     the bytes of workspace and of output that nsr_jpeg_encode needs for such a batch: the worst case of any
+ *                     content (a block of 63 AC codes of 26 bits and a DC code of 20, every byte stuffed), nothing is sized by
+ *                     the images.
+ *   nsr_jpeg_encode   out (out_bytes >= the size query's) receives frame k's segment at [offsets[k], offsets[k + 1]), offsets int64
+ *                     [n + 1] on the device, offsets[0] = 0; no byte of out at or behind offsets[n] is written.  workspace: 16-byte
+ *                     aligned, workspace_bytes >= the size query's.
+ * No atomics on global memory, every sum and scan in a fixed order: the same images give the same bytes, whatever else is in the
+ * batch. */
+int nsr_jpeg_size(int32_t n, int32_t H, int32_t W, int32_t subsampling, int64_t *workspace_bytes, int64_t *out_bytes);
+int nsr_jpeg_encode(const uint8_t *images, int32_t n, int32_t H, int32_t W, int32_t quality, int32_t subsampling, void *workspace,
+                    int64_t workspace_bytes, uint8_t *out, int64_t out_bytes, int64_t *offsets, void *stream);
+
 /* --- Frame preparation (src/utils/datasets.py:77-113, BaseDataset.__getitem__ after the files are decoded) ---------------------
  * The raw bytes of B frames of one geometry in, the tensors the tracker and the mapper read out: undistortion of the colour image
  * (its own launch, only with distortion coefficients), then ONE launch for the channel order, / 255, the resize of the colour

@@ -217,6 +217,9 @@ SYMBOLS = (
     ("nsr_figure_sheet", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("nsr_depth_colorize", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_jpeg_size", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("nsr_jpeg_encode", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                  C.c_int64, C.c_void_p, C.c_void_p]),
     ("nsr_frame_out_size", C.c_int, [C.POINTER(NsrFrameDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("nsr_frame_workspace_bytes", C.c_int64, [C.POINTER(NsrFrameDesc), C.c_int32]),
     ("nsr_frame_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NsrFrameDesc), C.c_int32, C.c_void_p, C.c_void_p,

@@ -21,6 +21,7 @@
 #include "../../nice_slam_amd/csrc/nsr_frame.h"
 #include "../../nice_slam_amd/csrc/nsr_pose.h"
 #include "../../nice_slam_amd/csrc/nsr_trajeval.h"
+#include "../../nice_slam_amd/csrc/nsr_jpeg.h"
 
 namespace {
 
@@ -1840,6 +1841,102 @@ int nsr_depth_colorize(const float *depth, int32_t B, int32_t H, int32_t W, cons
     P.npix = (long long)B * H * W;
     P.tiny = !vmax && (long long)H * W < nsr::kFigTinyPixels ? 1 : 0;
     return figure_launch(P, vmax == nullptr, stream, "nsr_depth_colorize");
+}
+
+}  // extern "C"
+
+// ---- JPEG encoding (include/nsr.h, "JPEG encoding") ----
+namespace {
+
+struct JpegLayout {
+    long long o_coef, o_bitoff, o_raw, o_ibits, o_nff, o_ioff, o_ftot, ws_bytes, out_bytes;
+};
+
+inline long long round16ll(long long v) { return (v + 15) & ~15ll; }
+
+// nullptr: the sizes are valid and P's geometry and L are filled; else what is wrong with them
+const char *jpeg_geometry(int32_t n, int32_t H, int32_t W, int32_t subsampling, nsr::JpegParams &P, JpegLayout &L) {
+    if (n < 0 || n > 65535) return "the batch size must be in [0, 65535]";
+    if (H < 1 || W < 1 || H > 65535 || W > 65535) return "image sizes must be in [1, 65535]";
+    if (subsampling != 0 && subsampling != 2) return "subsampling must be 0 (4:4:4) or 2 (4:2:0)";
+    P.n = n; P.H = H; P.W = W;
+    P.sub = subsampling == 0 ? 1 : 2;
+    const int side = 8 * P.sub;
+    P.mcux = (W + side - 1) / side;
+    P.mcuy = (H + side - 1) / side;
+    P.bpm = P.sub == 1 ? 3 : 6;
+    P.BI = P.mcux * P.bpm;
+    const long long nint = (long long)n * P.mcuy;
+    P.nblocks = nint * P.BI;
+    if (nint > 2147483647ll || P.nblocks > 2147483647ll) return "too many blocks for one call";
+    P.nint = (int)nint;
+    const long long rawcap = ((long long)P.BI * nsr::kJpgBlockBits + 7) / 8;
+    P.rawstride = (unsigned)round16ll(rawcap);
+    L.o_coef = 0;
+    L.o_bitoff = L.o_coef + 128 * P.nblocks;
+    L.o_raw = L.o_bitoff + round16ll(4 * P.nblocks);
+    L.o_ibits = L.o_raw + nint * P.rawstride;
+    L.o_nff = L.o_ibits + round16ll(4 * nint);
+    L.o_ioff = L.o_nff + round16ll(4 * nint);
+    L.o_ftot = L.o_ioff + round16ll(8 * nint);
+    L.ws_bytes = L.o_ftot + round16ll(8ll * n);
+    L.out_bytes = n * (P.mcuy * 2 * rawcap + 2ll * (P.mcuy - 1));
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nsr_jpeg_size(int32_t n, int32_t H, int32_t W, int32_t subsampling, int64_t *workspace_bytes, int64_t *out_bytes) {
+    nsr::JpegParams P;
+    JpegLayout L;
+    std::memset(&P, 0, sizeof(P));
+    if (const char *e = jpeg_geometry(n, H, W, subsampling, P, L)) return fail(std::string("nsr_jpeg_size: ") + e);
+    if (!workspace_bytes || !out_bytes) return fail("nsr_jpeg_size: null pointer");
+    *workspace_bytes = L.ws_bytes;
+    *out_bytes = L.out_bytes;
+    return 0;
+}
+
+int nsr_jpeg_encode(const uint8_t *images, int32_t n, int32_t H, int32_t W, int32_t quality, int32_t subsampling, void *workspace,
+                    int64_t workspace_bytes, uint8_t *out, int64_t out_bytes, int64_t *offsets, void *stream) {
+    nsr::JpegParams P;
+    JpegLayout L;
+    std::memset(&P, 0, sizeof(P));
+    if (const char *e = jpeg_geometry(n, H, W, subsampling, P, L)) return fail(std::string("nsr_jpeg_encode: ") + e);
+    if (quality < 1 || quality > 100) return fail("nsr_jpeg_encode: quality must be in [1, 100]");
+    if (n == 0) return 0;
+    if (!images || !workspace || !out || !offsets) return fail("nsr_jpeg_encode: null pointer");
+    if (workspace_bytes < L.ws_bytes || out_bytes < L.out_bytes) return fail("nsr_jpeg_encode: workspace or output smaller than nsr_jpeg_size reports");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail("nsr_jpeg_encode: the workspace must be 16-byte aligned");
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int c = 0; c < 2; ++c)
+        for (int k = 0; k < 64; ++k) {
+            const int v = (nsr::kJpgQuantBase[c][nsr::kJpgZigzag[k]] * scale + 50) / 100;
+            P.q[c][k] = (unsigned char)(v < 1 ? 1 : (v > 255 ? 255 : v));
+        }
+    char *ws = static_cast<char *>(workspace);
+    P.img = images;
+    P.coef = reinterpret_cast<short *>(ws + L.o_coef);
+    P.bitoff = reinterpret_cast<unsigned *>(ws + L.o_bitoff);
+    P.raw = reinterpret_cast<unsigned char *>(ws + L.o_raw);
+    P.ibits = reinterpret_cast<unsigned *>(ws + L.o_ibits);
+    P.nff = reinterpret_cast<unsigned *>(ws + L.o_nff);
+    P.ioff = reinterpret_cast<long long *>(ws + L.o_ioff);
+    P.ftot = reinterpret_cast<long long *>(ws + L.o_ftot);
+    P.out = out;
+    P.offsets = reinterpret_cast<long long *>(offsets);
+    const int T = nsr::kJpgThreads, scan_lds = nsr::kJpgScanLds;
+    if (P.sub == 1) NSR_LAUNCH(nsr::jpeg_transform_kernel<1>, dim3(nblk(P.nblocks, T)), dim3(T), 0, stream, P);
+    else NSR_LAUNCH(nsr::jpeg_transform_kernel<2>, dim3(nblk(P.nblocks, T)), dim3(T), 0, stream, P);
+    NSR_LAUNCH(nsr::jpeg_measure_kernel, dim3(P.nint), dim3(T), nsr::kJpgMeasureLds, stream, P);
+    NSR_LAUNCH(nsr::jpeg_pack_kernel, dim3(P.nint), dim3(T), nsr::kJpgPackLds, stream, P);
+    NSR_LAUNCH(nsr::jpeg_count_kernel, dim3(P.nint), dim3(T), scan_lds, stream, P);
+    NSR_LAUNCH(nsr::jpeg_offsets_kernel, dim3(P.n), dim3(T), scan_lds, stream, P, 0);
+    NSR_LAUNCH(nsr::jpeg_offsets_kernel, dim3(1), dim3(T), scan_lds, stream, P, 1);
+    NSR_LAUNCH(nsr::jpeg_stuff_kernel, dim3(P.nint), dim3(T), scan_lds, stream, P);
+    return finish("nsr_jpeg_encode");
 }
 
 }  // extern "C"

@@ -173,20 +173,24 @@ def colorize_depth(depth, vmax=None, engine: Optional[Engine] = None) -> torch.T
     return rgb[0] if single else rgb
 
 
-def save_sheet(sheet: torch.Tensor, path: str, quality: int = 90):
-    """one u8 [SH, SW, 3] sheet as an image file (``viewer.save_image``)"""
+def save_sheet(sheet: torch.Tensor, path: str, quality: int = 90, encoder: str = "pil", engine: Optional[Engine] = None):
+    """one u8 [SH, SW, 3] sheet as an image file (``viewer.save_image``: ``encoder`` "pil" or "gpu")"""
     from .viewer import save_image
-    save_image(sheet, path, quality=quality)
+    save_image(sheet, path, quality=quality, encoder=encoder, engine=engine)
 
 
 class Visualizer:
     """src/utils/Visualizer.py:8-107 on the GPU: ``vis`` renders the frame at a pose and saves the 2 x 3 figure when
     ``idx % freq == 0 and iter % inside_freq == 0``.  ``freq <= 0`` or ``inside_freq <= 0``: off, nothing is ever drawn (the
     reference would divide by zero) and the directory is not created.  ``stride`` / ``margin`` / ``gap``: the sheet's layout
-    (``figure_sheet``); ``engine``: where the sheet is built (default: the product's engine of ``device``)."""
+    (``figure_sheet``); ``engine``: where the sheet is built (default: the product's engine of ``device``); ``encoder``: "pil"
+    (the host encodes each sheet) or "gpu" (the sheets of a ``vis_many`` call are encoded where they are, in one call)."""
 
     def __init__(self, freq, inside_freq, vis_dir, renderer, verbose, device="cuda:0", stride: int = 1, margin: int = 8, gap: int = 8,
-                 engine: Optional[Engine] = None):
+                 engine: Optional[Engine] = None, encoder: str = "pil"):
+        if encoder not in ("pil", "gpu"):
+            raise ValueError(f"Visualizer: encoder must be 'pil' or 'gpu' (got {encoder!r})")
+        self.encoder = encoder
         self.freq, self.inside_freq = int(freq), int(inside_freq)
         self.device, self.vis_dir, self.verbose, self.renderer = device, vis_dir, verbose, renderer
         self.stride, self.margin, self.gap, self.engine = stride, margin, gap, engine
@@ -229,9 +233,17 @@ class Visualizer:
             gc = torch.as_tensor(gt_color).detach().to(E.device, torch.float32)
             sheets = figure_sheet(torch.stack(colors), gc[None].expand(n, *gc.shape), torch.stack(depths), gd[None].expand(n, *gd.shape),
                                   stride=self.stride, margin=self.margin, gap=self.gap, engine=E)
-        for (it, _), sheet in zip(todo, sheets):
+        streams = None
+        if self.encoder == "gpu":
+            from .jpeg import encode_jpeg
+            streams = encode_jpeg(sheets, quality=90, engine=E)
+        for k, ((it, _), sheet) in enumerate(zip(todo, sheets)):
             path = f"{self.vis_dir}/{int(idx):05d}_{it:04d}.jpg"
-            save_sheet(sheet, path)
+            if streams is None:
+                save_sheet(sheet, path)
+            else:
+                with open(path, "wb") as fh:
+                    fh.write(streams[k])
             self.drawn += 1
             if self.verbose:
                 print(f"Saved rendering visualization of color/depth image at {path}")

@@ -21,7 +21,8 @@ poses on the device (``get_tensor_from_camera``) and writes them back with ``Tra
 The figures of the reference's ``Visualizer`` (``tracking_vis/``, ``mapping_vis/``: ``vis_freq``, ``vis_inside_freq``,
 ``no_vis_on_first_frame``) are drawn by ``imgeval.Visualizer``.  The tracked frame stays one replay: its figures are drawn
 after it, from the pose BEFORE each due iteration -- the motion model's 7-vector, which the frame copies into a ``start``
-buffer, then ``hist[j - 1, 1:]`` -- all of one frame in one ``nsr_figure_sheet`` launch.  The copy is recorded only when some
+buffer, then ``hist[j - 1, 1:]`` -- all of one frame in one ``nsr_figure_sheet`` launch.  An optional ``encoder: gpu`` next to
+``vis_freq`` (``tracking`` / ``mapping``) has the sheets encoded on the GPU too (``jpeg.encode_jpeg``); absent, PIL does it.  The copy is recorded only when some
 tracked frame of the sequence can have a figure due; a frame (and a mapping call) without one executes what it did before.
 
 Deviations from the reference, all deliberate:
@@ -197,7 +198,7 @@ class Tracker:
         self.no_vis_on_first_frame = tc["no_vis_on_first_frame"]
         self.visualizer = Visualizer(tc["vis_freq"], tc["vis_inside_freq"],                # Tracker.py:66-68
                                      os.path.join(slam.output, "vis" if "Demo" in slam.output else "tracking_vis"), slam.renderer,
-                                     slam.verbose, self.device)
+                                     slam.verbose, self.device, encoder=tc.get("encoder", "pil"))
         # a tracked frame (idx >= 1) of this sequence can have a figure due: only then does the frame keep the motion model's pose
         self.keep_start = self.visualizer.on and self.num_cam_iters > 0 and any(
             self.visualizer.due(i, 0) for i in range(1, slam.n_img))
@@ -343,7 +344,7 @@ class Mapper:
         self.visualizer = None                                      # Mapper.py:88-90; the coarse mapper draws nothing
         if not coarse_mapper and "Demo" not in slam.output:
             self.visualizer = Visualizer(mc["vis_freq"], mc["vis_inside_freq"], os.path.join(slam.output, "mapping_vis"), slam.renderer,
-                                         slam.verbose, self.device)
+                                         slam.verbose, self.device, encoder=mc.get("encoder", "pil"))
 
     slam = property(lambda self: self._slam())
 

@@ -8,6 +8,7 @@ point-sampled wireframes, both trajectories as point clouds, one JPEG per frame 
     replay.update_mesh("output/mesh/00500_mesh.ply"); replay.update_pose(1, est[500]); replay.save("frame.jpg")
 
     python -m nice_slam_amd.viewer --output output/Replica/room0 --scale 1        # -> output/Replica/room0/tmp_rendering/*.jpg
+    python -m nice_slam_amd.viewer --output output/Replica/room0 --video          # ... encoded on the GPU, and output/.../vis.avi
 
 Every per-pixel and per-vertex loop runs in libnsr.so (include/nsr.h, "Replay view"; the rules are written out in
 csrc/nsr_view.h): area-weighted vertex normals (nsr_view_normals), the mesh layer over the depth rasterizer's bins
@@ -41,7 +42,7 @@ from .ply import read_mesh
 from .raster import _scene, _views_per_launch, max_extent, NEAR_REL
 
 __all__ = ["vertex_normals", "render_mesh", "draw_points", "camera_actor", "viewer_pose", "default_camera", "config_scale", "Replay",
-           "replay_run", "main"]
+           "replay_run", "save_image", "main"]
 
 CULL = {None: 0, "none": 0, "back": 1, "front": 2}
 WIDTH, HEIGHT = 960, 540                            # half of viz.py:158
@@ -343,11 +344,22 @@ class Replay:
         self.snapshot()
         return self.flush()[-1]
 
-    def save(self, path: str, quality: int = 90):
-        save_image(self.frame(), path, quality)
+    def save(self, path: str, quality: int = 90, encoder: str = "pil"):
+        save_image(self.frame(), path, quality, encoder=encoder, engine=self.E)
 
 
-def save_image(img: torch.Tensor, path: str, quality: int = 90):
+ENCODERS = ("pil", "gpu")
+
+
+def save_image(img: torch.Tensor, path: str, quality: int = 90, encoder: str = "pil", engine: Optional[Engine] = None):
+    """one uint8 [H, W, 3] image as a file.  ``encoder="pil"``: PIL on the host, whatever format the path names;
+    ``"gpu"``: a JPEG encoded where the pixels are (``jpeg.save_jpeg``, on ``engine`` or the product's)"""
+    if encoder not in ENCODERS:
+        raise ValueError(f"save_image: encoder must be 'pil' or 'gpu' (got {encoder!r})")
+    if encoder == "gpu":
+        from .jpeg import save_jpeg
+        save_jpeg(img, path, quality=quality, engine=engine)
+        return
     from PIL import Image
     Image.fromarray(img.cpu().numpy()).save(path, quality=quality)
 
@@ -395,10 +407,16 @@ def load_run(output: str, scale: float):
 
 
 def replay_run(output: str, scale: float = 1.0, no_gt_traj: bool = False, width=WIDTH, height=HEIGHT, view="first", every=1,
-               engine: Optional[Engine] = None) -> int:
+               engine: Optional[Engine] = None, encoder: str = "pil", video: Optional[str] = None) -> int:
     """Replay the run in ``output`` as visualizer.py:60-91 walks it -- the newest mesh when ``mesh/{i:05d}_mesh.ply`` exists, both
     poses every frame, the trajectories every 10th -- and write every ``every``-th frame to ``tmp_rendering/{n:06d}.jpg`` (n from
-    1).  Returns the number of images written."""
+    1).  ``encoder="gpu"``: every flushed batch is encoded by one ``jpeg.encode_jpeg`` call and the files are its streams;
+    ``video``: a file name under ``output`` (``vis.avi``) that receives the same streams as a Motion-JPEG video at 30 frames/s
+    (it implies the GPU encoder).  Returns the number of images written."""
+    if encoder not in ENCODERS:
+        raise ValueError(f"replay_run: encoder must be 'pil' or 'gpu' (got {encoder!r})")
+    if video is not None:
+        encoder = "gpu"
     est, gt, N = load_run(output, scale)
     replay = Replay(est[0], cam_scale=0.3, estimate_c2w_list=est, gt_c2w_list=gt, width=width, height=height, view=view, engine=engine)
     out_dir = os.path.join(output, "tmp_rendering")
@@ -406,9 +424,23 @@ def replay_run(output: str, scale: float = 1.0, no_gt_traj: bool = False, width=
     for old in glob.glob(os.path.join(out_dir, "*.jpg")):
         os.remove(old)
     written = 0
+    writer = None
+    if video is not None:
+        from .jpeg import MjpegWriter
+        writer = MjpegWriter(os.path.join(output, video), width, height, fps=30)
 
     def write():
         nonlocal written
+        if encoder == "gpu":
+            from .jpeg import encode_jpeg
+            frames = replay.flush()
+            for data in (encode_jpeg(frames, quality=90, engine=replay.E) if len(frames) else []):
+                written += 1
+                with open(os.path.join(out_dir, f"{written:06d}.jpg"), "wb") as fh:
+                    fh.write(data)
+                if writer is not None:
+                    writer.write(data)
+            return
         for img in replay.flush().cpu().numpy():
             written += 1
             from PIL import Image
@@ -431,7 +463,11 @@ def replay_run(output: str, scale: float = 1.0, no_gt_traj: bool = False, width=
             queued += 1
             if queued % FRAMES_PER_LAUNCH == 0:
                 write()
-    write()
+    try:
+        write()
+    finally:
+        if writer is not None:
+            writer.close()
     return written
 
 
@@ -446,6 +482,9 @@ def main(argv=None):
     ap.add_argument("--size", type=str, default=f"{WIDTH}x{HEIGHT}", help="image size WxH, at most 1024 a side")
     ap.add_argument("--view", choices=("first", "follow"), default="first", help="fixed viewer behind the first pose, or behind each pose")
     ap.add_argument("--every", type=int, default=1, help="write every N-th frame")
+    ap.add_argument("--encoder", choices=ENCODERS, default="pil", help="who encodes the JPEGs: PIL on the host, or the GPU (a batch per call)")
+    ap.add_argument("--video", nargs="?", const="vis.avi", default=None, metavar="NAME",
+                    help="also write the frames as a Motion-JPEG video OUTPUT/NAME (default vis.avi) at 30 frames/s; implies --encoder gpu")
     args = ap.parse_args(argv)
     try:
         width, height = (int(x) for x in args.size.lower().split("x"))
@@ -454,8 +493,11 @@ def main(argv=None):
     if args.every < 1:
         ap.error("--every must be positive")
     scale = config_scale(args.config) if args.config else (1.0 if args.scale is None else args.scale)
-    n = replay_run(args.output, scale, args.no_gt_traj, width, height, args.view, args.every)
+    n = replay_run(args.output, scale, args.no_gt_traj, width, height, args.view, args.every, encoder=args.encoder, video=args.video)
     print(f"wrote {n} images to {os.path.join(args.output, 'tmp_rendering')}")
+    if args.video is not None:
+        print(f"wrote {n} frames to {os.path.join(args.output, args.video)}")
+        return 0
     print(f"ffmpeg -f image2 -r 30 -pattern_type glob -i '{args.output}/tmp_rendering/*.jpg' -y {args.output}/vis.mp4")
     return 0
 
