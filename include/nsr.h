@@ -656,6 +656,36 @@ int nsr_jpeg_size(int32_t n, int32_t H, int32_t W, int32_t subsampling, int64_t 
 int nsr_jpeg_encode(const uint8_t *images, int32_t n, int32_t H, int32_t W, int32_t quality, int32_t subsampling, void *workspace,
                     int64_t workspace_bytes, uint8_t *out, int64_t out_bytes, int64_t *offsets, void *stream);
 
+/* --- JPEG decoding (baseline sequential DCT, 8 bit, Huffman coded; one or three components) ------------------------------------
+ * The bytes of n JPEG files that are on the device in, out u8 [n][H][W][3] RGB: the pixels libjpeg-turbo's default decoder gives
+ * (islow IDCT, fancy upsampling), bit for bit.  The caller walks the markers (nice_slam_amd/jpeg.py) and describes every file by
+ * one nsr_jpegdec_frame in device memory (8-byte aligned): its tables, and its entropy-coded segment as a byte range of `files`.
+ * The numerical contract is written out in nice_slam_amd/csrc/nsr_jpegdec.h.  All frames of a call share H, W in [1, 65535] and
+ * sampling (NSR_JPEG_444 / 422 / 420: three components, luma 1x1 / 2x1 / 2x2 over chroma 1x1, PIL's get_sampling codes;
+ * NSR_JPEG_GREY: one component); n <= 65535, n = 0 succeeds and launches nothing.  subsequence_bytes: the piece of a restart
+ * interval's stuffed stream that one lane decodes, a multiple of 4 in [16, 1024] (128 is the default of the callers); the result
+ * does not depend on it.  max_scan_bytes: the longest entropy-coded segment of the batch, at most 2^28.
+ *   nsr_jpegdec_size     the bytes of workspace nsr_jpegdec_decode needs; nothing is sized by what the files hold.
+ *   nsr_jpegdec_decode   workspace 16-byte aligned, workspace_bytes >= the size query's.  status int32 [n] on the device: 0, or
+ *                        bits 1 an invalid Huffman code, 2 a coefficient index past 63, 4 a block count other than the frame
+ *                        header's, 8 restart markers missing or out of sequence; such a frame's pixels are unspecified, the
+ *                        other frames of the batch are not affected.  Every stream fetch stays inside [scan_begin, scan_end).
+ * No atomics on global memory, every scan in a fixed order: the same bytes give the same pixels, whatever else is in the batch. */
+enum { NSR_JPEG_444 = 0, NSR_JPEG_422 = 1, NSR_JPEG_420 = 2, NSR_JPEG_GREY = 3 };
+typedef struct nsr_jpegdec_frame {
+    int64_t scan_begin, scan_end;       /* the entropy-coded segment: bytes [scan_begin, scan_end) of `files` */
+    int32_t restart_interval;           /* DRI, in MCUs; 0: none */
+    int32_t reserved;
+    uint8_t dc_table[4], ac_table[4];   /* per component (Y, Cb, Cr): its Huffman tables, 0..3 */
+    uint8_t quant[3][64];               /* per component: its quantisation table in zig-zag order, as DQT holds it */
+    uint8_t huff_bits[8][16];           /* DC tables 0..3, then AC tables 0..3: the number of codes of each length 1..16 */
+    uint8_t huff_vals[8][256];          /* their symbols in code order */
+} nsr_jpegdec_frame;
+int nsr_jpegdec_size(int32_t n, int32_t H, int32_t W, int32_t sampling, int64_t max_scan_bytes, int32_t subsequence_bytes,
+                     int64_t *workspace_bytes);
+int nsr_jpegdec_decode(const uint8_t *files, const nsr_jpegdec_frame *descriptors, int32_t n, int32_t H, int32_t W, int32_t sampling,
+                       int32_t subsequence_bytes, void *workspace, int64_t workspace_bytes, uint8_t *out, int32_t *status, void *stream);
+
 /* --- Frame preparation (src/utils/datasets.py:77-113, BaseDataset.__getitem__ after the files are decoded) ---------------------
  * The raw bytes of B frames of one geometry in, the tensors the tracker and the mapper read out: undistortion of the colour image
  * (its own launch, only with distortion coefficients), then ONE launch for the channel order, / 255, the resize of the colour

@@ -76,6 +76,12 @@ class NsrFrameDesc(C.Structure):
                 ("dist", C.c_double * 5), ("png_depth_scale", C.c_double), ("scale", C.c_double)]
 
 
+class NsrJpegDecFrame(C.Structure):
+    _fields_ = [("scan_begin", C.c_int64), ("scan_end", C.c_int64), ("restart_interval", C.c_int32), ("reserved", C.c_int32),
+                ("dc_table", C.c_uint8 * 4), ("ac_table", C.c_uint8 * 4), ("quant", (C.c_uint8 * 64) * 3),
+                ("huff_bits", (C.c_uint8 * 16) * 8), ("huff_vals", (C.c_uint8 * 256) * 8)]
+
+
 class NsrAdamSpan(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("step", C.c_void_p),
                 ("lr", C.c_float), ("pad_", C.c_int32)]
@@ -220,6 +226,9 @@ SYMBOLS = (
     ("nsr_jpeg_size", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("nsr_jpeg_encode", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                   C.c_int64, C.c_void_p, C.c_void_p]),
+    ("nsr_jpegdec_size", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    ("nsr_jpegdec_decode", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     ("nsr_frame_out_size", C.c_int, [C.POINTER(NsrFrameDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("nsr_frame_workspace_bytes", C.c_int64, [C.POINTER(NsrFrameDesc), C.c_int32]),
     ("nsr_frame_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NsrFrameDesc), C.c_int32, C.c_void_p, C.c_void_p,

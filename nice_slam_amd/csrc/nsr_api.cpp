@@ -22,6 +22,7 @@
 #include "../../nice_slam_amd/csrc/nsr_pose.h"
 #include "../../nice_slam_amd/csrc/nsr_trajeval.h"
 #include "../../nice_slam_amd/csrc/nsr_jpeg.h"
+#include "../../nice_slam_amd/csrc/nsr_jpegdec.h"
 
 namespace {
 
@@ -1937,6 +1938,99 @@ int nsr_jpeg_encode(const uint8_t *images, int32_t n, int32_t H, int32_t W, int3
     NSR_LAUNCH(nsr::jpeg_offsets_kernel, dim3(1), dim3(T), scan_lds, stream, P, 1);
     NSR_LAUNCH(nsr::jpeg_stuff_kernel, dim3(P.nint), dim3(T), scan_lds, stream, P);
     return finish("nsr_jpeg_encode");
+}
+
+}  // extern "C"
+
+// ---- JPEG decoding (include/nsr.h, "JPEG decoding") ----
+namespace {
+
+struct JpegDecLayout {
+    long long o_coef, o_planes, o_istart, o_nfound, o_mflags, o_cstat, ws_bytes;
+};
+
+// nullptr: the sizes are valid and P's geometry and L are filled; else what is wrong with them
+const char *jpegdec_geometry(int32_t n, int32_t H, int32_t W, int32_t sampling, int32_t subsequence_bytes, nsr::JpegDecParams &P,
+                             JpegDecLayout &L) {
+    if (n < 0 || n > 65535) return "the batch size must be in [0, 65535]";
+    if (H < 1 || W < 1 || H > 65535 || W > 65535) return "image sizes must be in [1, 65535]";
+    if (sampling < NSR_JPEG_444 || sampling > NSR_JPEG_GREY) return "sampling must be 0 (4:4:4), 1 (4:2:2), 2 (4:2:0) or 3 (one component)";
+    if (subsequence_bytes < 16 || subsequence_bytes > 1024 || subsequence_bytes % 4) return "subsequence_bytes must be a multiple of 4 in [16, 1024]";
+    P.n = n; P.H = H; P.W = W; P.sub_bytes = subsequence_bytes;
+    P.hs = sampling == NSR_JPEG_422 || sampling == NSR_JPEG_420 ? 2 : 1;
+    P.vs = sampling == NSR_JPEG_420 ? 2 : 1;
+    P.ncomp = sampling == NSR_JPEG_GREY ? 1 : 3;
+    P.bpm = P.ncomp == 1 ? 1 : P.hs * P.vs + 2;
+    P.mcux = (W + 8 * P.hs - 1) / (8 * P.hs);
+    P.mcuy = (H + 8 * P.vs - 1) / (8 * P.vs);
+    const long long M = (long long)P.mcux * P.mcuy;
+    P.nblk = M * P.bpm;
+    if (n * P.nblk > 2147483647ll || (long long)n * H * W > (1ll << 38)) return "too many blocks for one call";
+    P.M = (int)M;
+    P.pw_y = P.mcux * P.hs * 8;
+    P.pw_c = P.mcux * 8;
+    P.ph_c = P.mcuy * 8;
+    P.cw = (W + P.hs - 1) / P.hs;
+    P.ch = (H + P.vs - 1) / P.vs;
+    P.poff_c = (long long)P.pw_y * P.mcuy * P.vs * 8;
+    P.plane_bytes = P.poff_c + (P.ncomp == 3 ? 2ll * P.pw_c * P.ph_c : 0ll);
+    L.o_coef = 0;
+    L.o_planes = L.o_coef + 128ll * n * P.nblk;
+    L.o_istart = L.o_planes + round16ll(n * P.plane_bytes);
+    L.o_nfound = L.o_istart + round16ll(4ll * n * (M + 1));
+    L.o_mflags = L.o_nfound + round16ll(4ll * n);
+    L.o_cstat = L.o_mflags + round16ll(4ll * n);
+    L.ws_bytes = L.o_cstat + round16ll(4ll * n * M);
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nsr_jpegdec_size(int32_t n, int32_t H, int32_t W, int32_t sampling, int64_t max_scan_bytes, int32_t subsequence_bytes,
+                     int64_t *workspace_bytes) {
+    nsr::JpegDecParams P;
+    JpegDecLayout L;
+    std::memset(&P, 0, sizeof(P));
+    if (const char *e = jpegdec_geometry(n, H, W, sampling, subsequence_bytes, P, L)) return fail(std::string("nsr_jpegdec_size: ") + e);
+    if (max_scan_bytes < 0 || max_scan_bytes > nsr::kJpdMaxScan) return fail("nsr_jpegdec_size: max_scan_bytes must be in [0, 2^28]");
+    if (!workspace_bytes) return fail("nsr_jpegdec_size: null pointer");
+    *workspace_bytes = L.ws_bytes;
+    return 0;
+}
+
+int nsr_jpegdec_decode(const uint8_t *files, const nsr_jpegdec_frame *descriptors, int32_t n, int32_t H, int32_t W, int32_t sampling,
+                       int32_t subsequence_bytes, void *workspace, int64_t workspace_bytes, uint8_t *out, int32_t *status, void *stream) {
+    nsr::JpegDecParams P;
+    JpegDecLayout L;
+    std::memset(&P, 0, sizeof(P));
+    if (const char *e = jpegdec_geometry(n, H, W, sampling, subsequence_bytes, P, L)) return fail(std::string("nsr_jpegdec_decode: ") + e);
+    if (n == 0) return 0;
+    if (!files || !descriptors || !workspace || !out || !status) return fail("nsr_jpegdec_decode: null pointer");
+    if (workspace_bytes < L.ws_bytes) return fail("nsr_jpegdec_decode: workspace smaller than nsr_jpegdec_size reports");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail("nsr_jpegdec_decode: the workspace must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(descriptors) & 7) return fail("nsr_jpegdec_decode: the descriptors must be 8-byte aligned");
+    char *ws = static_cast<char *>(workspace);
+    P.files = files;
+    P.desc = descriptors;
+    P.coef = reinterpret_cast<short *>(ws + L.o_coef);
+    P.planes = reinterpret_cast<unsigned char *>(ws + L.o_planes);
+    P.istart = reinterpret_cast<int *>(ws + L.o_istart);
+    P.nfound = reinterpret_cast<int *>(ws + L.o_nfound);
+    P.mflags = reinterpret_cast<int *>(ws + L.o_mflags);
+    P.cstat = reinterpret_cast<int *>(ws + L.o_cstat);
+    P.out = out;
+    P.status = status;
+    const int T = nsr::kJpgThreads, scan_lds = nsr::kJpgScanLds + 16;
+    const unsigned gx = (unsigned)(P.M < nsr::kJpdMaxGridX ? P.M : nsr::kJpdMaxGridX);
+    NSR_LAUNCH(nsr::jpegdec_clear_kernel, dim3(nblk(8ll * n * P.nblk, T)), dim3(T), 0, stream, P);
+    NSR_LAUNCH(nsr::jpegdec_markers_kernel, dim3(n), dim3(T), scan_lds, stream, P);
+    NSR_LAUNCH(nsr::jpegdec_huffman_kernel, dim3(gx, n), dim3(nsr::kJpdThreads), nsr::kJpdHuffmanLds, stream, P);
+    NSR_LAUNCH(nsr::jpegdec_dc_kernel, dim3(gx, n), dim3(T), scan_lds, stream, P);
+    NSR_LAUNCH(nsr::jpegdec_idct_kernel, dim3(nblk(n * P.nblk, T)), dim3(T), 0, stream, P);
+    NSR_LAUNCH(nsr::jpegdec_color_kernel, dim3(nblk((long long)n * H * W, T)), dim3(T), 0, stream, P);
+    return finish("nsr_jpegdec_decode");
 }
 
 }  // extern "C"

@@ -10,7 +10,8 @@ the per-frame preparation on the GPU.
     prep = FramePreparer(cfg)                                                  # frames that do not come from a folder
     color, depth = prep.prepare(color_u8, depth_u16, bgr=True)                 # e.g. what cv2.imread returned
 
-The host decodes the files (PIL) and uploads the raw bytes -- u8 colour, u16 (or fp32) depth.  Everything
+The host decodes the files (PIL) and uploads the raw bytes -- u8 colour, u16 (or fp32) depth; with ``decoder="gpu"`` the colour
+files' own bytes are uploaded and decoded on the device (nice_slam_amd.jpeg: the same pixels), depth stays on the host.  Everything
 ``BaseDataset.__getitem__`` (datasets.py:77-113) does after that runs in libnsr.so (include/nsr.h, "Frame preparation"; the
 arithmetic is written out in csrc/nsr_frame.h): the undistortion of the colour image, BGR -> RGB, / 255, the resize to the
 depth image's size, the depth scale, the ``crop_size`` resize, ``crop_edge`` and the cast to fp32.
@@ -173,8 +174,13 @@ class BaseDataset:
     """``ds[i]`` -> (i, colour [H, W, 3], depth [H, W], c2w [4, 4]), fp32 on the device.  Subclasses fill ``color_paths``,
     ``depth_paths`` and ``poses`` (fp32 4 x 4 tensors in the reference's convention, translation NOT yet scaled)."""
 
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine: Optional[Engine] = None):
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine: Optional[Engine] = None, decoder: Optional[str] = None):
         self.name = cfg["dataset"]
+        decoder = (cfg.get("data") or {}).get("decoder", "pil") if decoder is None else decoder
+        if decoder not in ("pil", "gpu"):
+            raise ValueError(f"decoder must be 'pil' or 'gpu' (got {decoder!r})")
+        self.decoder = decoder
+        self.decode_fallbacks = 0                  # frames of decoder="gpu" that went through PIL after all
         self.prep = FramePreparer(cfg, engine=engine, scale=scale, device=device)
         self.device = self.prep.E.device
         self.scale = self.prep.scale
@@ -196,9 +202,15 @@ class BaseDataset:
     def read_raw(self, index: int):
         """(colour u8 [Hc, Wc, 3] RGB, depth u16 or fp32 [Hd, Wd]) as decoded, host arrays"""
         from PIL import Image
-        color_path, depth_path = self.color_paths[index], self.depth_paths[index]
-        with Image.open(color_path) as im:
+        with Image.open(self.color_paths[index]) as im:
             color = np.array(im.convert("RGB"), dtype=np.uint8)
+        depth = self.read_depth(index)
+        return color, depth
+
+    def read_depth(self, index: int):
+        """depth u16 or fp32 [Hd, Wd] as decoded, a host array (read_raw's second value)"""
+        from PIL import Image
+        depth_path = self.depth_paths[index]
         if ".png" in depth_path:
             with Image.open(depth_path) as im:
                 depth = np.array(im)
@@ -212,11 +224,44 @@ class BaseDataset:
             depth = read_exr_depth(depth_path)
         else:
             raise ValueError(f"{depth_path}: depth images are .png or .exr")
-        return color, depth
+        return depth
+
+    def read_color_gpu(self, indices: Sequence[int]) -> torch.Tensor:
+        """u8 [B, Hc, Wc, 3] RGB on the device of the frames' colour files, decoded there (nice_slam_amd.jpeg): the files' bytes are
+        uploaded, not their pixels.  A file the decoder does not take (not a JPEG, progressive, ...; ``jpeg.probe_jpeg`` says why)
+        or whose stream the device reports damaged goes through PIL as in ``read_raw`` -- the pixels are the same either way,
+        and PIL's error is the error of a file nobody can read -- and is counted in ``decode_fallbacks``."""
+        from PIL import Image
+
+        from . import jpeg
+        data = []
+        for i in indices:
+            with open(self.color_paths[i], "rb") as fh:
+                data.append(fh.read())
+        info = [jpeg.probe_jpeg(d) for d in data]
+        out = [None] * len(data)
+        groups = {}                                # frames of one size and sampling decode in one call
+        for k, p in enumerate(info):
+            if p["supported"]:
+                groups.setdefault((p["height"], p["width"], p["sampling"]), []).append(k)
+        for ks in groups.values():
+            frames, status = jpeg.decode_jpeg_status([data[k] for k in ks], engine=self.prep.E)
+            for j, k in enumerate(ks):
+                if status[j] == 0:
+                    out[k] = frames[j]
+        for k, i in enumerate(indices):
+            if out[k] is None:
+                self.decode_fallbacks += 1
+                with Image.open(self.color_paths[i]) as im:
+                    out[k] = torch.from_numpy(np.array(im.convert("RGB"), dtype=np.uint8)).to(self.device)
+        return torch.stack(out)
 
     def load_batch(self, indices: Sequence[int]):
         """(indices, colour [B, H, W, 3], depth [B, H, W], c2w [B, 4, 4]) of several frames, prepared by one launch"""
         indices = [int(i) for i in indices]
+        if self.decoder == "gpu":
+            color, depth = self.prep.prepare(self.read_color_gpu(indices), np.stack([self.read_depth(i) for i in indices]), bgr=False)
+            return indices, color, depth, torch.stack([self.poses[i] for i in indices]).to(self.device)
         raw = [self.read_raw(i) for i in indices]
         color, depth = self.prep.prepare(np.stack([r[0] for r in raw]), np.stack([r[1] for r in raw]), bgr=False)
         return indices, color, depth, torch.stack([self.poses[i] for i in indices]).to(self.device)
@@ -225,13 +270,16 @@ class BaseDataset:
         index = int(index)
         if not 0 <= index < self.n_img:
             raise IndexError(index)
-        color, depth = self.prep.prepare(*self.read_raw(index), bgr=False)
+        if self.decoder == "gpu":
+            color, depth = self.prep.prepare(self.read_color_gpu([index])[0], self.read_depth(index), bgr=False)
+        else:
+            color, depth = self.prep.prepare(*self.read_raw(index), bgr=False)
         return index, color, depth, self.poses[index].to(self.device)
 
 
 class Replica(BaseDataset):
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None):
-        super().__init__(cfg, input_folder, scale, device, engine)
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None):
+        super().__init__(cfg, input_folder, scale, device, engine, decoder)
         self.color_paths = sorted(glob.glob(f"{self.input_folder}/results/frame*.jpg"))
         self.depth_paths = sorted(glob.glob(f"{self.input_folder}/results/depth*.png"))
         with open(f"{self.input_folder}/traj.txt", "r") as f:
@@ -242,8 +290,8 @@ class Replica(BaseDataset):
 
 
 class Azure(BaseDataset):
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None):
-        super().__init__(cfg, input_folder, scale, device, engine)
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None):
+        super().__init__(cfg, input_folder, scale, device, engine, decoder)
         self.color_paths = sorted(glob.glob(os.path.join(self.input_folder, "color", "*.jpg")))
         self.depth_paths = sorted(glob.glob(os.path.join(self.input_folder, "depth", "*.png")))
         path = os.path.join(self.input_folder, "scene", "trajectory.log")
@@ -258,8 +306,8 @@ class Azure(BaseDataset):
 
 
 class ScanNet(BaseDataset):
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None):
-        super().__init__(cfg, input_folder, scale, device, engine)
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None):
+        super().__init__(cfg, input_folder, scale, device, engine, decoder)
         self.input_folder = os.path.join(self.input_folder, "frames")
 
         def number(p):
@@ -275,8 +323,8 @@ class ScanNet(BaseDataset):
 
 
 class CoFusion(BaseDataset):
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None):
-        super().__init__(cfg, input_folder, scale, device, engine)
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None):
+        super().__init__(cfg, input_folder, scale, device, engine, decoder)
         self.color_paths = sorted(glob.glob(os.path.join(self.input_folder, "colour", "*.png")))
         self.depth_paths = sorted(glob.glob(os.path.join(self.input_folder, "depth_noise", "*.exr")))
         self.poses = [torch.eye(4) for _ in self.color_paths]      # the reference's proxy: the frames could not be aligned
@@ -284,8 +332,8 @@ class CoFusion(BaseDataset):
 
 
 class TUM_RGBD(BaseDataset):
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None):
-        super().__init__(cfg, input_folder, scale, device, engine)
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None):
+        super().__init__(cfg, input_folder, scale, device, engine, decoder)
         self.color_paths, self.depth_paths, self.poses = self.loadtum(self.input_folder, frame_rate=32)
         self._finish()
 
@@ -362,7 +410,9 @@ class TUM_RGBD(BaseDataset):
 dataset_dict = {"replica": Replica, "scannet": ScanNet, "cofusion": CoFusion, "azure": Azure, "tumrgbd": TUM_RGBD}
 
 
-def get_dataset(cfg, input_folder=None, scale=None, device="cuda:0", engine: Optional[Engine] = None) -> BaseDataset:
+def get_dataset(cfg, input_folder=None, scale=None, device="cuda:0", engine: Optional[Engine] = None, decoder: Optional[str] = None) -> BaseDataset:
     """The reader of ``cfg['dataset']`` (datasets.py:47-48).  ``input_folder``: instead of ``cfg['data']['input_folder']``
-    (the reference's ``args.input_folder``); ``scale``: instead of ``cfg['scale']``."""
-    return dataset_dict[cfg["dataset"]](cfg, input_folder, scale, device, engine)
+    (the reference's ``args.input_folder``); ``scale``: instead of ``cfg['scale']``.  ``decoder``: "pil" (the default; also
+    ``cfg['data']['decoder']``) decodes the colour files on the host, "gpu" on the device (``BaseDataset.read_color_gpu``); the
+    tensors are the same."""
+    return dataset_dict[cfg["dataset"]](cfg, input_folder, scale, device, engine, decoder)

@@ -17,10 +17,27 @@ twice per batch: the frames' offsets, then exactly the bytes that were used.
 
 ``MjpegWriter`` writes a RIFF AVI 1.0 file (one ``vids`` / ``MJPG`` stream, ``00dc`` chunks, an ``idx1`` index), which ffmpeg, VLC
 and OpenCV read; it stops with an error before the file would pass 2^31 - 1 bytes (OpenDML is not written).
+
+And the way back: baseline JPEG files decoded on the GPU, and the reader of such a video.
+
+    info = jpeg.probe_jpeg(data)                                 # size, sampling, restart interval, supported (and why not)
+    frames = jpeg.decode_jpeg([data0, data1])                    # files (bytes) of one size -> u8 [n, H, W, 3] on the device
+    img = jpeg.read_jpeg("frame000000.jpg")                      # u8 [H, W, 3]
+    with jpeg.MjpegReader("vis.avi") as video:
+        frames = video.read()                                    # u8 [len(video), H, W, 3]
+
+The decoder takes what Pillow writes by default and what the dataset sequences hold: SOF0, 8 bit, Huffman coded, one interleaved
+scan, greyscale or YCbCr at 4:4:4, 4:2:2 or 4:2:0, any tables (optimised ones too), any restart interval or none.  The host walks
+the markers, checks the tables and uploads the files' bytes as they are with one descriptor per file; the entropy decoding (by
+self-synchronising subsequences), the DC sums, the inverse DCT, the upsampling and the colour conversion run in libnsr.so
+(include/nsr.h, "JPEG decoding"; csrc/nsr_jpegdec.h writes the arithmetic out).  The pixels are those of libjpeg-turbo's default
+decoder -- ``np.array(Image.open(f).convert("RGB"))`` -- bit for bit (checked against Pillow 12.2.0 with libjpeg-turbo 3.1,
+``features.version("jpg")`` 6.2).  ``decode_jpeg`` never falls back: a file outside this set, or a damaged stream, raises.
 """
 from __future__ import annotations
 
 import ctypes as C
+import re
 import struct
 from typing import List, Optional
 
@@ -30,7 +47,8 @@ import torch
 from . import _capi
 from .engine import Engine, gpu
 
-__all__ = ["encode_jpeg", "save_jpeg", "MjpegWriter", "quant_tables", "jfif_header", "SUBSAMPLING"]
+__all__ = ["encode_jpeg", "save_jpeg", "MjpegWriter", "quant_tables", "jfif_header", "SUBSAMPLING",
+           "probe_jpeg", "decode_jpeg", "decode_jpeg_status", "read_jpeg", "MjpegReader", "read_video", "SAMPLING"]
 
 SUBSAMPLING = {"4:4:4": 0, "4:2:0": 2}          # the library's codes: PIL's JpegImagePlugin.get_sampling
 MAX_BYTES_PER_LAUNCH = 1 << 31                  # workspace + worst-case output of one library call (a batch is split to stay below)
@@ -227,3 +245,355 @@ class MjpegWriter:
     def __exit__(self, *exc):
         self.close()
         return False
+
+
+# --------------------------------------------------------------------------------------------------
+# decoding
+# --------------------------------------------------------------------------------------------------
+SAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2, "grey": 3}     # the library's codes (the first three are PIL's get_sampling)
+_LUMA_SAMPLING = {(1, 1): "4:4:4", (2, 1): "4:2:2", (2, 2): "4:2:0"}
+_NEXT_MARKER = re.compile(rb"\xff[^\x00\xd0-\xd7\xff]")      # the first marker in entropy-coded data that is no RSTm
+_FRAME_DTYPE = np.dtype([("scan_begin", "<i8"), ("scan_end", "<i8"), ("restart_interval", "<i4"), ("reserved", "<i4"),
+                         ("dc_table", "u1", 4), ("ac_table", "u1", 4), ("quant", "u1", (3, 64)), ("huff_bits", "u1", (8, 16)),
+                         ("huff_vals", "u1", (8, 256))])
+assert _FRAME_DTYPE.itemsize == C.sizeof(_capi.NsrJpegDecFrame)
+_SOF_NAMES = {0xc1: "extended sequential (SOF1)", 0xc2: "progressive (SOF2)", 0xc3: "lossless (SOF3)", 0xc5: "hierarchical (SOF5)",
+              0xc6: "hierarchical (SOF6)", 0xc7: "hierarchical (SOF7)", 0xc9: "arithmetic coding (SOF9)", 0xca: "arithmetic coding (SOF10)",
+              0xcb: "arithmetic coding (SOF11)", 0xcd: "arithmetic coding (SOF13)", 0xce: "arithmetic coding (SOF14)",
+              0xcf: "arithmetic coding (SOF15)", 0xcc: "arithmetic coding (DAC)"}
+
+
+class _Unsupported(Exception):
+    pass
+
+
+def _check_huffman(cls: int, bits, vals):
+    """T.81 annex C: no length holds more codes than are left (the all-ones code stays free, as libjpeg demands), and the
+    symbols are as many as the counts say"""
+    code = 0
+    for length in range(1, 17):
+        code += bits[length - 1]
+        if code > (1 << length) - (1 if bits[length - 1] else 0):
+            raise _Unsupported(f"a Huffman table is oversubscribed at length {length}")
+        code <<= 1
+    if len(vals) != sum(bits) or len(vals) > 256:
+        raise _Unsupported("a Huffman table's symbol count does not match its code counts")
+    if cls == 0 and any(v > 15 for v in vals):
+        raise _Unsupported("a DC Huffman table holds a symbol above 15")
+
+
+def _parse(data: bytes) -> dict:
+    """The header of a JPEG file up to its first scan: {height, width, components, sampling, restart_interval, quant [3][64],
+    dc_table, ac_table, huff {(class, id): (bits, vals)}, scan_begin, scan_end}; ``_Unsupported`` for what the decoder does not take.
+    The size and the sampling factors are in the exception's ``info`` when the frame header was read."""
+    info = {"height": None, "width": None, "components": None, "sampling": None, "restart_interval": 0}
+
+    def refuse(why):
+        e = _Unsupported(why)
+        e.info = info
+        raise e
+
+    if len(data) < 4 or data[:2] != b"\xff\xd8":
+        refuse("not a JPEG file (no SOI)")
+    qt, huff, sof, jfif, adobe, at = {}, {}, None, False, None, 2
+    while True:
+        if at + 4 > len(data):
+            refuse("the file ends before a scan")
+        if data[at] != 0xff:
+            refuse(f"no marker at byte {at}")
+        while data[at + 1] == 0xff and at + 4 < len(data):
+            at += 1
+        m = data[at + 1]
+        if m == 0x01 or 0xd0 <= m <= 0xd8:
+            at += 2
+            continue
+        if m == 0xd9:
+            refuse("EOI before a scan")
+        length = struct.unpack(">H", data[at + 2:at + 4])[0]
+        seg = data[at + 4:at + 2 + length]
+        if length < 2 or len(seg) != length - 2:
+            refuse("a marker segment runs past the file")
+        if m == 0xc0:
+            if sof is not None:
+                refuse("two frame headers")
+            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
+                refuse("a malformed frame header")
+            prec, h, w, nf = struct.unpack(">BHHB", seg[:6])
+            sof = [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(nf)]
+            info.update(height=h, width=w, components=nf)
+            if prec != 8:
+                refuse(f"{prec}-bit samples")
+            if h == 0:
+                refuse("the height comes in a DNL segment")
+            if w == 0:
+                refuse("a width of 0")
+            if nf == 1:
+                if sof[0][1:3] != (1, 1):
+                    refuse(f"one component sampled {sof[0][1]}x{sof[0][2]}")
+                info["sampling"] = "grey"
+            elif nf == 3:
+                if sof[1][1:3] != (1, 1) or sof[2][1:3] != (1, 1) or sof[0][1:3] not in _LUMA_SAMPLING:
+                    refuse("sampling factors " + " ".join(f"{c[1]}x{c[2]}" for c in sof) + " (4:4:4, 4:2:2 and 4:2:0 are decoded)")
+                info["sampling"] = _LUMA_SAMPLING[sof[0][1:3]]
+            else:
+                refuse(f"{nf} components")
+        elif m in _SOF_NAMES:
+            refuse(_SOF_NAMES[m])
+        elif m == 0xc4:
+            p = 0
+            while p < len(seg):
+                if p + 17 > len(seg):
+                    refuse("a malformed DHT segment")
+                cls, tid, bits = seg[p] >> 4, seg[p] & 15, seg[p + 1:p + 17]
+                if cls > 1 or tid > 3:
+                    refuse(f"Huffman table class {cls} id {tid}")
+                vals = seg[p + 17:p + 17 + sum(bits)]
+                try:
+                    _check_huffman(cls, bits, vals)
+                except _Unsupported as e:
+                    refuse(str(e))
+                huff[(cls, tid)] = (bits, vals)
+                p += 17 + len(vals)
+        elif m == 0xdb:
+            p = 0
+            while p < len(seg):
+                if seg[p] >> 4:
+                    refuse("a 16-bit quantisation table")
+                if (seg[p] & 15) > 3 or p + 65 > len(seg):
+                    refuse("a malformed DQT segment")
+                qt[seg[p] & 15] = seg[p + 1:p + 65]
+                p += 65
+        elif m == 0xdd:
+            if len(seg) != 2:
+                refuse("a malformed DRI segment")
+            info["restart_interval"] = struct.unpack(">H", seg)[0]
+        elif m == 0xe0 and seg[:5] == b"JFIF\0":
+            jfif = True
+        elif m == 0xee and seg[:5] == b"Adobe" and len(seg) >= 12:
+            adobe = seg[11]
+        elif m == 0xda:
+            break
+        at += 2 + length
+    if sof is None:
+        refuse("a scan before the frame header")
+    nf = len(sof)
+    if len(seg) < 1 or seg[0] != nf or len(seg) != 4 + 2 * nf:
+        refuse("several scans (the first one does not hold every component)")
+    if nf == 3 and not jfif:                       # libjpeg's rule: JFIF says YCbCr; else Adobe's transform; else the component ids
+        if adobe is not None and adobe != 1:
+            refuse(f"Adobe colour transform {adobe} (RGB or YCCK data)")
+        if adobe is None and [c[0] for c in sof] != [1, 2, 3]:
+            refuse("three components that are not marked as YCbCr")
+    if tuple(seg[1 + 2 * nf:]) != (0, 63, 0):
+        refuse("a scan of part of the spectrum")
+    out = dict(info, quant=[], dc_table=[], ac_table=[], huff=huff)
+    for i, (cid, _, _, tq) in enumerate(sof):
+        if seg[1 + 2 * i] != cid:
+            refuse("the scan's components are not in the frame's order")
+        td, ta = seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15
+        if tq not in qt or (0, td) not in huff or (1, ta) not in huff:
+            refuse("a component refers to a table the file does not define")
+        out["quant"].append(qt[tq])
+        out["dc_table"].append(td)
+        out["ac_table"].append(ta)
+    begin = at + 2 + length
+    hit = _NEXT_MARKER.search(data, begin)
+    if hit is None:
+        end = len(data)                            # no EOI: the stream is cut short, which the device reports
+    else:
+        end = hit.start()
+        if data[end + 1] == 0xdc:
+            refuse("a DNL segment")
+        if data[end + 1] != 0xd9:
+            refuse("several scans")
+    while end > begin and data[end - 1] == 0xff:   # fill bytes before the marker
+        end -= 1
+    if end - begin > 1 << 28:
+        refuse("a scan of more than 2^28 bytes")
+    out.update(scan_begin=begin, scan_end=end)
+    return out
+
+
+def probe_jpeg(data: bytes) -> dict:
+    """What the header of a JPEG file says: ``height``, ``width``, ``components``, ``sampling`` ("4:4:4", "4:2:2", "4:2:0", "grey";
+    None for any other), ``restart_interval`` (MCUs, 0: none), and whether ``decode_jpeg`` takes the file: ``supported``, with the
+    ``reason`` when it does not.  Nothing is launched."""
+    try:
+        p = _parse(bytes(data))
+    except _Unsupported as e:
+        return dict(getattr(e, "info", {}), supported=False, reason=str(e))
+    return {k: p[k] for k in ("height", "width", "components", "sampling", "restart_interval")} | {"supported": True, "reason": None}
+
+
+def jpegdec_size(n: int, H: int, W: int, sampling: str, max_scan_bytes: int = 0, subsequence_bytes: int = 128,
+                 engine: Optional[Engine] = None) -> int:
+    """workspace bytes of one library call that decodes n files of H x W"""
+    ws = C.c_int64(0)
+    (engine or gpu()).lib.call("nsr_jpegdec_size", int(n), int(H), int(W), SAMPLING[sampling], int(max_scan_bytes), int(subsequence_bytes),
+                               C.byref(ws))
+    return ws.value
+
+
+def _descriptors(parsed, offsets) -> np.ndarray:
+    rec = np.zeros(len(parsed), _FRAME_DTYPE)
+    for k, (p, off) in enumerate(zip(parsed, offsets)):
+        rec["scan_begin"][k], rec["scan_end"][k] = off + p["scan_begin"], off + p["scan_end"]
+        rec["restart_interval"][k] = p["restart_interval"]
+        for i in range(p["components"]):
+            rec["dc_table"][k, i], rec["ac_table"][k, i] = p["dc_table"][i], p["ac_table"][i]
+            rec["quant"][k, i] = np.frombuffer(p["quant"][i], np.uint8)
+        for (cls, tid), (bits, vals) in p["huff"].items():
+            rec["huff_bits"][k, 4 * cls + tid] = np.frombuffer(bits, np.uint8)
+            rec["huff_vals"][k, 4 * cls + tid, :len(vals)] = np.frombuffer(vals, np.uint8)
+    return rec
+
+
+def decode_jpeg_status(files, engine: Optional[Engine] = None, subsequence_bytes: int = 128):
+    """``decode_jpeg`` that hands a damaged stream back to the caller instead of raising: (u8 [n, H, W, 3] on the device, the
+    frames' status words as a list).  A frame with a nonzero status has unspecified pixels (include/nsr.h names the bits)."""
+    if isinstance(files, (bytes, bytearray, memoryview)):
+        files = [files]
+    files = [bytes(f) for f in files]
+    E = engine or gpu()
+    if not files:
+        return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=E.device), []
+    parsed = []
+    for k, f in enumerate(files):
+        try:
+            parsed.append(_parse(f))
+        except _Unsupported as e:
+            raise ValueError(f"decode_jpeg: frame {k} is not supported: {e}") from None
+    H, W, sampling = parsed[0]["height"], parsed[0]["width"], parsed[0]["sampling"]
+    for k, p in enumerate(parsed):
+        if (p["height"], p["width"], p["sampling"]) != (H, W, sampling):
+            raise ValueError(f"decode_jpeg: frame {k} is {p['height']} x {p['width']} {p['sampling']}, frame 0 is {H} x {W} {sampling}: "
+                             f"the frames of one call share size and sampling")
+    n = len(files)
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=E.device)
+    status = torch.empty(n, dtype=torch.int32, device=E.device)
+    ws1 = jpegdec_size(1, H, W, sampling, 0, subsequence_bytes, E)
+    step = max(1, min(n, 65535, MAX_BYTES_PER_LAUNCH // max(ws1 + 3 * H * W, 1)))
+    with torch.no_grad(), E.guard():
+        for k0 in range(0, n, step):
+            k1 = min(k0 + step, n)
+            offsets = np.cumsum([0] + [len(f) for f in files[k0:k1]])
+            blob = torch.from_numpy(np.frombuffer(b"".join(files[k0:k1]), np.uint8).copy()).to(E.device)      # the files as they are
+            desc = torch.from_numpy(_descriptors(parsed[k0:k1], offsets).view(np.uint8).reshape(-1)).to(E.device)
+            nws = jpegdec_size(k1 - k0, H, W, sampling, max(p["scan_end"] - p["scan_begin"] for p in parsed[k0:k1]), subsequence_bytes, E)
+            ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=E.device)
+            E.call("nsr_jpegdec_decode", blob.data_ptr(), desc.data_ptr(), k1 - k0, H, W, SAMPLING[sampling], int(subsequence_bytes),
+                   ws.data_ptr(), nws, out[k0:k1].data_ptr(), status[k0:k1].data_ptr())
+    return out, status.cpu().tolist()
+
+
+def decode_jpeg(files, engine: Optional[Engine] = None, subsequence_bytes: int = 128) -> torch.Tensor:
+    """u8 [n, H, W, 3] RGB on the device of n JPEG files (a list of ``bytes``, or one ``bytes`` value for n = 1): Pillow's pixels
+    of ``im.convert("RGB")``, bit for bit.  One library call for the batch.  ``ValueError`` -- the message names the frame -- for a
+    file the decoder does not take (``probe_jpeg`` tells why), for frames of different size or sampling in one call, and for a
+    stream the device found damaged.  There is no other decoder behind this one.  ``subsequence_bytes``: the piece of the stream one
+    lane decodes (a multiple of 4 in [16, 1024]); the pixels do not depend on it."""
+    out, status = decode_jpeg_status(files, engine, subsequence_bytes)
+    for k, st in enumerate(status):
+        if st:
+            raise ValueError(f"decode_jpeg: frame {k} holds a damaged stream (status {st}: "
+                             + ", ".join(w for b, w in ((1, "an invalid Huffman code"), (2, "a coefficient past the block's end"),
+                                                        (4, "a block count other than the header's"), (8, "restart markers out of sequence"))
+                                         if st & b) + ")")
+    return out
+
+
+def read_jpeg(path: str, engine: Optional[Engine] = None) -> torch.Tensor:
+    """u8 [H, W, 3] on the device of one JPEG file"""
+    with open(path, "rb") as fh:
+        return decode_jpeg(fh.read(), engine)[0]
+
+
+class MjpegReader:
+    """The frames of a Motion-JPEG video in a RIFF AVI file, as ``MjpegWriter`` (ffmpeg, OpenCV) writes it: the ``movi`` list is
+    walked once, ``frame_bytes(i)`` is frame i's JPEG file, ``read(indices)`` decodes frames on the device, ``batch`` at a time.
+
+        with MjpegReader("vis.avi") as video:
+            print(len(video), video.width, video.height, video.fps)
+            frames = video.read()                       # u8 [n, H, W, 3]
+    """
+
+    def __init__(self, path: str, engine: Optional[Engine] = None, batch: int = 16):
+        self.path, self.engine, self.batch = path, engine, max(1, int(batch))
+        self.fh = open(path, "rb")
+        try:
+            self._walk()
+        except Exception:
+            self.fh.close()
+            self.fh = None
+            raise
+
+    def _walk(self):
+        fh = self.fh
+        head = fh.read(12)
+        size = fh.seek(0, 2)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"AVI ":
+            raise ValueError(f"MjpegReader: {self.path} is not a RIFF AVI file")
+        self.index, self.width, self.height, self.fps = [], None, None, None      # index: (offset of the data, size) per frame
+
+        def chunks(start, end):
+            at = start
+            while at + 8 <= end:
+                fh.seek(at)
+                fourcc, n = struct.unpack("<4sI", fh.read(8))
+                if at + 8 + n > end:
+                    raise ValueError(f"MjpegReader: {self.path}: chunk {fourcc!r} at byte {at} runs past its parent")
+                yield fourcc, at + 8, n
+                at += 8 + n + (n & 1)
+
+        for fourcc, at, n in chunks(12, min(size, 8 + struct.unpack("<I", head[4:8])[0])):
+            if fourcc != b"LIST":
+                continue
+            fh.seek(at)
+            kind = fh.read(4)
+            if kind == b"hdrl":
+                for cc, a, m in chunks(at + 4, at + n):
+                    if cc == b"avih" and m >= 40:
+                        fh.seek(a)
+                        v = struct.unpack("<10I", fh.read(40))
+                        self.width, self.height = v[8], v[9]
+                        self.fps = 1000000.0 / v[0] if v[0] else None
+            elif kind == b"movi":
+                for cc, a, m in chunks(at + 4, at + n):
+                    if cc[2:] in (b"dc", b"db") and m > 0:
+                        self.index.append((a, m))
+
+    def __len__(self):
+        return len(self.index)
+
+    def frame_bytes(self, i: int) -> bytes:
+        if self.fh is None:
+            raise ValueError("MjpegReader: the file is closed")
+        at, n = self.index[i]
+        self.fh.seek(at)
+        return self.fh.read(n)
+
+    def read(self, indices=None) -> torch.Tensor:
+        """u8 [n, H, W, 3] on the device: the frames ``indices`` (all of them by default), decoded ``batch`` files per call"""
+        indices = list(range(len(self))) if indices is None else [int(i) for i in indices]
+        parts = [decode_jpeg([self.frame_bytes(i) for i in indices[k:k + self.batch]], self.engine) for k in range(0, len(indices), self.batch)]
+        if not parts:
+            return decode_jpeg([], self.engine)
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def close(self):
+        if self.fh is not None:
+            self.fh.close()
+            self.fh = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def read_video(path: str, engine: Optional[Engine] = None) -> torch.Tensor:
+    """u8 [n, H, W, 3] on the device: every frame of a Motion-JPEG AVI file"""
+    with MjpegReader(path, engine) as video:
+        return video.read()

@@ -22,7 +22,9 @@ The figures of the reference's ``Visualizer`` (``tracking_vis/``, ``mapping_vis/
 ``no_vis_on_first_frame``) are drawn by ``imgeval.Visualizer``.  The tracked frame stays one replay: its figures are drawn
 after it, from the pose BEFORE each due iteration -- the motion model's 7-vector, which the frame copies into a ``start``
 buffer, then ``hist[j - 1, 1:]`` -- all of one frame in one ``nsr_figure_sheet`` launch.  An optional ``encoder: gpu`` next to
-``vis_freq`` (``tracking`` / ``mapping``) has the sheets encoded on the GPU too (``jpeg.encode_jpeg``); absent, PIL does it.  The copy is recorded only when some
+``vis_freq`` (``tracking`` / ``mapping``) has the sheets encoded on the GPU too (``jpeg.encode_jpeg``); absent, PIL does it.  An
+optional ``decoder: gpu`` under ``data`` has the sequence's colour JPEGs decoded on the GPU (``jpeg.decode_jpeg``: the same
+pixels; absent, PIL decodes them).  The copy is recorded only when some
 tracked frame of the sequence can have a figure due; a frame (and a mapping call) without one executes what it did before.
 
 Deviations from the reference, all deliberate:
@@ -532,7 +534,7 @@ class NICE_SLAM:
 
         if dataset is None:
             folder = cfg["data"]["input_folder"] if getattr(args, "input_folder", None) is None else args.input_folder
-            dataset = get_dataset(cfg, folder, self.scale, device=self.device)
+            dataset = get_dataset(cfg, folder, self.scale, device=self.device, decoder=cfg["data"].get("decoder", "pil"))
         self.frame_reader = dataset
         self.n_img = len(dataset) if frames is None else max(1, min(int(frames), len(dataset)))
         self.traj = Trajectory(self.n_img, on(self.device))
