@@ -1,7 +1,8 @@
 // nsr_raster.h -- depth rasterization of triangle meshes and the pieces of the 2-D depth metric around it (include/nsr.h,
 // "Depth rasterization"): a tiled z-buffer rasterizer, the per-view depth L1 and the view-acceptance test of the candidate
 // poses (src/tools/eval_recon.py:131-211, calc_2d_metric, which renders with Open3D's OpenGL visualizer, and check_proj).
-// Included by nsr_api.cpp AFTER nsr_recon.h, whose cull_sees it reuses, and nsr_kernels.h, whose device primitives it uses.
+// Included by nsr_api.cpp after nsr_recon.h, whose cull_sees it reuses, and nsr_kernels.h, whose device primitives it uses.
+// The fragment pass of the resolve (raster_tile_pass) is also the replay view's: nsr_view.h runs it with a sink of its own.
 //
 // Numerical contract (tests/raster_reference.py restates it in numpy, in this operation order):
 //   Camera     c2w in the OpenCV convention (x right, y down, z forward: Open3D's extrinsic = inv(c2w)); the caller inverts it
@@ -43,13 +44,18 @@ constexpr int kRasterMaxTiles = 1024;            // per view: images up to 1024 
 constexpr int kRasterViewChunk = 256;            // candidate poses per LDS chunk of the view test
 constexpr unsigned kRasterEmpty = 0x7f800000u;   // +inf: no fragment yet
 
+// min into an LDS cell: 32-bit depth bits, or 64-bit keys (depth bits << 32 | an id: nsr_view.h)
 #if defined(__HIP__)
 typedef __attribute__((address_space(3))) unsigned nsr_luint;
+typedef __attribute__((address_space(3))) unsigned long long nsr_lu64;
 NSR_DEV void raster_lds_min(unsigned *p, unsigned v) {
     __hip_atomic_fetch_min((nsr_luint *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+NSR_DEV void raster_lds_min(unsigned long long *p, unsigned long long v) {
+    __hip_atomic_fetch_min((nsr_lu64 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
 #else
-inline void raster_lds_min(unsigned *p, unsigned v) { if (v < *p) *p = v; }   // the emulator runs one lane at a time
+template <class T> inline void raster_lds_min(T *p, T v) { if (v < *p) *p = v; }   // the emulator runs one lane at a time
 #endif
 
 struct RasterParams {
@@ -257,14 +263,15 @@ NSR_KERNEL void raster_emit_kernel(const RasterParams P) {
     raster_wave_pass<true>(P, k, chunk, wcnt);
 }
 
-// resolve: one block per (tile, view).  LDS layout (bytes)
+// resolve: one block per (tile, view).  LDS layout (bytes), the same for every sink; the z-buffer comes last, sized by its cell
 constexpr int kRzN = 0;                                        // [9][256] double: sign-corrected edge normals
 constexpr int kRzPlane = kRzN + 9 * 8 * kRasterThreads;        // [4][256] double: n, n . V0
 constexpr int kRzDir = kRzPlane + 4 * 8 * kRasterThreads;      // [2][32] double: the tile's ray x and y components
 constexpr int kRzBox = kRzDir + 2 * 8 * kRasterTile;           // [256] int: rows y0 | y1 << 8, cols x0 | x1 << 16 (tile-local)
 constexpr int kRzRows = kRzBox + 2 * 4 * kRasterThreads;       // [2][256 + 1] int: row-count scan (ping-pong)
-constexpr int kRzZ = kRzRows + 2 * 4 * (kRasterThreads + 1);   // [32 * 32] unsigned: the z-buffer
-constexpr int kRasterResolveLds = kRzZ + 4 * kRasterTile * kRasterTile;
+constexpr int kRzZ = kRzRows + 2 * 4 * (kRasterThreads + 1);   // [32 * 32] Sink::Cell: the z-buffer
+static_assert(kRzZ % 8 == 0, "64-bit cells need 8-byte alignment");
+template <class Sink> constexpr int raster_resolve_lds() { return kRzZ + (int)sizeof(typename Sink::Cell) * kRasterTile * kRasterTile; }
 
 NSR_DEV void raster_edge(const float *a, const float *b, double *N) {
     const double ax = a[0], ay = a[1], az = a[2], bx = b[0], by = b[1], bz = b[2];
@@ -273,17 +280,34 @@ NSR_DEV void raster_edge(const float *a, const float *b, double *N) {
     N[2] = ax * by - ay * bx;
 }
 
-NSR_KERNEL void raster_resolve_kernel(const RasterParams P) {
+// The fragments of block (tile, view) into its z-buffer in LDS, from the clear to the last fragment of the last batch of 256
+// bin entries.  Returns the finished z-buffer, the block synchronised.  What a pixel holds is the sink's business:
+//   Cell, kEmpty       the z-buffer cell and its value before any fragment;
+//   kFaceId            whether cell() wants the item's face id (one more load per item);
+//   keeps(num)         whether a face draws at all, by its plane numerator n . V0;
+//   cell(z, face)      what is min-ed into the pixel for a fragment of depth z = (float)Z.
+// All of them are compile-time properties: a sink that keeps every face and ignores the id pays for neither.
+struct RasterDepthSink {                                        // nsr_raster_depth: every face, the bits of (float)Z
+    typedef unsigned Cell;
+    static constexpr Cell kEmpty = kRasterEmpty;
+    static constexpr bool kFaceId = false;
+    NSR_DEV bool keeps(double) const { return true; }
+    NSR_DEV Cell cell(float z, unsigned) const { return __builtin_bit_cast(unsigned, z); }
+};
+constexpr int kRasterResolveLds = raster_resolve_lds<RasterDepthSink>();
+
+template <class Sink>
+NSR_DEV const typename Sink::Cell *raster_tile_pass(const RasterParams &P, const Sink &sink) {
     char *lds = lds_base();
     double *sN = reinterpret_cast<double *>(lds + kRzN);
     double *sP = reinterpret_cast<double *>(lds + kRzPlane);
     double *sD = reinterpret_cast<double *>(lds + kRzDir);
     int *sBox = reinterpret_cast<int *>(lds + kRzBox);
     int *sRows = reinterpret_cast<int *>(lds + kRzRows);
-    unsigned *zb = reinterpret_cast<unsigned *>(lds + kRzZ);
+    typename Sink::Cell *zb = reinterpret_cast<typename Sink::Cell *>(lds + kRzZ);
     const int t = tid(), k = bid_y(), tile = bid_x();
     const int gx0 = (tile % P.tx) * kRasterTile, gy0 = (tile / P.tx) * kRasterTile;
-    for (int e = t; e < kRasterTile * kRasterTile; e += kRasterThreads) zb[e] = kRasterEmpty;
+    for (int e = t; e < kRasterTile * kRasterTile; e += kRasterThreads) zb[e] = Sink::kEmpty;
     if (t < kRasterTile) sD[t] = ((double)(gx0 + t) - P.cx) / P.fx;
     else if (t < 2 * kRasterTile) sD[t] = ((double)(gy0 + t - kRasterTile) - P.cy) / P.fy;
     long long e0 = P.tile_start[(long long)k * P.ntiles + tile], e1 = P.tile_start[(long long)k * P.ntiles + tile + 1];
@@ -316,8 +340,10 @@ NSR_KERNEL void raster_resolve_kernel(const RasterParams P) {
             const double ux = (double)V[1][0] - v0x, uy = (double)V[1][1] - v0y, uz = (double)V[1][2] - v0z;
             const double wx = (double)V[2][0] - v0x, wy = (double)V[2][1] - v0y, wz = (double)V[2][2] - v0z;
             const double nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;
+            const double num = (nx * v0x + ny * v0y) + nz * v0z;
             sP[t] = nx; sP[kRasterThreads + t] = ny; sP[2 * kRasterThreads + t] = nz;
-            sP[3 * kRasterThreads + t] = (nx * v0x + ny * v0y) + nz * v0z;
+            sP[3 * kRasterThreads + t] = num;
+            if (!sink.keeps(num)) nrows = 0;
         }
         // exclusive scan of the row counts: item r of the batch is row r - rows[j] of triangle j, rows[j] <= r < rows[j + 1]
         int cur = 0;
@@ -345,6 +371,7 @@ NSR_KERNEL void raster_resolve_kernel(const RasterParams P) {
             double N[9];
             for (int q = 0; q < 9; ++q) N[q] = sN[q * kRasterThreads + j];
             const double nx = sP[j], ny = sP[kRasterThreads + j], nz = sP[2 * kRasterThreads + j], num = sP[3 * kRasterThreads + j];
+            const unsigned fid = Sink::kFaceId ? (unsigned)P.bins[b0 + j] : 0u;
             for (int x = x0; x <= x1; ++x) {
                 const double dx = sD[x];
                 const double a = (dx * N[0] + dy * N[1]) + N[2];
@@ -354,11 +381,18 @@ NSR_KERNEL void raster_resolve_kernel(const RasterParams P) {
                 if (!(pos || neg) || (a == 0.0 && b == 0.0 && c == 0.0)) continue;
                 const double Z = num / ((nx * dx + ny * dy) + nz);
                 if (!(Z >= P.near && Z <= P.far)) continue;
-                raster_lds_min(zb + row * kRasterTile + x, __builtin_bit_cast(unsigned, (float)Z));
+                raster_lds_min(zb + row * kRasterTile + x, sink.cell((float)Z, fid));
             }
         }
     }
     block_sync();
+    return zb;
+}
+
+NSR_KERNEL void raster_resolve_kernel(const RasterParams P) {
+    const unsigned *zb = raster_tile_pass(P, RasterDepthSink());
+    const int t = tid(), k = bid_y(), tile = bid_x();
+    const int gx0 = (tile % P.tx) * kRasterTile, gy0 = (tile / P.tx) * kRasterTile;
     for (int e = t; e < kRasterTile * kRasterTile; e += kRasterThreads) {
         const int x = gx0 + (e % kRasterTile), y = gy0 + (e / kRasterTile);
         if (x >= P.W || y >= P.H) continue;

@@ -2,7 +2,8 @@
 // reference's visualizer.py draws in an Open3D window (src/tools/viz.py: a shaded mesh with back faces hidden, camera wireframes
 // and trajectories as point clouds).  Three pieces: area-weighted vertex normals, a mesh layer (depth, owning face, shaded colour)
 // over the bins of nsr_raster.h, and a point layer drawn over a base layer with a depth test.
-// Included by nsr_api.cpp AFTER nsr_raster.h, whose parameters, bins, constants and edge function it reuses unchanged.
+// Included by nsr_api.cpp after nsr_raster.h: the mesh layer runs that header's fragment pass (raster_tile_pass) over its
+// parameters and bins with a sink of its own, so coverage, depth and near / far are one piece of code for both.
 //
 // Numerical contract (tests/view_reference.py restates it in numpy, in this operation order):
 //   Normals    per vertex the sum of (V1 - V0) x (V2 - V0) over its incident faces: area-weighted, which is what Open3D's
@@ -11,7 +12,7 @@
 //              (ascending face id; a face that names the vertex twice is listed twice and is degenerate: it adds zeros).  No
 //              atomics: one thread per vertex walks its CSR list.  Stored twice: the fp64 sums, and (float)(s / sqrt((sx sx + sy
 //              sy) + sz sz)) per component; a sum of length 0 (or a non-finite one) stays (0, 0, 0).
-//   Mesh       camera, vertex pass, coverage, edge values, depth, near / far: nsr_raster.h, expression by expression.  Cull mode,
+//   Mesh       camera, vertex pass, coverage, edge values, depth, near / far: nsr_raster.h's own code (raster_tile_pass).  Cull mode,
 //              per face, by the sign of the plane numerator num = n . V0 (n = (V1 - V0) x (V2 - V0), the camera at the origin):
 //              none keeps every face, back keeps the faces with num < 0 (the normal points to the camera: counter-clockwise on
 //              screen in a right-handed frame, OpenGL's front face), front keeps the others.  A culled face produces no fragment;
@@ -37,7 +38,7 @@
 //              takes the point's colour unshaded; every other pixel copies the base.
 //
 // Launches: normals: one thread per vertex.  Mesh: nsr_raster_bin as it is, raster_emit_kernel, then view_resolve_kernel, one
-// block per (tile, view): raster_resolve_kernel's batches with 64-bit keys, then 4 pixels a thread for weights and shading.
+// block per (tile, view): raster_tile_pass with 64-bit keys (ViewKeySink), then 4 pixels a thread for weights and shading.
 // Points: one block per (tile, frame), every thread takes a point per round of 256.  No global atomics, each pixel stored once:
 // every result is bit-identical run to run.
 #pragma once
@@ -48,15 +49,6 @@ constexpr int kViewCullNone = 0, kViewCullBack = 1, kViewCullFront = 2;
 constexpr int kViewMaxPointSize = 64;
 constexpr double kViewAmbient = 0.35;
 constexpr unsigned long long kViewEmpty = ~0ull;
-
-#if defined(__HIP__)
-typedef __attribute__((address_space(3))) unsigned long long nsr_lu64;
-NSR_DEV void view_lds_min(unsigned long long *p, unsigned long long v) {
-    __hip_atomic_fetch_min((nsr_lu64 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-#else
-inline void view_lds_min(unsigned long long *p, unsigned long long v) { if (v < *p) *p = v; }   // the emulator runs one lane at a time
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // Vertex normals
@@ -112,15 +104,19 @@ struct MeshViewParams {
     unsigned char *rgb;              // [K][H][W][3]
 };
 
-// resolve: one block per (tile, view).  LDS layout (bytes): raster_resolve_kernel's, the z-buffer widened to 64-bit keys
-constexpr int kVzN = 0;                                        // [9][256] double
-constexpr int kVzPlane = kVzN + 9 * 8 * kRasterThreads;        // [4][256] double
-constexpr int kVzDir = kVzPlane + 4 * 8 * kRasterThreads;      // [2][32] double
-constexpr int kVzBox = kVzDir + 2 * 8 * kRasterTile;           // [256] int
-constexpr int kVzRows = kVzBox + 2 * 4 * kRasterThreads;       // [2][256 + 1] int (padded to 8 bytes)
-constexpr int kVzKey = kVzRows + 2 * 4 * (kRasterThreads + 1); // [32 * 32] unsigned long long: depth bits << 32 | face id
-constexpr int kViewResolveLds = kVzKey + 8 * kRasterTile * kRasterTile;
-static_assert(kVzKey % 8 == 0, "64-bit keys need 8-byte alignment");
+// the mesh layer's sink of raster_tile_pass: the faces the cull mode keeps, depth bits << 32 | face id
+struct ViewKeySink {
+    typedef unsigned long long Cell;
+    static constexpr Cell kEmpty = kViewEmpty;
+    static constexpr bool kFaceId = true;
+    int cull;
+    NSR_DEV bool keeps(double num) const {
+        const bool facing = num < 0.0;                               // the normal points to the camera
+        return !((cull == kViewCullBack && !facing) || (cull == kViewCullFront && facing));
+    }
+    NSR_DEV Cell cell(float z, unsigned face) const { return ((unsigned long long)__builtin_bit_cast(unsigned, z) << 32) | face; }
+};
+constexpr int kViewResolveLds = raster_resolve_lds<ViewKeySink>();
 
 // the sign-corrected value of edge (a, b) of a face at the ray (dx, dy, 1): the coverage's expression
 NSR_DEV double view_edge_value(const float *Va, const float *Vb, int ia, int ib, double dx, double dy) {
@@ -139,95 +135,11 @@ NSR_DEV unsigned char view_u8(double x) {
 
 NSR_KERNEL void view_resolve_kernel(const MeshViewParams M) {
     const RasterParams &P = M.R;
-    char *lds = lds_base();
-    double *sN = reinterpret_cast<double *>(lds + kVzN);
-    double *sP = reinterpret_cast<double *>(lds + kVzPlane);
-    double *sD = reinterpret_cast<double *>(lds + kVzDir);
-    int *sBox = reinterpret_cast<int *>(lds + kVzBox);
-    int *sRows = reinterpret_cast<int *>(lds + kVzRows);
-    unsigned long long *zb = reinterpret_cast<unsigned long long *>(lds + kVzKey);
+    const unsigned long long *zb = raster_tile_pass(P, ViewKeySink{M.cull});
+    const double *sD = reinterpret_cast<const double *>(lds_base() + kRzDir);
     const int t = tid(), k = bid_y(), tile = bid_x();
     const int gx0 = (tile % P.tx) * kRasterTile, gy0 = (tile / P.tx) * kRasterTile;
-    for (int e = t; e < kRasterTile * kRasterTile; e += kRasterThreads) zb[e] = kViewEmpty;
-    if (t < kRasterTile) sD[t] = ((double)(gx0 + t) - P.cx) / P.fx;
-    else if (t < 2 * kRasterTile) sD[t] = ((double)(gy0 + t - kRasterTile) - P.cy) / P.fy;
-    long long e0 = P.tile_start[(long long)k * P.ntiles + tile], e1 = P.tile_start[(long long)k * P.ntiles + tile + 1];
-    e0 = e0 < 0 ? 0 : e0;
-    e1 = e1 > P.cap ? P.cap : e1;
     const float *cam = P.cam + 4 * (long long)k * P.nv;
-    for (long long b0 = e0; b0 < e1; b0 += kRasterThreads) {
-        block_sync();                                             // the previous batch is no longer read
-        int nrows = 0;
-        const long long f = b0 + t < e1 ? P.bins[b0 + t] : -1;
-        const int i0 = f >= 0 && f < P.nf ? P.faces[3 * f] : -1, i1 = f >= 0 && f < P.nf ? P.faces[3 * f + 1] : -1,
-                  i2 = f >= 0 && f < P.nf ? P.faces[3 * f + 2] : -1;
-        if (i0 >= 0 && i1 >= 0 && i2 >= 0 && i0 < P.nv && i1 < P.nv && i2 < P.nv) {
-            const int *r = P.rect + 2 * ((long long)k * P.nf + f);
-            int x0 = (r[0] & 0xffff) - gx0, x1 = ((r[0] >> 16) & 0xffff) - gx0, y0 = (r[1] & 0xffff) - gy0, y1 = ((r[1] >> 16) & 0xffff) - gy0;
-            x0 = x0 < 0 ? 0 : x0; y0 = y0 < 0 ? 0 : y0;
-            x1 = x1 > kRasterTile - 1 ? kRasterTile - 1 : x1; y1 = y1 > kRasterTile - 1 ? kRasterTile - 1 : y1;
-            nrows = y1 >= y0 && x1 >= x0 ? y1 - y0 + 1 : 0;
-            sBox[t] = y0 | (x0 << 8) | (x1 << 16);
-            const int idx[3] = {i0, i1, i2};
-            const float *V[3] = {cam + 4ll * idx[0], cam + 4ll * idx[1], cam + 4ll * idx[2]};
-            for (int e = 0; e < 3; ++e) {
-                const int a = e, c = (e + 1) % 3;
-                double N[3];
-                const bool canon = idx[a] <= idx[c];
-                raster_edge(canon ? V[a] : V[c], canon ? V[c] : V[a], N);
-                for (int q = 0; q < 3; ++q) sN[(3 * e + q) * kRasterThreads + t] = canon ? N[q] : -N[q];
-            }
-            const double v0x = V[0][0], v0y = V[0][1], v0z = V[0][2];
-            const double ux = (double)V[1][0] - v0x, uy = (double)V[1][1] - v0y, uz = (double)V[1][2] - v0z;
-            const double wx = (double)V[2][0] - v0x, wy = (double)V[2][1] - v0y, wz = (double)V[2][2] - v0z;
-            const double nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;
-            const double num = (nx * v0x + ny * v0y) + nz * v0z;
-            sP[t] = nx; sP[kRasterThreads + t] = ny; sP[2 * kRasterThreads + t] = nz;
-            sP[3 * kRasterThreads + t] = num;
-            const bool facing = num < 0.0;                           // the normal points to the camera
-            if ((M.cull == kViewCullBack && !facing) || (M.cull == kViewCullFront && facing)) nrows = 0;
-        }
-        // exclusive scan of the row counts: item r of the batch is row r - rows[j] of triangle j, rows[j] <= r < rows[j + 1]
-        int cur = 0;
-        sRows[t] = nrows;
-        block_sync();
-        for (int d = 1; d < kRasterThreads; d <<= 1) {
-            const int x = sRows[cur * (kRasterThreads + 1) + t] + (t >= d ? sRows[cur * (kRasterThreads + 1) + t - d] : 0);
-            sRows[(1 - cur) * (kRasterThreads + 1) + t] = x;
-            cur = 1 - cur;
-            block_sync();
-        }
-        const int *incl = sRows + cur * (kRasterThreads + 1);
-        const int total = incl[kRasterThreads - 1];
-        for (int item = t; item < total; item += kRasterThreads) {
-            int lo = 0, hi = kRasterThreads - 1;                     // first j with incl[j] > item
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (incl[mid] > item) hi = mid; else lo = mid + 1;
-            }
-            const int j = lo;
-            const int bx = sBox[j];
-            const int row = (bx & 0xff) + item - (j > 0 ? incl[j - 1] : 0);
-            const int x0 = (bx >> 8) & 0xff, x1 = (bx >> 16) & 0xff;
-            const double dy = sD[kRasterTile + row];
-            double N[9];
-            for (int q = 0; q < 9; ++q) N[q] = sN[q * kRasterThreads + j];
-            const double nx = sP[j], ny = sP[kRasterThreads + j], nz = sP[2 * kRasterThreads + j], num = sP[3 * kRasterThreads + j];
-            const unsigned long long fid = (unsigned)P.bins[b0 + j];
-            for (int x = x0; x <= x1; ++x) {
-                const double dx = sD[x];
-                const double a = (dx * N[0] + dy * N[1]) + N[2];
-                const double b = (dx * N[3] + dy * N[4]) + N[5];
-                const double c = (dx * N[6] + dy * N[7]) + N[8];
-                const bool pos = a >= 0.0 && b >= 0.0 && c >= 0.0, neg = a <= 0.0 && b <= 0.0 && c <= 0.0;
-                if (!(pos || neg) || (a == 0.0 && b == 0.0 && c == 0.0)) continue;
-                const double Z = num / ((nx * dx + ny * dy) + nz);
-                if (!(Z >= P.near && Z <= P.far)) continue;
-                view_lds_min(zb + row * kRasterTile + x, ((unsigned long long)__builtin_bit_cast(unsigned, (float)Z) << 32) | fid);
-            }
-        }
-    }
-    block_sync();
     const float *w = P.w2c + 12 * k;
     for (int e = t; e < kRasterTile * kRasterTile; e += kRasterThreads) {
         const int lx = e % kRasterTile, ly = e / kRasterTile, x = gx0 + lx, y = gy0 + ly;
@@ -322,7 +234,7 @@ NSR_KERNEL void view_points_kernel(const PointViewParams P) {
         for (int yy = y0; yy <= y1; ++yy)
             for (int xx = x0; xx <= x1; ++xx) {
                 const float d = based[(long long)(gy0 + yy) * P.W + gx0 + xx];
-                if (d == 0.f || cz <= d) view_lds_min(zb + yy * kRasterTile + xx, key);
+                if (d == 0.f || cz <= d) raster_lds_min(zb + yy * kRasterTile + xx, key);
             }
     }
     block_sync();

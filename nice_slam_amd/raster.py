@@ -63,16 +63,25 @@ def max_extent(vertices) -> float:
     return float((v.amax(0) - v.amin(0)).max())
 
 
-def _views_per_launch(E: Engine, nv: int, nf: int, H: int, W: int) -> int:
-    ntiles = ((W + 31) // 32) * ((H + 31) // 32)
-    per_view = 16 * nv + 8 * nf + 4 * ntiles * ((nf + 255) // 256) + 8 * ntiles + 16 * nf + 4 * H * W
-    if E.device.type != "cuda":
-        return 8
-    free = torch.cuda.mem_get_info(E.device)[0]
-    return int(max(1, min(MAX_VIEWS_PER_LAUNCH, free // 4 // per_view)))
+def launch_views(E: Engine, scene, H: int, W: int, requested, what: str) -> int:
+    """views drawn per launch of ``scene`` (what ``checked_scene`` returns) at H x W: ``requested``, or what a quarter of the free
+    memory allows, at most 64; never more than the scene has"""
+    nv, nf, K = scene[0].shape[0], scene[1].shape[0], len(scene[2])
+    if requested is not None:
+        step = int(requested)
+    elif E.device.type != "cuda":
+        step = 8
+    else:
+        ntiles = ((W + 31) // 32) * ((H + 31) // 32)
+        per_view = 16 * nv + 8 * nf + 4 * ntiles * ((nf + 255) // 256) + 8 * ntiles + 16 * nf + 4 * H * W
+        step = int(max(1, min(MAX_VIEWS_PER_LAUNCH, torch.cuda.mem_get_info(E.device)[0] // 4 // per_view)))
+    step = min(K, step)
+    if step < 1:
+        raise ValueError(f"{what}: views_per_launch must be positive (got {requested})")
+    return step
 
 
-def _scene(E: Engine, vertices, faces, c2w, near, what: str):
+def checked_scene(E: Engine, vertices, faces, c2w, near, what: str):
     """(vertices fp32, faces int32, w2c [K, 12] fp32, near) on the engine's device, checked: what a batch of views is drawn from"""
     v = E.tensor(vertices, torch.float32, what + ": vertices")
     f = E.faces(faces)
@@ -91,33 +100,45 @@ def _scene(E: Engine, vertices, faces, c2w, near, what: str):
     return v, f, torch.from_numpy(w2c_rows(c2w, np.float64)).to(E.device), near
 
 
+def binned_batches(E: Engine, scene, camera, step: int, what: str):
+    """The views of ``scene`` (what ``checked_scene`` returns) binned ``step`` at a time for ``camera`` = (H, W, fx, fy, cx, cy,
+    near, far): yields (k0, kb, w2c[k0:k0 + kb], workspace, bins, n) per batch, ready for nsr_raster_depth or nsr_view_mesh.  One
+    workspace sized for a full step and one entry counter serve every batch; the bins grow (to n + n // 4) only when a batch
+    needs more, so memory is bounded by one batch whatever K is.  Call it under ``E.guard()``."""
+    v, f, w2c, _ = scene
+    nv, nf = v.shape[0], f.shape[0]
+    nbytes = int(E.lib.nsr_raster_workspace_bytes(nv, nf, step, camera[0], camera[1]))
+    if nbytes < 0:
+        raise _capi.NsrError(f"{what}: unsupported sizes ({nv} vertices, {nf} faces, {camera[0]} x {camera[1]})")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)
+    n_ent = torch.zeros(1, dtype=torch.int64, device=E.device)
+    bins = torch.empty(1, dtype=torch.int32, device=E.device)
+    for k0 in range(0, len(w2c), step):
+        wk = w2c[k0:k0 + step]
+        E.call("nsr_raster_bin", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), len(wk), *camera, ws.data_ptr(), n_ent.data_ptr())
+        n = int(n_ent.item())
+        if n > bins.numel():
+            del bins
+            bins = torch.empty(n + n // 4, dtype=torch.int32, device=E.device)
+        yield k0, len(wk), wk, ws, bins, n
+
+
 def render_depth(vertices, faces, c2w, H=H_REF, W=W_REF, fx=FOCAL_REF, fy=FOCAL_REF, cx=249.5, cy=249.5, near=None, far=FAR_REF,
-                 engine: Optional[Engine] = None) -> torch.Tensor:
+                 engine: Optional[Engine] = None, views_per_launch=None) -> torch.Tensor:
     """Depth images [K, H, W] fp32 on the engine's device of the mesh (vertices [V, 3], faces [F, 3]) seen from each c2w
     ([4, 4] or [K, 4, 4], OpenCV convention: x right, y down, z forward).  Depth is camera-space z, 0 where nothing is drawn;
-    fragments outside [near, far] are discarded; near defaults to 0.01 x the mesh's largest axis-aligned extent."""
+    fragments outside [near, far] are discarded; near defaults to 0.01 x the mesh's largest axis-aligned extent.
+    ``views_per_launch``: as in ``visibility_counts``."""
     E = engine or gpu()
-    lib = E.lib
-    v, f, w2c, near = _scene(E, vertices, faces, c2w, near, "render_depth")
-    K = len(w2c)
-    out = torch.empty((K, int(H), int(W)), dtype=torch.float32, device=E.device)
-    nv, nf = v.shape[0], f.shape[0]
-    step = _views_per_launch(E, nv, nf, int(H), int(W))
-    args = (int(H), int(W), float(fx), float(fy), float(cx), float(cy), float(near), float(far))
+    scene = checked_scene(E, vertices, faces, c2w, near, "render_depth")
+    v, f, w2c, near = scene
+    out = torch.empty((len(w2c), int(H), int(W)), dtype=torch.float32, device=E.device)
+    step = launch_views(E, scene, int(H), int(W), views_per_launch, "render_depth")
+    camera = (int(H), int(W), float(fx), float(fy), float(cx), float(cy), float(near), float(far))
     with torch.no_grad(), E.guard():
-        for k0 in range(0, K, step):
-            kb = min(step, K - k0)
-            nbytes = int(lib.nsr_raster_workspace_bytes(nv, nf, kb, int(H), int(W)))
-            if nbytes < 0:
-                raise _capi.NsrError(f"render_depth: unsupported sizes ({nv} vertices, {nf} faces, {H} x {W})")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)
-            n_ent = torch.zeros(1, dtype=torch.int64, device=E.device)
-            wk = w2c[k0:k0 + kb]
-            E.call("nsr_raster_bin", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), n_ent.data_ptr())
-            n = int(n_ent.item())
-            bins = torch.empty(max(n, 1), dtype=torch.int32, device=E.device)
-            E.call("nsr_raster_depth", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), bins.data_ptr(), n,
-                   out[k0:k0 + kb].data_ptr())
+        for k0, kb, wk, ws, bins, n in binned_batches(E, scene, camera, step, "render_depth"):
+            E.call("nsr_raster_depth", v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], wk.data_ptr(), kb, *camera, ws.data_ptr(),
+                   bins.data_ptr(), n, out[k0:k0 + kb].data_ptr())
     return out
 
 
@@ -388,37 +409,22 @@ def visibility_counts(points, vertices, faces, c2w, H, W, fx, fy, cx, cy, eps=EP
     pixels a side are rendered at 1 / m scale (``raster_div``, default the smallest m that fits: 2 for 680 x 1200) with the
     intrinsics of ``scaled_camera``.  near defaults to 0.01 x the mesh's largest axis-aligned extent."""
     E = engine or gpu()
-    lib = E.lib
     pts = E.tensor(points, what="visibility_counts: points")
-    v, f, w2c, near = _scene(E, vertices, faces, c2w, near, "visibility_counts")
-    K, N, nv, nf = len(w2c), pts.shape[0], v.shape[0], f.shape[0]
+    scene = checked_scene(E, vertices, faces, c2w, near, "visibility_counts")
+    v, f, w2c, near = scene
+    N = pts.shape[0]
     m = raster_divisor(H, W) if raster_div is None else int(raster_div)
     Hs, Ws, fxs, fys, cxs, cys = scaled_camera(H, W, fx, fy, cx, cy, m)
     count = torch.zeros(N, dtype=torch.int32, device=E.device)
     if N == 0:
         return count
-    step = min(K, int(views_per_launch) if views_per_launch is not None else _views_per_launch(E, nv, nf, Hs, Ws))
-    if step < 1:
-        raise ValueError(f"visibility_counts: views_per_launch must be positive (got {views_per_launch})")
-    nbytes = int(lib.nsr_raster_workspace_bytes(nv, nf, step, Hs, Ws))
-    if nbytes < 0:
-        raise _capi.NsrError(f"visibility_counts: unsupported sizes ({nv} vertices, {nf} faces, {Hs} x {Ws})")
-    args = (Hs, Ws, fxs, fys, cxs, cys, float(near), float(far))
+    step = launch_views(E, scene, Hs, Ws, views_per_launch, "visibility_counts")
+    camera = (Hs, Ws, fxs, fys, cxs, cys, float(near), float(far))
     with torch.no_grad(), E.guard():
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)          # one batch's workspace, depth stack and bins,
-        depth = torch.empty((step, Hs, Ws), dtype=torch.float32, device=E.device)   # reused by every batch
-        n_ent = torch.zeros(1, dtype=torch.int64, device=E.device)
-        bins = torch.empty(1, dtype=torch.int32, device=E.device)
-        for k0 in range(0, K, step):
-            kb = min(step, K - k0)
-            wk = w2c[k0:k0 + kb]
-            E.call("nsr_raster_bin", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), n_ent.data_ptr())
-            n = int(n_ent.item())
-            if n > bins.numel():
-                del bins
-                bins = torch.empty(n + n // 4, dtype=torch.int32, device=E.device)
-            E.call("nsr_raster_depth", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), bins.data_ptr(), n,
-                   depth.data_ptr())
+        depth = torch.empty((step, Hs, Ws), dtype=torch.float32, device=E.device)   # one batch's depth stack, reused by every batch
+        for _, kb, wk, ws, bins, n in binned_batches(E, scene, camera, step, "visibility_counts"):
+            E.call("nsr_raster_depth", v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], wk.data_ptr(), kb, *camera, ws.data_ptr(),
+                   bins.data_ptr(), n, depth.data_ptr())
             E.call("nsr_points_visible", pts.data_ptr(), N, int(pts.dtype == torch.float64), wk.data_ptr(), kb, depth.data_ptr(), Hs, Ws,
                    fxs, fys, cxs, cys, float(near), float(far), float(eps), count.data_ptr())
     return count

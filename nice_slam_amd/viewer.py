@@ -39,7 +39,7 @@ import torch
 from . import _capi
 from .engine import Engine, gpu, pose_stack, to_numpy, w2c_rows
 from .ply import read_mesh
-from .raster import _scene, _views_per_launch, max_extent, NEAR_REL
+from .raster import binned_batches, checked_scene, launch_views, max_extent, NEAR_REL
 
 __all__ = ["vertex_normals", "render_mesh", "draw_points", "camera_actor", "viewer_pose", "default_camera", "config_scale", "Replay",
            "replay_run", "save_image", "main"]
@@ -96,20 +96,21 @@ def _u8(E: Engine, a, n: int, what: str) -> torch.Tensor:
 
 
 def render_mesh(vertices, faces, c2w, H=HEIGHT, W=WIDTH, fx=None, fy=None, cx=None, cy=None, colors=None, normals=None, cull=None,
-                near=None, far=FAR, engine: Optional[Engine] = None):
+                near=None, far=FAR, engine: Optional[Engine] = None, views_per_launch=None):
     """(rgb uint8 [K, H, W, 3], depth fp32 [K, H, W], face int32 [K, H, W]) on the engine's device: the mesh seen from each c2w
     ([4, 4] or [K, 4, 4], OpenCV convention), shaded by a headlight.  ``colors``: uint8 [V, 3] vertex colours (None: grey),
     ``normals``: fp32 [V, 3] (None: ``vertex_normals``), ``cull``: None / "none", "back" (hide the faces whose normal
     (V1 - V0) x (V2 - V0) points away from the camera) or "front".  Background: white, depth 0, face -1.  With no culling the
-    depth is ``render_depth``'s bit for bit.  Intrinsics default to ``default_camera(H, W)``; near to 0.01 x the mesh's extent."""
+    depth is ``render_depth``'s bit for bit.  Intrinsics default to ``default_camera(H, W)``; near to 0.01 x the mesh's extent.
+    ``views_per_launch``: as in ``raster.visibility_counts``."""
     E = engine or gpu()
-    lib = E.lib
     if cull not in CULL:
         raise _capi.NsrError(f"render_mesh: bad cull mode {cull!r} (None, 'none', 'back', 'front')")
     H, W = int(H), int(W)
     dfx, dfy, dcx, dcy = default_camera(H, W)
     fx, fy, cx, cy = (float(d if a is None else a) for a, d in ((fx, dfx), (fy, dfy), (cx, dcx), (cy, dcy)))
-    v, f, w2c, near = _scene(E, vertices, faces, c2w, near, "render_mesh")
+    scene = checked_scene(E, vertices, faces, c2w, near, "render_mesh")
+    v, f, w2c, near = scene
     nv, nf, K = v.shape[0], f.shape[0], len(w2c)
     nrm = vertex_normals(v, f, engine=E) if normals is None else E.tensor(normals, torch.float32, "render_mesh: normals")
     if nrm.shape[0] != nv:
@@ -118,21 +119,11 @@ def render_mesh(vertices, faces, c2w, H=HEIGHT, W=WIDTH, fx=None, fy=None, cx=No
     rgb = torch.empty((K, H, W, 3), dtype=torch.uint8, device=E.device)
     depth = torch.empty((K, H, W), dtype=torch.float32, device=E.device)
     face = torch.empty((K, H, W), dtype=torch.int32, device=E.device)
-    step = _views_per_launch(E, nv, nf, H, W)
-    args = (H, W, fx, fy, cx, cy, float(near), float(far))
+    step = launch_views(E, scene, H, W, views_per_launch, "render_mesh")
+    camera = (H, W, fx, fy, cx, cy, float(near), float(far))
     with torch.no_grad(), E.guard():
-        for k0 in range(0, K, step):
-            kb = min(step, K - k0)
-            nbytes = int(lib.nsr_view_workspace_bytes(nv, nf, kb, H, W))
-            if nbytes < 0:
-                raise _capi.NsrError(f"render_mesh: unsupported sizes ({nv} vertices, {nf} faces, {H} x {W})")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)
-            n_ent = torch.zeros(1, dtype=torch.int64, device=E.device)
-            wk = w2c[k0:k0 + kb]
-            E.call("nsr_raster_bin", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), n_ent.data_ptr())
-            n = int(n_ent.item())
-            bins = torch.empty(max(n, 1), dtype=torch.int32, device=E.device)
-            E.call("nsr_view_mesh", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *args, ws.data_ptr(), bins.data_ptr(), n,
+        for k0, kb, wk, ws, bins, n in binned_batches(E, scene, camera, step, "render_mesh"):
+            E.call("nsr_view_mesh", v.data_ptr(), nv, f.data_ptr(), nf, wk.data_ptr(), kb, *camera, ws.data_ptr(), bins.data_ptr(), n,
                    nrm.data_ptr(), None if col is None else col.data_ptr(), CULL[cull], depth[k0:k0 + kb].data_ptr(),
                    face[k0:k0 + kb].data_ptr(), rgb[k0:k0 + kb].data_ptr())
     return rgb, depth, face

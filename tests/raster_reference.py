@@ -153,6 +153,13 @@ def render_views(verts, faces, c2w, H, W, fx, fy, cx, cy, near, far):
     return np.stack([render(verts, faces, w[k], H, W, fx, fy, cx, cy, near, far) for k in range(len(w))])
 
 
+def bin_entries(verts, faces, w2c12, H, W, fx, fy, cx, cy, near, tile=32):
+    """the (face, tile) pairs of one view by this file's pixel boxes: the size of the view's bins up to the boxes' margins"""
+    x0, x1, y0, y1 = _boxes(vertex_pass(verts, w2c12), np.asarray(faces, np.int64), near, H, W, fx, fy, cx, cy)
+    live = (x1 >= x0) & (y1 >= y0)
+    return int(((x1 // tile - x0 // tile + 1) * (y1 // tile - y0 // tile + 1))[live].sum())
+
+
 def depth_l1(a, b):
     """[K] fp64 per-view means: |a - b| in fp64, trees of 256 (pairs t, t + w), block partials summed in order"""
     a = np.asarray(a, F32).reshape(len(a), -1).astype(np.float64)

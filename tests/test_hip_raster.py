@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import raster_reference as R
+from test_raster_emu import check_depth_batches
 from nice_slam_amd import raster
 
 pytestmark = pytest.mark.gpu
@@ -57,6 +58,10 @@ def test_room_matches_restatement(scene):
     l1 = raster.depth_l1(torch.from_numpy(got).cuda(), other).cpu().numpy()
     assert np.array_equal(l1, R.depth_l1(got, other.cpu().numpy()))
     assert np.array_equal(l1, raster.depth_l1(torch.from_numpy(got).cuda(), other).cpu().numpy())
+
+
+def test_batches_of_views():
+    check_depth_batches(None)
 
 
 def test_large_near_triangles():

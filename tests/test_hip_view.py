@@ -12,6 +12,7 @@ import torch
 
 import raster_reference as R
 import view_reference as V
+from test_view_emu import check_mesh_batches
 from nice_slam_amd import raster, viewer
 
 pytestmark = pytest.mark.gpu
@@ -89,6 +90,10 @@ def test_mesh_layer_matches_restatement(scene, cull):
     if cull == "front":                   # a mesh without colours
         grey = viewer.render_mesh(v, f, c2w[:1], H, W, *CAM, cull=cull, near=near, far=far)[0].cpu().numpy()
         check_colour(grey, V.render_mesh_views(v, f, c2w[:1], H, W, *CAM, near, far, nrm, None, cull)[0], "MI355X grey")
+
+
+def test_batches_of_views():
+    check_mesh_batches(None)
 
 
 def test_points_full_frame(scene):

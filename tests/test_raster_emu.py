@@ -13,7 +13,7 @@ from scipy.spatial import ConvexHull
 import emu_harness
 import raster_reference as R
 from nice_slam_amd import _capi, raster, recon
-from nice_slam_amd.engine import Engine
+from nice_slam_amd.engine import Engine, gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "depth_eval.npz")
@@ -83,6 +83,50 @@ def test_depth_matches_restatement(E):
     other = render(E, v[::-1].copy(), (len(v) - 1 - f)[:, ::-1].copy(), c2w, near, far)
     l1 = raster.depth_l1(torch.from_numpy(got), torch.from_numpy(other * np.float32(1.01)), E).numpy()
     assert np.array_equal(l1, R.depth_l1(got, other * np.float32(1.01)))
+
+
+BATCH_NEAR, BATCH_FAR = 0.3, 2.5
+
+
+def batch_case():
+    """the mixed scene and three of eight views, the one with the fewest bin entries last (counted on the CPU with the
+    restatement's pixel boxes): drawn two views a launch, the second batch is smaller than the workspace it reuses and its
+    entries end before the first batch's do in the reused bins"""
+    rng = np.random.default_rng(1)
+    v, f = mixed_scene(rng)
+    cand = views(rng, 8)
+    n = np.array([R.bin_entries(v, f, w, H, W, FX, FY, CX, CY, BATCH_NEAR) for w in R.w2c_rows(cand)])
+    order = np.argsort(n, kind="stable")
+    pick = [order[-1], order[-2], order[0]]
+    assert n[pick[2]] < n[pick[1]] <= n[pick[0]]
+    return v, f, cand[pick]
+
+
+def check_depth_batches(E):
+    """render_depth two views a launch against all three at once and the restatement (E: an engine, None: the GPU's)"""
+    v, f, c2w = batch_case()
+    draw = lambda step: raster.render_depth(v, f, c2w, H, W, FX, FY, CX, CY, near=BATCH_NEAR, far=BATCH_FAR, engine=E,
+                                            views_per_launch=step).cpu().numpy()
+    two = draw(2)
+    assert np.array_equal(two, draw(3))
+    assert np.array_equal(two, R.render_views(v, f, c2w, H, W, FX, FY, CX, CY, BATCH_NEAR, BATCH_FAR))
+    with pytest.raises(ValueError, match="render_depth: views_per_launch must be positive"):
+        draw(0)
+    # the loop itself: batches of 2 and 1 in one workspace and one bin array, the last view's entries the fewest
+    E = E or gpu()
+    scene = raster.checked_scene(E, v, f, c2w, BATCH_NEAR, "test")
+    camera = (H, W, FX, FY, CX, CY, BATCH_NEAR, BATCH_FAR)
+    with E.guard():
+        seen = [(k0, kb, tuple(wk.shape), ws.data_ptr(), bins.data_ptr(), bins.numel(), n)
+                for k0, kb, wk, ws, bins, n in raster.binned_batches(E, scene, camera, 2, "test")]
+        each = [b[5] for b in raster.binned_batches(E, scene, camera, 1, "test")]
+    assert [s[:3] for s in seen] == [(0, 2, (2, 12)), (2, 1, (1, 12))]
+    assert seen[0][3:6] == seen[1][3:6] and seen[0][5] >= seen[0][6]
+    assert [s[6] for s in seen] == [each[0] + each[1], each[2]] and 0 < each[2] < min(each[:2])
+
+
+def test_batches_of_views(E):
+    check_depth_batches(E)
 
 
 def test_watertight_room(E):

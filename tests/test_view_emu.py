@@ -10,7 +10,7 @@ import torch
 import emu_harness
 import raster_reference as R
 import view_reference as V
-from test_raster_emu import CX, CY, FX, FY, H, ROOM_HI, ROOM_LO, W, mixed_scene, views
+from test_raster_emu import BATCH_FAR, BATCH_NEAR, CX, CY, FX, FY, H, ROOM_HI, ROOM_LO, W, batch_case, mixed_scene, views
 from nice_slam_amd import _capi, raster, viewer
 from nice_slam_amd.engine import Engine
 
@@ -185,6 +185,26 @@ def test_room_from_outside_shows_its_far_walls(E):
     rp = viewer.Replay(np.eye(4), width=W, height=H, engine=E)
     rp.update_mesh((v, f))
     assert np.array_equal(rp.mesh["f"].numpy(), flipped)
+
+
+def check_mesh_batches(E):
+    """render_mesh two views a launch against all three at once and the restatement (E: an engine, None: the GPU's)"""
+    v, f, c2w = batch_case()
+    colors = np.random.default_rng(3).integers(0, 256, (len(v), 3), dtype=np.uint8)
+    draw = lambda step: [x.cpu().numpy() for x in viewer.render_mesh(v, f, c2w, H, W, *CAM, colors=colors, cull="back", near=BATCH_NEAR,
+                                                                     far=BATCH_FAR, engine=E, views_per_launch=step)]
+    two = draw(2)
+    assert all(np.array_equal(a, b) for a, b in zip(two, draw(3)))
+    nrm = viewer.vertex_normals(v, f, engine=E).cpu().numpy()
+    want = V.render_mesh_views(v, f, c2w, H, W, *CAM, BATCH_NEAR, BATCH_FAR, nrm, colors, "back")
+    assert np.array_equal(two[1], want[1]) and np.array_equal(two[2], want[2])
+    check_colour(two[0], want[0], "two views a launch")
+    with pytest.raises(ValueError, match="render_mesh: views_per_launch must be positive"):
+        draw(0)
+
+
+def test_batches_of_views(E):
+    check_mesh_batches(E)
 
 
 def test_duplicated_face_is_owned_by_the_smaller_id(E):
