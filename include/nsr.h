@@ -25,6 +25,7 @@
  *   nsr_pack_rows        <- (none) gather / scatter of the voxel rows + blobs that travel in the multi-GPU all-reduce
  *   nsr_mc_* / nsr_point_masks / nsr_cc_* <- src/utils/Mesher.py:53-212,349-574  marching cubes, point_masks, mesh.split
  *   nsr_nn_* / nsr_sample_surface / nsr_dist_stats / nsr_icp_stats / nsr_transform_points / nsr_cull_vertices
+ *   nsr_meshdist_* / nsr_face_normals / nsr_normal_stats
  *                        <- src/tools/eval_recon.py:24-59,91-117, src/tools/cull_mesh.py:45-75  reconstruction evaluation
  *   nsr_raster_* / nsr_depth_error / nsr_view_unseen
  *                        <- src/tools/eval_recon.py:131-211  depth rendering and the 2-D depth metric
@@ -480,6 +481,47 @@ int nsr_transform_points(double *pts, int64_t n, const double *m, void *stream);
  * keep[f] = 1 unless none of the face's vertices is seen (faces [nf][3] int32; nf = 0: no faces). */
 int nsr_cull_vertices(const void *verts, int64_t n, int32_t fp64, const float *w2c, int32_t K, int32_t H, int32_t W, double fx,
                       double fy, double cx, double cy, const int32_t *faces, int64_t nf, uint8_t *seen, uint8_t *keep, void *stream);
+
+/* --- Point-to-mesh distance (no counterpart in the reference: an opt-in estimator of nice_slam_amd.recon) ----------------
+ * The exact distance from every query to a triangle list, the closest point and its face.  verts [nv][3] fp32 (fp64 = 0) or
+ * fp64 (fp64 = 1), faces [nf][3] int32 with every index in [0, nv) (a face with an index outside is ignored), queries [n][3]
+ * fp32 or fp64; everything is computed in fp64, in the expression order written in nice_slam_amd/csrc/nsr_meshdist.h; a
+ * degenerate face counts as its three edges.  dist = sqrt of the smallest per-face squared distance over ALL faces, ties of
+ * bit-equal squared distance -> smallest face index.  Coordinates must be finite.  The index is a cell grid over the box of
+ * the vertices (nsr_nn_bounds), a face registered in every cell its box overlaps; built without atomics.
+ *   nsr_meshdist_plan             HOST: the grid plan for nf faces from the box (HOST copy of bounds[0..5]), NSR_NN_PLAN_DOUBLES
+ *                                 host doubles (nsr_nn_plan's layout: nsr_nn_keys gives the queries' cell keys)
+ *   nsr_meshdist_count            count [nf] int64: cells the face is registered in; over [nf] int64: 1 for a face that would
+ *                                 overlap more than NSR_MESHDIST_CELL_CAP cells (count 0: it goes to the oversize list, which
+ *                                 every query tests), so the pair table holds at most NSR_MESHDIST_CELL_CAP * nf entries
+ *   nsr_meshdist_fill             count_cum [nf]: the INCLUSIVE scan of count, n_pairs its last entry; keys [n_pairs] int64 and
+ *                                 pair_face [n_pairs] int64: every face's (cell key, face) pairs at the face's own offset
+ *   nsr_meshdist_workspace_bytes  device workspace of build / query (-1: invalid, or n_pairs >= 2^31 - 1)
+ *   nsr_meshdist_build            after sorting the keys (sorted_keys, `order`: the stable permutation that sorts them): fills the
+ *                                 workspace; over_cum [nf]: the inclusive scan of over, n_over its last entry
+ *   nsr_meshdist_query            dist [n] fp64, face [n] int64, closest [n][3] fp64, ncand [n] int32 (optional: faces examined,
+ *                                 repeats counted); qorder [n] (optional): the order in which threads take the queries
+ *   nsr_face_normals              normals [nf][3] fp64: (b - a) x (c - a) / its length, the zero vector for a degenerate face
+ *   nsr_normal_stats              out[0] = sum of |query_normals[i] . face_normals[face[i]]|, out[1] = number of pairs in which
+ *                                 neither normal is the zero vector (the others add nothing); the fixed order of nsr_dist_stats;
+ *                                 partial: nsr_recon_partial_doubles(n) doubles of device scratch
+ * plan: HOST everywhere. */
+#define NSR_MESHDIST_CELL_CAP 32
+int nsr_meshdist_plan(const double *bounds, int64_t nf, double *plan);
+int nsr_meshdist_count(const void *verts, int64_t nv, int32_t fp64, const int32_t *faces, int64_t nf, const double *plan, int64_t *count,
+                       int64_t *over, void *stream);
+int nsr_meshdist_fill(const void *verts, int64_t nv, int32_t fp64, const int32_t *faces, int64_t nf, const double *plan,
+                      const int64_t *count_cum, int64_t n_pairs, int64_t *keys, int64_t *pair_face, void *stream);
+int64_t nsr_meshdist_workspace_bytes(const double *plan, int64_t nf, int64_t n_pairs, int64_t n_over);
+int nsr_meshdist_build(const void *verts, int64_t nv, int32_t fp64, const int32_t *faces, int64_t nf, const double *plan,
+                       const int64_t *sorted_keys, const int64_t *order, const int64_t *pair_face, int64_t n_pairs, const int64_t *over,
+                       const int64_t *over_cum, int64_t n_over, void *workspace, void *stream);
+int nsr_meshdist_query(const void *query, int64_t n_query, int32_t fp64, const int64_t *qorder, const double *plan, const void *workspace,
+                       int64_t nf, int64_t n_pairs, int64_t n_over, double *dist, int64_t *face, double *closest, int32_t *ncand,
+                       void *stream);
+int nsr_face_normals(const void *verts, int64_t nv, int32_t fp64, const int32_t *faces, int64_t nf, double *normals, void *stream);
+int nsr_normal_stats(const double *query_normals, const double *face_normals, const int64_t *face, int64_t n, int64_t nf, double *partial,
+                     double *out, void *stream);
 
 /* --- Mesh bound from keyframes (src/utils/Mesher.py:214-279, get_bound_from_frames) -------------------------------------
  * TSDF fusion restating Open3D's legacy ScalableTSDFVolume (units of 16^3 voxels, depth_sampling_stride 4, depth_scale 1,

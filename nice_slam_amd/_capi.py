@@ -172,6 +172,18 @@ SYMBOLS = (
     ("nsr_transform_points", C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_void_p]),
     ("nsr_cull_vertices", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                     C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_meshdist_plan", C.c_int, [C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double)]),
+    ("nsr_meshdist_count", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    ("nsr_meshdist_fill", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_meshdist_workspace_bytes", C.c_int64, [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int64]),
+    ("nsr_meshdist_build", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("nsr_meshdist_query", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_face_normals", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("nsr_normal_stats", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("nsr_tsdf_unit_box", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                     C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     ("nsr_tsdf_workspace_bytes", C.c_int64, [C.POINTER(C.c_int32)]),

@@ -13,6 +13,7 @@
 // (spelled from two levels up: the library build finds it beside this file, the CPU emulator build -- which compiles a copy of
 //  this file elsewhere -- through its include path tests/emu)
 #include "../../nice_slam_amd/csrc/nsr_recon.h"
+#include "../../nice_slam_amd/csrc/nsr_meshdist.h"
 #include "../../nice_slam_amd/csrc/nsr_bound.h"
 #include "../../nice_slam_amd/csrc/nsr_raster.h"
 #include "../../nice_slam_amd/csrc/nsr_view.h"
@@ -1256,6 +1257,166 @@ int nsr_cull_vertices(const void *verts, int64_t n, int32_t fp64, const float *w
     if (n > 0) NSR_LAUNCH(nsr::cull_vertex_kernel, dim3(nblk(n, nsr::kCullThreads)), dim3(nsr::kCullThreads), nsr::kCullChunk * 12 * 4, stream, P);
     if (nf > 0) NSR_LAUNCH(nsr::cull_face_kernel, dim3(nblk(nf, 256)), dim3(256), 0, stream, P);
     return finish("nsr_cull_vertices");
+}
+
+}  // extern "C"
+
+// ---- point-to-mesh distance (include/nsr.h, "Point-to-mesh distance") ----
+namespace {
+
+// workspace of nsr_meshdist_build / nsr_meshdist_query (byte offsets, each 16-byte aligned)
+struct MdLayout { long long tri, pface, olist, fstart, fend, cstart, cend, crep, total; };
+
+MdLayout md_layout(long long nf, long long npairs, long long nover, long long ncell, long long ncoarse) {
+    MdLayout L;
+    L.tri = 0;
+    L.pface = L.tri + align16(72 * nf);
+    L.olist = L.pface + align16(4 * npairs);
+    L.fstart = L.olist + align16(4 * nover);
+    L.fend = L.fstart + align16(4 * ncell);
+    L.cstart = L.fend + align16(4 * ncell);
+    L.cend = L.cstart + align16(4 * ncoarse);
+    L.crep = L.cend + align16(4 * ncoarse);
+    L.total = L.crep + align16(24 * ncoarse);
+    return L;
+}
+
+// the mesh and its grid as MdParams; false with the error set
+bool md_setup(nsr::MdParams &P, const char *who, const double *plan, const void *verts, int64_t nv, int32_t fp64, const int32_t *faces,
+              int64_t nf) {
+    std::memset(&P, 0, sizeof(P));
+    if (nf < 1) { fail(std::string(who) + ": the mesh has no faces"); return false; }
+    if (nv < 1 || nv > 2147483647ll || nf > 2147483647ll / 3) { fail(std::string(who) + ": vertex or face count outside int32 indexing"); return false; }
+    if (!nn_from_plan(P.G, plan, nf)) { fail(std::string(who) + ": invalid plan for this mesh"); return false; }
+    P.verts = verts; P.nv = nv; P.vfp64 = fp64 ? 1 : 0; P.faces = faces; P.nf = nf;
+    return true;
+}
+
+bool md_counts_ok(const char *who, int64_t nf, int64_t npairs, int64_t nover) {
+    if (npairs < 0 || nover < 0 || nover > nf || npairs > (int64_t)nsr::kMdCellCap * nf) { fail(std::string(who) + ": pair or oversize count outside the mesh's range"); return false; }
+    if (npairs >= 2147483647ll) { fail(std::string(who) + ": the pair table overflows int32 indexing"); return false; }
+    return true;
+}
+
+void md_bind_workspace(nsr::MdParams &P, void *workspace) {
+    const MdLayout L = md_layout(P.nf, P.npairs, P.nover, P.G.ncell, P.G.ncoarse);
+    char *w = static_cast<char *>(workspace);
+    P.tri = reinterpret_cast<double *>(w + L.tri);
+    P.pface = reinterpret_cast<int *>(w + L.pface);
+    P.olist = reinterpret_cast<int *>(w + L.olist);
+    P.fstart = reinterpret_cast<int *>(w + L.fstart);
+    P.fend = reinterpret_cast<int *>(w + L.fend);
+    P.cstart = reinterpret_cast<int *>(w + L.cstart);
+    P.cend = reinterpret_cast<int *>(w + L.cend);
+    P.crep = reinterpret_cast<double *>(w + L.crep);
+}
+
+}  // namespace
+
+extern "C" {
+
+int nsr_meshdist_plan(const double *bounds, int64_t nf, double *plan) {
+    if (nf < 1) return fail("nsr_meshdist_plan: the mesh has no faces");
+    if (nf > 2147483647ll / 3) return fail("nsr_meshdist_plan: more faces than int32 indexing holds");
+    if (nsr_nn_plan(bounds, nf, plan) != 0) return fail("nsr_meshdist_plan: no grid for these bounds (" + g_err + ")");
+    return 0;
+}
+
+int64_t nsr_meshdist_workspace_bytes(const double *plan, int64_t nf, int64_t n_pairs, int64_t n_over) {
+    nsr::NnParams G;
+    if (nf < 1 || !nn_from_plan(G, plan, nf) || !md_counts_ok("nsr_meshdist_workspace_bytes", nf, n_pairs, n_over)) return -1;
+    return md_layout(nf, n_pairs, n_over, G.ncell, G.ncoarse).total;
+}
+
+int nsr_meshdist_count(const void *verts, int64_t nv, int32_t fp64, const int32_t *faces, int64_t nf, const double *plan, int64_t *count,
+                       int64_t *over, void *stream) {
+    nsr::MdParams P;
+    if (!md_setup(P, "nsr_meshdist_count", plan, verts, nv, fp64, faces, nf)) return 1;
+    if (!verts || !faces || !count || !over) return fail("nsr_meshdist_count: null pointer");
+    P.count = reinterpret_cast<long long *>(count); P.over = reinterpret_cast<long long *>(over);
+    NSR_LAUNCH(nsr::md_count_kernel, dim3(nblk(nf, 256)), dim3(256), 0, stream, P);
+    return finish("nsr_meshdist_count");
+}
+
+int nsr_meshdist_fill(const void *verts, int64_t nv, int32_t fp64, const int32_t *faces, int64_t nf, const double *plan,
+                      const int64_t *count_cum, int64_t n_pairs, int64_t *keys, int64_t *pair_face, void *stream) {
+    nsr::MdParams P;
+    if (!md_setup(P, "nsr_meshdist_fill", plan, verts, nv, fp64, faces, nf)) return 1;
+    if (!md_counts_ok("nsr_meshdist_fill", nf, n_pairs, 0)) return 1;
+    if (n_pairs == 0) return 0;
+    if (!verts || !faces || !count_cum || !keys || !pair_face) return fail("nsr_meshdist_fill: null pointer");
+    P.cum = reinterpret_cast<const long long *>(count_cum); P.npairs = n_pairs;
+    P.keys = reinterpret_cast<long long *>(keys); P.pair_face = reinterpret_cast<long long *>(pair_face);
+    NSR_LAUNCH(nsr::md_fill_kernel, dim3(nblk(nf, 256)), dim3(256), 0, stream, P);
+    return finish("nsr_meshdist_fill");
+}
+
+int nsr_meshdist_build(const void *verts, int64_t nv, int32_t fp64, const int32_t *faces, int64_t nf, const double *plan,
+                       const int64_t *sorted_keys, const int64_t *order, const int64_t *pair_face, int64_t n_pairs, const int64_t *over,
+                       const int64_t *over_cum, int64_t n_over, void *workspace, void *stream) {
+    nsr::MdParams P;
+    if (!md_setup(P, "nsr_meshdist_build", plan, verts, nv, fp64, faces, nf)) return 1;
+    if (!md_counts_ok("nsr_meshdist_build", nf, n_pairs, n_over)) return 1;
+    if (!verts || !faces || !over || !over_cum || !workspace || (n_pairs > 0 && (!sorted_keys || !order || !pair_face)))
+        return fail("nsr_meshdist_build: null pointer");
+    P.npairs = n_pairs; P.nover = n_over;
+    md_bind_workspace(P, workspace);
+    P.skeys = reinterpret_cast<const long long *>(sorted_keys); P.order = reinterpret_cast<const long long *>(order);
+    P.pairs = reinterpret_cast<const long long *>(pair_face);
+    P.over = const_cast<long long *>(reinterpret_cast<const long long *>(over)); P.ocum = reinterpret_cast<const long long *>(over_cum);
+    const long long nclear = P.G.ncell > P.G.ncoarse ? P.G.ncell : P.G.ncoarse;
+    NSR_LAUNCH(nsr::md_clear_kernel, dim3(nblk(nclear, 256)), dim3(256), 0, stream, P);
+    NSR_LAUNCH(nsr::md_tri_kernel, dim3(nblk(nf, 256)), dim3(256), 0, stream, P);
+    if (n_pairs > 0) NSR_LAUNCH(nsr::md_gather_kernel, dim3(nblk(n_pairs, 256)), dim3(256), 0, stream, P);
+    return finish("nsr_meshdist_build");
+}
+
+int nsr_meshdist_query(const void *query, int64_t n_query, int32_t fp64, const int64_t *qorder, const double *plan, const void *workspace,
+                       int64_t nf, int64_t n_pairs, int64_t n_over, double *dist, int64_t *face, double *closest, int32_t *ncand,
+                       void *stream) {
+    nsr::MdParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (n_query < 0) return fail("nsr_meshdist_query: negative count");
+    if (nf < 1 || !nn_from_plan(P.G, plan, nf)) return fail("nsr_meshdist_query: invalid plan for this mesh");
+    if (!md_counts_ok("nsr_meshdist_query", nf, n_pairs, n_over)) return 1;
+    if (n_query == 0) return 0;
+    if (!query || !workspace || !dist || !face || !closest) return fail("nsr_meshdist_query: null pointer");
+    P.nf = nf; P.npairs = n_pairs; P.nover = n_over;
+    md_bind_workspace(P, const_cast<void *>(workspace));
+    P.q = query; P.n = n_query; P.qfp64 = fp64 ? 1 : 0; P.qorder = reinterpret_cast<const long long *>(qorder);
+    P.dist = dist; P.face = reinterpret_cast<long long *>(face); P.closest = closest; P.ncand = ncand;
+    NSR_LAUNCH(nsr::md_query_kernel, dim3(nblk(n_query, 64)), dim3(64), 0, stream, P);
+    return finish("nsr_meshdist_query");
+}
+
+int nsr_face_normals(const void *verts, int64_t nv, int32_t fp64, const int32_t *faces, int64_t nf, double *normals, void *stream) {
+    if (nv < 0 || nf < 0) return fail("nsr_face_normals: negative count");
+    if (nv > 2147483647ll) return fail("nsr_face_normals: more than 2^31 - 1 vertices");
+    if (nf == 0) return 0;
+    if (!verts || !faces || !normals) return fail("nsr_face_normals: null pointer");
+    nsr::MdNormalParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.verts = verts; P.faces = faces; P.nv = nv; P.nf = nf; P.vfp64 = fp64 ? 1 : 0; P.normals = normals;
+    NSR_LAUNCH(nsr::md_normals_kernel, dim3(nblk(nf, 256)), dim3(256), 0, stream, P);
+    return finish("nsr_face_normals");
+}
+
+int nsr_normal_stats(const double *query_normals, const double *face_normals, const int64_t *face, int64_t n, int64_t nf, double *partial,
+                     double *out, void *stream) {
+    if (n < 0 || nf < 0) return fail("nsr_normal_stats: negative count");
+    if (!partial || !out || (n > 0 && (!query_normals || !face_normals || !face))) return fail("nsr_normal_stats: null pointer");
+    nsr::MdNormalParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.qn = query_normals; P.normals = const_cast<double *>(face_normals); P.face = reinterpret_cast<const long long *>(face);
+    P.n = n; P.nf = nf; P.partial = partial;
+    nsr::RedParams R;
+    std::memset(&R, 0, sizeof(R));
+    R.n = n; R.partial = partial; R.out = out;
+    R.nblocks = (n + nsr::kRedThreads - 1) / nsr::kRedThreads;
+    if (R.nblocks > 0)
+        NSR_LAUNCH(nsr::md_normal_stats_kernel, dim3((unsigned)R.nblocks), dim3(nsr::kRedThreads), 2 * nsr::kRedThreads * 8, stream, P);
+    NSR_LAUNCH(nsr::reduce_final_kernel<nsr::kRedDist>, dim3(1), dim3(64), 0, stream, R);
+    return finish("nsr_normal_stats");
 }
 
 }  // extern "C"

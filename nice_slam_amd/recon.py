@@ -4,8 +4,10 @@
     from nice_slam_amd import recon
     recon.calc_3d_metric("rec.ply", "gt.ply")      # {accuracy_cm, completion_cm, completion_ratio_pct}
     recon.calc_2d_metric("rec.ply", "gt.ply")      # {depth_l1_cm, per_view}  (nice_slam_amd/raster.py)
+    recon.calc_3d_metric("rec.ply", "gt.ply", surface="mesh")   # point-to-MESH distances: + precision / recall / F-score,
+                                                                # normal consistency (surface_metrics; not the reference's metric)
 
-    python -m nice_slam_amd.recon eval --rec_mesh R --gt_mesh G -3d
+    python -m nice_slam_amd.recon eval --rec_mesh R --gt_mesh G -3d [--surface mesh [--thresholds T ...] [--error_mesh OUT.ply]]
     python -m nice_slam_amd.recon depth --rec_mesh R --gt_mesh G
     python -m nice_slam_amd.recon cull --input_mesh M --traj traj.txt --output_mesh OUT [--occlusion]
     python -m nice_slam_amd.recon unseen --gt_mesh G --traj traj.txt --output G_pc_unseen.npy
@@ -25,7 +27,11 @@ Deviations from the reference (also in INTEGRATION.md):
     rasterizer, not Open3D's OpenGL depth buffer; its own deviations are listed in raster.py;
   * ``cull_mesh(occlusion=True)`` (``cull --occlusion``) also drops what the mesh itself hides from every camera, a test
     cull_mesh.py does not have; off by default.  ``unseen_points`` (``unseen``) makes the ``_pc_unseen.npy`` cloud of a ground
-    truth, which the reference ships only for its own scenes.
+    truth, which the reference ships only for its own scenes;
+  * ``surface="mesh"`` (``eval -3d --surface mesh``, ``surface_metrics``, ``MeshIndex``, ``error_mesh``) measures from each sample
+    to the other MESH (nsr_meshdist_*: the exact point-to-triangle distance) instead of to the other sample cloud.  This is
+    NOT the reference's metric: it has no sampling floor, so its accuracy and completion are smaller.  Opt-in; the default
+    is the reference's estimator, unchanged.
 """
 from __future__ import annotations
 
@@ -45,7 +51,7 @@ from .ply import read_mesh, write_ply
 __all__ = ["nearest", "accuracy", "completion", "completion_ratio", "recon_metrics", "sample_surface", "align_icp",
            "calc_3d_metric", "cull_mesh", "load_poses", "read_mesh", "NNIndex",
            "render_depth", "depth_l1", "cam_position", "sample_views", "calc_2d_metric", "cull_masks", "visibility_counts",
-           "unseen_points"]
+           "unseen_points", "MeshIndex", "mesh_distance", "face_normals", "surface_metrics", "error_mesh"]
 
 
 # --------------------------------------------------------------------------------------------------
@@ -245,14 +251,174 @@ def align_icp(source, target, threshold=0.1, init=None, max_iteration=30, relati
 
 
 # --------------------------------------------------------------------------------------------------
+# point-to-mesh distance (no counterpart in the reference: opt-in)
+# --------------------------------------------------------------------------------------------------
+class MeshIndex:
+    """Exact point-to-triangle-mesh distance: a uniform cell grid over the box of ``vertices`` [V, 3] (fp32 or fp64) with every
+    face of ``faces`` [F, 3] registered in the cells its box overlaps, built on the device without atomics.
+    ``query(points)`` -> (dist fp64 [N], face int64 [N], closest fp64 [N, 3]): the minimum over ALL faces of the per-face
+    distance (csrc/nsr_meshdist.h), in fp64, ties to the smallest face index; a degenerate face counts as its edges."""
+
+    def __init__(self, vertices, faces, engine: Optional[Engine] = None):
+        E = self.engine = engine or gpu()
+        lib = E.lib
+        v = self.vertices = E.tensor(vertices, what="mesh_distance: vertices")
+        f = self.faces = E.faces(faces)
+        V, F = v.shape[0], f.shape[0]
+        if F == 0 or V == 0:
+            raise ValueError("mesh_distance: the mesh has no faces")
+        if not bool(torch.isfinite(v).all()):
+            raise ValueError("mesh_distance: vertex coordinates must be finite")
+        if int(f.min()) < 0 or int(f.max()) >= V:
+            raise ValueError("mesh_distance: face index outside the vertex array")
+        self.nf = F
+        self.fp64 = int(v.dtype == torch.float64)
+        mesh = (v.data_ptr(), V, self.fp64, f.data_ptr(), F)
+        with torch.no_grad(), E.guard():
+            bounds = torch.empty(6 * 257, dtype=torch.float64, device=E.device)
+            E.call("nsr_nn_bounds", v.data_ptr(), V, self.fp64, bounds.data_ptr())
+            self.plan = (C.c_double * 16)()
+            lib.call("nsr_meshdist_plan", c_doubles(bounds[:6].cpu().numpy()), F, self.plan)
+            count = torch.empty(F, dtype=torch.int64, device=E.device)
+            over = torch.empty(F, dtype=torch.int64, device=E.device)
+            E.call("nsr_meshdist_count", *mesh, self.plan, count.data_ptr(), over.data_ptr())
+            cum, ocum = torch.cumsum(count, 0), torch.cumsum(over, 0)
+            self.npairs, self.nover = int(cum[-1]), int(ocum[-1])
+            nbytes = lib.nsr_meshdist_workspace_bytes(self.plan, F, self.npairs, self.nover)
+            if nbytes < 0:
+                raise _capi.NsrError(f"mesh_distance: {self.npairs} (cell, face) pairs overflow the index's int32 tables")
+            keys = torch.empty(self.npairs, dtype=torch.int64, device=E.device)
+            pair_face = torch.empty(self.npairs, dtype=torch.int64, device=E.device)
+            E.call("nsr_meshdist_fill", *mesh, self.plan, cum.data_ptr(), self.npairs, keys.data_ptr(), pair_face.data_ptr())
+            sk, order = torch.sort(keys, stable=True)
+            self.ws = torch.empty(int(nbytes), dtype=torch.uint8, device=E.device)
+            E.call("nsr_meshdist_build", *mesh, self.plan, sk.data_ptr(), order.contiguous().data_ptr(), pair_face.data_ptr(), self.npairs,
+                   over.data_ptr(), ocum.data_ptr(), self.nover, self.ws.data_ptr())
+
+    def query(self, points, with_candidates: bool = False):
+        """(dist, face, closest[, ncand int32 [N]: faces examined, repeats counted])"""
+        E = self.engine
+        qt = E.tensor(points, what="mesh_distance: query")
+        N = qt.shape[0]
+        dist = torch.empty(N, dtype=torch.float64, device=E.device)
+        face = torch.empty(N, dtype=torch.int64, device=E.device)
+        closest = torch.empty((N, 3), dtype=torch.float64, device=E.device)
+        ncand = torch.empty(N, dtype=torch.int32, device=E.device) if with_candidates else None
+        if N:
+            if not bool(torch.isfinite(qt).all()):
+                raise ValueError("mesh_distance: query coordinates must be finite")
+            fp64 = int(qt.dtype == torch.float64)
+            with torch.no_grad(), E.guard():
+                keys = torch.empty(N, dtype=torch.int64, device=E.device)
+                E.call("nsr_nn_keys", qt.data_ptr(), N, fp64, self.plan, keys.data_ptr())
+                qorder = torch.sort(keys, stable=True)[1].contiguous()
+                E.call("nsr_meshdist_query", qt.data_ptr(), N, fp64, qorder.data_ptr(), self.plan, self.ws.data_ptr(), self.nf, self.npairs,
+                       self.nover, dist.data_ptr(), face.data_ptr(), closest.data_ptr(), None if ncand is None else ncand.data_ptr())
+        return (dist, face, closest, ncand) if with_candidates else (dist, face, closest)
+
+
+def mesh_distance(points, vertices, faces, engine: Optional[Engine] = None):
+    """(dist fp64 [N], face int64 [N], closest fp64 [N, 3]): for every point the nearest point of the triangle mesh."""
+    return MeshIndex(vertices, faces, engine).query(points)
+
+
+def face_normals(vertices, faces, engine: Optional[Engine] = None) -> torch.Tensor:
+    """Unit normals fp64 [F, 3] of the faces, (v1 - v0) x (v2 - v0) normalised; the zero vector for a degenerate face."""
+    E = engine or gpu()
+    v = E.tensor(vertices, what="face_normals: vertices")
+    f = E.faces(faces)
+    n = torch.empty((f.shape[0], 3), dtype=torch.float64, device=E.device)
+    with torch.no_grad(), E.guard():
+        E.call("nsr_face_normals", v.data_ptr(), v.shape[0], int(v.dtype == torch.float64), f.data_ptr(), f.shape[0], n.data_ptr())
+    return n
+
+
+def _normal_stats(E: Engine, sample_normals: torch.Tensor, fnormals: torch.Tensor, face: torch.Tensor):
+    """(sum of |n . m|, valid pairs) of the samples' normals against the normals of the faces the search returned"""
+    n = face.shape[0]
+    qn = sample_normals.contiguous()
+    partial = torch.empty(int(E.lib.nsr_recon_partial_doubles(n)), dtype=torch.float64, device=E.device)
+    out = torch.empty(2, dtype=torch.float64, device=E.device)
+    with E.guard():
+        E.call("nsr_normal_stats", qn.data_ptr(), fnormals.data_ptr(), face.data_ptr(), n, fnormals.shape[0], partial.data_ptr(), out.data_ptr())
+    s, c = (float(x) for x in out.cpu())
+    return s, c
+
+
+def _aligned_meshes(E: Engine, rec_mesh, gt_mesh, align: bool):
+    rv, rf = E.mesh(rec_mesh)
+    gv, gf = E.mesh(gt_mesh)
+    if align:
+        T = align_icp(rv, gv, 0.1, engine=E)[0]
+        rv = rv.clone()
+        E.transform(rv, T)
+    return rv, rf, gv, gf
+
+
+def surface_metrics(rec_mesh, gt_mesh, align=True, n_points=200000, seed=0, thresholds=(0.05,), engine: Optional[Engine] = None):
+    """The 3-D metrics with point-to-MESH distances: the ICP alignment and the seeded samples of ``calc_3d_metric``, but accuracy
+    measures from each reconstruction sample to the ground-truth mesh and completion from each ground-truth sample to the
+    reconstructed mesh, so the sampling spacing of the other surface does not enter.  NOT the reference's estimator.
+    Returns accuracy_cm, completion_cm, chamfer_cm (their mean), completion_ratio_pct (at 0.05 m); per threshold t of
+    ``thresholds`` [m] the dicts precision_pct[t] (reconstruction samples closer than t), recall_pct[t] (ground-truth samples
+    closer than t) and fscore_pct[t] = 2PR / (P + R) (0 when P + R = 0); normal_consistency: the mean over the two directions of
+    the mean |n . m| of a sample's face normal against the normal of its nearest face, and normal_pairs: the pairs that
+    entered it (a pair with a degenerate face on either side does not)."""
+    E = engine or gpu()
+    rv, rf, gv, gf = _aligned_meshes(E, rec_mesh, gt_mesh, align)
+    rec_pts, rec_fi = sample_surface(rv, rf, n_points, seed=seed, engine=E)
+    gt_pts, gt_fi = sample_surface(gv, gf, n_points, seed=seed + 1, engine=E)
+    d_acc, f_acc, _ = MeshIndex(gv, gf, E).query(rec_pts)
+    d_comp, f_comp, _ = MeshIndex(rv, rf, E).query(gt_pts)
+    n = int(n_points)
+    acc, comp = _mean(E, d_acc), _mean(E, d_comp)
+    out = {"accuracy_cm": acc * 100, "completion_cm": comp * 100, "chamfer_cm": (acc * 100 + comp * 100) / 2,
+           "completion_ratio_pct": (_dist_stats(E, d_comp, 0.05)[1] / n if n else float("nan")) * 100,
+           "precision_pct": {}, "recall_pct": {}, "fscore_pct": {}}
+    for t in thresholds:
+        t = float(t)
+        p = (_dist_stats(E, d_acc, t)[1] / n if n else float("nan")) * 100
+        r = (_dist_stats(E, d_comp, t)[1] / n if n else float("nan")) * 100
+        out["precision_pct"][t], out["recall_pct"][t] = p, r
+        out["fscore_pct"][t] = 2 * p * r / (p + r) if p + r > 0 else 0.0
+    rn, gn = face_normals(rv, rf, E), face_normals(gv, gf, E)
+    s_a, c_a = _normal_stats(E, rn[rec_fi], gn, f_acc)
+    s_c, c_c = _normal_stats(E, gn[gt_fi], rn, f_comp)
+    means = [s / c for s, c in ((s_a, c_a), (s_c, c_c)) if c > 0]
+    out["normal_consistency"] = sum(means) / len(means) if means else float("nan")
+    out["normal_pairs"] = int(c_a + c_c)
+    return out
+
+
+def error_mesh(rec_mesh, gt_mesh, path: Optional[str] = None, vmax=0.05, align=False, engine: Optional[Engine] = None):
+    """Distance fp64 [V] of every vertex of the reconstruction to the ground-truth MESH; with ``path`` the reconstruction is
+    written there as a PLY whose vertices carry the distance through the figures' plasma map (0 -> its first entry, ``vmax``
+    [m] and beyond -> its last).  ``align``: ICP-align the reconstruction first, as the metrics do."""
+    from .imgeval import colorize_depth
+    E = engine or gpu()
+    rv, rf, gv, gf = _aligned_meshes(E, rec_mesh, gt_mesh, align)
+    d = MeshIndex(gv, gf, E).query(rv)[0]
+    if path is not None:
+        rgb = colorize_depth(d.float().reshape(1, -1), vmax=float(vmax), engine=E)[0] if d.shape[0] else torch.empty((0, 3), dtype=torch.uint8)
+        write_ply(path, rv.cpu().numpy(), rf.cpu().numpy(), colors=rgb.cpu().numpy())
+    return d
+
+
+# --------------------------------------------------------------------------------------------------
 # the 3-D metric (eval_recon.py:91-117)
 # --------------------------------------------------------------------------------------------------
-def calc_3d_metric(rec_mesh, gt_mesh, align=True, n_points=200000, seed=0, engine: Optional[Engine] = None):
+def calc_3d_metric(rec_mesh, gt_mesh, align=True, n_points=200000, seed=0, engine: Optional[Engine] = None, surface="points",
+                   thresholds=(0.05,)):
     """Accuracy [cm], completion [cm] and completion ratio [%] of a reconstructed mesh against the ground truth, as
     eval_recon.py's calc_3d_metric: (optionally) ICP-align the reconstruction's vertices to the ground truth's, sample
     ``n_points`` on each surface, then two nearest-neighbour passes.  Meshes: PLY paths or (vertices, faces) pairs (e.g. the
     device tensors ``Mesher.get_mesh`` returns).  The samplers are seeded (``seed`` for the reconstruction, ``seed + 1`` for
-    the ground truth)."""
+    the ground truth).  ``surface="mesh"``: the point-to-mesh estimator instead, ``surface_metrics``' dict (``thresholds`` goes
+    there); not the reference's metric."""
+    if surface == "mesh":
+        return surface_metrics(rec_mesh, gt_mesh, align=align, n_points=n_points, seed=seed, thresholds=thresholds, engine=engine)
+    if surface != "points":
+        raise ValueError(f"calc_3d_metric: surface must be 'points' or 'mesh' (got {surface!r})")
     E = engine or gpu()
     rv, rf = E.mesh(rec_mesh)
     gv, gf = E.mesh(gt_mesh)
@@ -352,6 +518,12 @@ def main(argv=None):
     ev.add_argument("-2d", "--metric_2d", action="store_true", help="enable 2D metric (not available)")
     ev.add_argument("-3d", "--metric_3d", action="store_true", help="enable 3D metric")
     ev.add_argument("--seed", type=int, default=0, help="seed of the surface samplers")
+    ev.add_argument("--n_points", type=int, default=200000, help="surface samples per mesh")
+    ev.add_argument("--surface", choices=("points", "mesh"), default=None,
+                    help="mesh: point-to-mesh distances, with F-score and normal consistency (not the reference's metric)")
+    ev.add_argument("--thresholds", type=float, nargs="+", default=[0.05], help="with --surface mesh: F-score thresholds (m)")
+    ev.add_argument("--error_mesh", type=str, default=None,
+                    help="with --surface mesh: write the aligned reconstruction coloured by its distance to the ground-truth mesh")
     de = sub.add_parser("depth", help="eval_recon.py calc_2d_metric: Depth L1 of a reconstructed mesh")
     de.add_argument("--rec_mesh", type=str, required=True, help="reconstructed mesh file path")
     de.add_argument("--gt_mesh", type=str, required=True, help="ground truth mesh file path")
@@ -380,11 +552,25 @@ def main(argv=None):
         if args.metric_2d:
             raise NotImplementedError("eval -2d is not wired to the rasterizer: the 2-D depth metric (eval_recon.py calc_2d_metric) "
                                       "is `python -m nice_slam_amd.recon depth --rec_mesh R --gt_mesh G`")
+        if args.surface != "mesh" and (args.error_mesh or args.thresholds != [0.05]):
+            raise SystemExit("recon eval: --thresholds and --error_mesh need --surface mesh")
         if args.metric_3d:
-            m = calc_3d_metric(args.rec_mesh, args.gt_mesh, seed=args.seed)
+            m = calc_3d_metric(args.rec_mesh, args.gt_mesh, n_points=args.n_points, seed=args.seed, surface=args.surface or "points",
+                               thresholds=args.thresholds)
             print("accuracy: ", m["accuracy_cm"])
             print("completion: ", m["completion_cm"])
             print("completion ratio: ", m["completion_ratio_pct"])
+            if args.surface == "mesh":
+                print("chamfer: ", m["chamfer_cm"])
+                for t in m["fscore_pct"]:
+                    print(f"precision@{t}: ", m["precision_pct"][t])
+                    print(f"recall@{t}: ", m["recall_pct"][t])
+                    print(f"f-score@{t}: ", m["fscore_pct"][t])
+                print("normal consistency: ", m["normal_consistency"])
+                print("normal pairs: ", m["normal_pairs"])
+            if args.error_mesh:
+                d = error_mesh(args.rec_mesh, args.gt_mesh, args.error_mesh, align=True)
+                print("error mesh: ", args.error_mesh, "max", float(d.max()) if d.shape[0] else 0.0)
     elif args.cmd == "depth":
         unseen = False if args.no_unseen else args.unseen
         m = calc_2d_metric(args.rec_mesh, args.gt_mesh, align=not args.no_align, n_imgs=args.n_imgs, unseen=unseen, seed=args.seed)
