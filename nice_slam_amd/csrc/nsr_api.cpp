@@ -1007,52 +1007,73 @@ namespace {
 
 inline long long align16(long long b) { return (b + 15) & ~15ll; }
 
-struct NnLayout { long long sref, sidx, fstart, fend, cstart, cend, cbox, total; };
+// the four run tables of a grid (nsr::NnGrid) inside an index's workspace: byte offsets from `at`, each 16-byte aligned
+struct RunLayout { long long fstart, fend, cstart, cend, end; };
 
-NnLayout nn_layout(long long m, long long ncell, long long ncoarse) {
+RunLayout run_layout(long long at, const nsr::NnGrid &G) {
+    RunLayout R;
+    R.fstart = at;
+    R.fend = R.fstart + align16(4 * G.ncell);
+    R.cstart = R.fend + align16(4 * G.ncell);
+    R.cend = R.cstart + align16(4 * G.ncoarse);
+    R.end = R.cend + align16(4 * G.ncoarse);
+    return R;
+}
+
+void bind_runs(nsr::NnGrid &G, char *w, const RunLayout &R) {
+    G.fstart = reinterpret_cast<int *>(w + R.fstart);
+    G.fend = reinterpret_cast<int *>(w + R.fend);
+    G.cstart = reinterpret_cast<int *>(w + R.cstart);
+    G.cend = reinterpret_cast<int *>(w + R.cend);
+}
+
+struct NnLayout { long long sref, sidx; RunLayout runs; long long cbox, total; };
+
+NnLayout nn_layout(long long m, const nsr::NnGrid &G) {
     NnLayout L;
     L.sref = 0;
     L.sidx = L.sref + align16(24 * m);
-    L.fstart = L.sidx + align16(8 * m);
-    L.fend = L.fstart + align16(4 * ncell);
-    L.cstart = L.fend + align16(4 * ncell);
-    L.cend = L.cstart + align16(4 * ncoarse);
-    L.cbox = L.cend + align16(4 * ncoarse);
-    L.total = L.cbox + align16(48 * ncoarse);
+    L.runs = run_layout(L.sidx + align16(8 * m), G);
+    L.cbox = L.runs.end;
+    L.total = L.cbox + align16(48 * G.ncoarse);
     return L;
 }
 
-// the plan as NnParams; false if it is not one nsr_nn_plan could have written for m points (m < 0: for any number of points)
-bool nn_from_plan(nsr::NnParams &P, const double *plan, long long m) {
-    std::memset(&P, 0, sizeof(P));
+// the plan as a grid (its run tables unbound); false if it is not one nsr_nn_plan could have written for m points (m < 0: for
+// any number of points)
+bool grid_from_plan(nsr::NnGrid &G, const double *plan, long long m) {
+    std::memset(&G, 0, sizeof(G));
     if (!plan || m == 0) return false;
     for (int d = 0; d < 3; ++d) {
-        P.lo[d] = plan[nsr::kNnLo + d];
-        P.hi[d] = plan[nsr::kNnHi + d];
+        G.lo[d] = plan[nsr::kNnLo + d];
+        G.hi[d] = plan[nsr::kNnHi + d];
         const double n = plan[nsr::kNnDim + d], c = plan[nsr::kNnCDim + d];
         if (!(n >= 1 && n <= (1 << 20) && c == std::ceil(n / nsr::kNnLocal))) return false;
-        P.nd[d] = (int)n;
-        P.nc[d] = (int)c;
-        if (!std::isfinite(P.lo[d]) || !std::isfinite(P.hi[d])) return false;
+        G.nd[d] = (int)n;
+        G.nc[d] = (int)c;
+        if (!std::isfinite(G.lo[d]) || !std::isfinite(G.hi[d])) return false;
     }
-    P.h = plan[nsr::kNnH];
-    P.slack = plan[nsr::kNnSlack];
-    P.ncell = (long long)P.nd[0] * P.nd[1] * P.nd[2];
-    P.ncoarse = (long long)P.nc[0] * P.nc[1] * P.nc[2];
+    G.h = plan[nsr::kNnH];
+    G.slack = plan[nsr::kNnSlack];
+    G.ncell = (long long)G.nd[0] * G.nd[1] * G.nd[2];
+    G.ncoarse = (long long)G.nc[0] * G.nc[1] * G.nc[2];
+    return G.h > 0 && std::isfinite(G.h) && G.ncell == (long long)plan[nsr::kNnCells] && G.ncoarse == (long long)plan[nsr::kNnCoarse] &&
+           (m < 0 || G.ncell <= 4 * m + 64);
+}
+
+// NnParams for m reference points over the plan's grid; false as grid_from_plan
+bool nn_from_plan(nsr::NnParams &P, const double *plan, long long m) {
+    std::memset(&P, 0, sizeof(P));
     P.m = m;
-    return P.h > 0 && std::isfinite(P.h) && P.ncell == (long long)plan[nsr::kNnCells] && P.ncoarse == (long long)plan[nsr::kNnCoarse] &&
-           (m < 0 || P.ncell <= 4 * m + 64);
+    return grid_from_plan(P.G, plan, m);
 }
 
 void nn_bind_workspace(nsr::NnParams &P, void *workspace) {
-    const NnLayout L = nn_layout(P.m, P.ncell, P.ncoarse);
+    const NnLayout L = nn_layout(P.m, P.G);
     char *w = static_cast<char *>(workspace);
     P.sref = reinterpret_cast<double *>(w + L.sref);
     P.sidx = reinterpret_cast<long long *>(w + L.sidx);
-    P.fstart = reinterpret_cast<int *>(w + L.fstart);
-    P.fend = reinterpret_cast<int *>(w + L.fend);
-    P.cstart = reinterpret_cast<int *>(w + L.cstart);
-    P.cend = reinterpret_cast<int *>(w + L.cend);
+    bind_runs(P.G, w, L.runs);
     P.cbox = reinterpret_cast<double *>(w + L.cbox);
 }
 
@@ -1124,7 +1145,7 @@ int nsr_nn_plan(const double *bounds, int64_t n_ref, double *plan) {
 int64_t nsr_nn_workspace_bytes(const double *plan, int64_t n_ref) {
     nsr::NnParams P;
     if (!nn_from_plan(P, plan, n_ref)) return -1;
-    return nn_layout(P.m, P.ncell, P.ncoarse).total;
+    return nn_layout(P.m, P.G).total;
 }
 
 int nsr_nn_keys(const void *pts, int64_t n, int32_t fp64, const double *plan, int64_t *keys, void *stream) {
@@ -1147,10 +1168,10 @@ int nsr_nn_build(const void *ref, int64_t n_ref, int32_t fp64, const double *pla
     P.pts = ref; P.n = n_ref; P.fp64 = fp64 ? 1 : 0;
     P.keys = const_cast<long long *>(reinterpret_cast<const long long *>(sorted_keys));
     P.order = reinterpret_cast<const long long *>(order);
-    const long long nclear = P.ncell > P.ncoarse ? P.ncell : P.ncoarse;
-    NSR_LAUNCH(nsr::nn_clear_kernel, dim3(nblk(nclear, 256)), dim3(256), 0, stream, P);
+    const long long nclear = P.G.ncell > P.G.ncoarse ? P.G.ncell : P.G.ncoarse;
+    NSR_LAUNCH(nsr::nn_clear_kernel, dim3(nblk(nclear, 256)), dim3(256), 0, stream, P.G);
     NSR_LAUNCH(nsr::nn_gather_kernel, dim3(nblk(n_ref, 256)), dim3(256), 0, stream, P);
-    NSR_LAUNCH(nsr::nn_box_kernel, dim3(nblk(P.ncoarse, 64)), dim3(64), 0, stream, P);
+    NSR_LAUNCH(nsr::nn_box_kernel, dim3(nblk(P.G.ncoarse, 64)), dim3(64), 0, stream, P);
     return finish("nsr_nn_build");
 }
 
@@ -1265,19 +1286,16 @@ int nsr_cull_vertices(const void *verts, int64_t n, int32_t fp64, const float *w
 namespace {
 
 // workspace of nsr_meshdist_build / nsr_meshdist_query (byte offsets, each 16-byte aligned)
-struct MdLayout { long long tri, pface, olist, fstart, fend, cstart, cend, crep, total; };
+struct MdLayout { long long tri, pface, olist; RunLayout runs; long long crep, total; };
 
-MdLayout md_layout(long long nf, long long npairs, long long nover, long long ncell, long long ncoarse) {
+MdLayout md_layout(long long nf, long long npairs, long long nover, const nsr::NnGrid &G) {
     MdLayout L;
     L.tri = 0;
     L.pface = L.tri + align16(72 * nf);
     L.olist = L.pface + align16(4 * npairs);
-    L.fstart = L.olist + align16(4 * nover);
-    L.fend = L.fstart + align16(4 * ncell);
-    L.cstart = L.fend + align16(4 * ncell);
-    L.cend = L.cstart + align16(4 * ncoarse);
-    L.crep = L.cend + align16(4 * ncoarse);
-    L.total = L.crep + align16(24 * ncoarse);
+    L.runs = run_layout(L.olist + align16(4 * nover), G);
+    L.crep = L.runs.end;
+    L.total = L.crep + align16(24 * G.ncoarse);
     return L;
 }
 
@@ -1287,7 +1305,7 @@ bool md_setup(nsr::MdParams &P, const char *who, const double *plan, const void 
     std::memset(&P, 0, sizeof(P));
     if (nf < 1) { fail(std::string(who) + ": the mesh has no faces"); return false; }
     if (nv < 1 || nv > 2147483647ll || nf > 2147483647ll / 3) { fail(std::string(who) + ": vertex or face count outside int32 indexing"); return false; }
-    if (!nn_from_plan(P.G, plan, nf)) { fail(std::string(who) + ": invalid plan for this mesh"); return false; }
+    if (!grid_from_plan(P.G, plan, nf)) { fail(std::string(who) + ": invalid plan for this mesh"); return false; }
     P.verts = verts; P.nv = nv; P.vfp64 = fp64 ? 1 : 0; P.faces = faces; P.nf = nf;
     return true;
 }
@@ -1299,15 +1317,12 @@ bool md_counts_ok(const char *who, int64_t nf, int64_t npairs, int64_t nover) {
 }
 
 void md_bind_workspace(nsr::MdParams &P, void *workspace) {
-    const MdLayout L = md_layout(P.nf, P.npairs, P.nover, P.G.ncell, P.G.ncoarse);
+    const MdLayout L = md_layout(P.nf, P.npairs, P.nover, P.G);
     char *w = static_cast<char *>(workspace);
     P.tri = reinterpret_cast<double *>(w + L.tri);
     P.pface = reinterpret_cast<int *>(w + L.pface);
     P.olist = reinterpret_cast<int *>(w + L.olist);
-    P.fstart = reinterpret_cast<int *>(w + L.fstart);
-    P.fend = reinterpret_cast<int *>(w + L.fend);
-    P.cstart = reinterpret_cast<int *>(w + L.cstart);
-    P.cend = reinterpret_cast<int *>(w + L.cend);
+    bind_runs(P.G, w, L.runs);
     P.crep = reinterpret_cast<double *>(w + L.crep);
 }
 
@@ -1323,9 +1338,9 @@ int nsr_meshdist_plan(const double *bounds, int64_t nf, double *plan) {
 }
 
 int64_t nsr_meshdist_workspace_bytes(const double *plan, int64_t nf, int64_t n_pairs, int64_t n_over) {
-    nsr::NnParams G;
-    if (nf < 1 || !nn_from_plan(G, plan, nf) || !md_counts_ok("nsr_meshdist_workspace_bytes", nf, n_pairs, n_over)) return -1;
-    return md_layout(nf, n_pairs, n_over, G.ncell, G.ncoarse).total;
+    nsr::NnGrid G;
+    if (nf < 1 || !grid_from_plan(G, plan, nf) || !md_counts_ok("nsr_meshdist_workspace_bytes", nf, n_pairs, n_over)) return -1;
+    return md_layout(nf, n_pairs, n_over, G).total;
 }
 
 int nsr_meshdist_count(const void *verts, int64_t nv, int32_t fp64, const int32_t *faces, int64_t nf, const double *plan, int64_t *count,
@@ -1365,7 +1380,7 @@ int nsr_meshdist_build(const void *verts, int64_t nv, int32_t fp64, const int32_
     P.pairs = reinterpret_cast<const long long *>(pair_face);
     P.over = const_cast<long long *>(reinterpret_cast<const long long *>(over)); P.ocum = reinterpret_cast<const long long *>(over_cum);
     const long long nclear = P.G.ncell > P.G.ncoarse ? P.G.ncell : P.G.ncoarse;
-    NSR_LAUNCH(nsr::md_clear_kernel, dim3(nblk(nclear, 256)), dim3(256), 0, stream, P);
+    NSR_LAUNCH(nsr::nn_clear_kernel, dim3(nblk(nclear, 256)), dim3(256), 0, stream, P.G);
     NSR_LAUNCH(nsr::md_tri_kernel, dim3(nblk(nf, 256)), dim3(256), 0, stream, P);
     if (n_pairs > 0) NSR_LAUNCH(nsr::md_gather_kernel, dim3(nblk(n_pairs, 256)), dim3(256), 0, stream, P);
     return finish("nsr_meshdist_build");
@@ -1377,7 +1392,7 @@ int nsr_meshdist_query(const void *query, int64_t n_query, int32_t fp64, const i
     nsr::MdParams P;
     std::memset(&P, 0, sizeof(P));
     if (n_query < 0) return fail("nsr_meshdist_query: negative count");
-    if (nf < 1 || !nn_from_plan(P.G, plan, nf)) return fail("nsr_meshdist_query: invalid plan for this mesh");
+    if (nf < 1 || !grid_from_plan(P.G, plan, nf)) return fail("nsr_meshdist_query: invalid plan for this mesh");
     if (!md_counts_ok("nsr_meshdist_query", nf, n_pairs, n_over)) return 1;
     if (n_query == 0) return 0;
     if (!query || !workspace || !dist || !face || !closest) return fail("nsr_meshdist_query: null pointer");
@@ -1405,17 +1420,14 @@ int nsr_normal_stats(const double *query_normals, const double *face_normals, co
                      double *out, void *stream) {
     if (n < 0 || nf < 0) return fail("nsr_normal_stats: negative count");
     if (!partial || !out || (n > 0 && (!query_normals || !face_normals || !face))) return fail("nsr_normal_stats: null pointer");
-    nsr::MdNormalParams P;
+    nsr::RedParams P;
     std::memset(&P, 0, sizeof(P));
-    P.qn = query_normals; P.normals = const_cast<double *>(face_normals); P.face = reinterpret_cast<const long long *>(face);
-    P.n = n; P.nf = nf; P.partial = partial;
-    nsr::RedParams R;
-    std::memset(&R, 0, sizeof(R));
-    R.n = n; R.partial = partial; R.out = out;
-    R.nblocks = (n + nsr::kRedThreads - 1) / nsr::kRedThreads;
-    if (R.nblocks > 0)
-        NSR_LAUNCH(nsr::md_normal_stats_kernel, dim3((unsigned)R.nblocks), dim3(nsr::kRedThreads), 2 * nsr::kRedThreads * 8, stream, P);
-    NSR_LAUNCH(nsr::reduce_final_kernel<nsr::kRedDist>, dim3(1), dim3(64), 0, stream, R);
+    P.src = query_normals; P.tgt = face_normals; P.idx = reinterpret_cast<const long long *>(face); P.n = n; P.m = nf;
+    P.partial = partial; P.out = out;
+    P.nblocks = (n + nsr::kRedThreads - 1) / nsr::kRedThreads;
+    if (P.nblocks > 0)
+        NSR_LAUNCH(nsr::reduce_kernel<nsr::kRedNormal>, dim3((unsigned)P.nblocks), dim3(nsr::kRedThreads), 2 * nsr::kRedThreads * 8, stream, P);
+    NSR_LAUNCH(nsr::reduce_final_kernel<nsr::kRedDist>, dim3(1), dim3(64), 0, stream, P);
     return finish("nsr_normal_stats");
 }
 

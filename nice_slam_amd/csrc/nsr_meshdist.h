@@ -1,8 +1,9 @@
 // nsr_meshdist.h -- exact point-to-triangle-mesh distance (include/nsr.h, "Point-to-mesh distance"): the closest point of a
 // triangle list to every query, the faces' unit normals and the fixed-order sum of |n . m| over matched normals.
-// Included by nsr_api.cpp AFTER nsr_recon.h, whose grid vocabulary (NnParams, nn_cell, nn_key, nn_key_fine, nn_load) and
-// reduction tail (reduce_final_kernel) it uses; it includes nothing itself, so that the library and the CPU emulator resolve
-// the device primitives to their own versions.  fp64 throughout, no contraction, no atomics: every table and every result is
+// Included by nsr_api.cpp AFTER nsr_recon.h, whose grid (NnGrid, nn_cell, nn_key, nn_load, nn_clear_kernel, nn_mark_runs), shell
+// walk (nn_walk<Sink>: the query's prologue, the shells, the bound and the stop test live there, once) and reductions
+// (reduce_kernel<kRedNormal>, reduce_final_kernel) it uses; it includes nothing itself, so that the library and the CPU emulator
+// resolve the device primitives to their own versions.  fp64 throughout, no contraction, no atomics: every table and every result is
 // bit-identical from run to run.
 //
 // Per-face distance (md_face).  a, b, c the corners, p the query, dot(u, v) = (ux*vx + uy*vy) + uz*vz, every difference and
@@ -39,19 +40,19 @@
 // Query.  Every point of a face lies in a cell the face is registered in, so
 //     dist(q, mesh) = min over (cell C, face f in C) of dist(q, f within C)   and   dist(q, f within C) >= dist(q, C).
 // A cell is skipped only when a lower bound on dist(q, C), less the plan's slack, exceeds the best distance found; a face that
-// is examined contributes its full distance.  The lane walks shells of fine cells as nn_query_kernel does, with the same
-// bound on everything outside the walked box; a query still open after kMdShells shells takes the coarse route: an upper bound
-// from one corner of one face per occupied coarse cell, then every coarse cell, and inside it every fine cell, whose box can
-// hold a point at or below the bound.  Ties of bit-equal squared distance go to the smallest face index.
+// is examined contributes its full distance.  The lane walks shells of fine cells by nn_walk (nsr_recon.h), whose bound on
+// everything outside the walked box holds for the part of a face out there as it does for a point; a query still open after
+// kNnFineShells shells takes the coarse route: an upper bound from one corner of one face per occupied coarse cell, then every
+// coarse cell, and inside it every fine cell, whose box can hold a point at or below the bound.  Ties of bit-equal squared
+// distance go to the smallest face index.
 #pragma once
 
 namespace nsr {
 
-constexpr int kMdShells = 3;
 constexpr int kMdCellCap = 32;                  // cells a face may be registered in; more: the oversize list
 
 struct MdParams {
-    NnParams G;                      // the grid: lo, hi, h, slack, nd, nc, ncell, ncoarse (the rest unused)
+    NnGrid G;                        // the grid over the box of the vertices; its runs are runs of pface
     const void *verts;               // [nv][3] fp32 or fp64
     const int *faces;                // [nf][3]
     long long nv, nf;
@@ -66,8 +67,6 @@ struct MdParams {
     double *tri;                     // [nf][9] the corners, fp64 (zeros for an invalid face)
     int *pface;                      // [npairs] faces in key order
     int *olist;                      // [nover] oversize faces, ascending
-    int *fstart, *fend;              // [ncell] fine-cell runs
-    int *cstart, *cend;              // [ncoarse] coarse-cell runs
     double *crep;                    // [ncoarse][3] a corner of a face registered in the coarse cell
     const void *q;                   // [n][3] queries
     long long n;
@@ -188,12 +187,6 @@ NSR_KERNEL void md_fill_kernel(const MdParams P) {
             }
 }
 
-NSR_KERNEL void md_clear_kernel(const MdParams P) {
-    const long long i = (long long)bid_x() * nthreads() + tid();
-    if (i < P.G.ncell) { P.fstart[i] = 0; P.fend[i] = 0; }
-    if (i < P.G.ncoarse) { P.cstart[i] = 0; P.cend[i] = 0; }
-}
-
 NSR_KERNEL void md_tri_kernel(const MdParams P) {
     const long long f = (long long)bid_x() * nthreads() + tid();
     if (f >= P.nf) return;
@@ -214,16 +207,9 @@ NSR_KERNEL void md_gather_kernel(const MdParams P) {
     long long fi = (o >= 0 && o < P.npairs) ? P.pairs[o] : 0;
     if (fi < 0 || fi >= P.nf) fi = 0;
     P.pface[j] = (int)fi;
-    const long long k = P.skeys[j], f = nn_key_fine(P.G, k);
-    if (f < 0) return;
-    if (j == 0 || P.skeys[j - 1] != k) P.fstart[f] = (int)j;
-    if (j == P.npairs - 1 || P.skeys[j + 1] != k) P.fend[f] = (int)(j + 1);
-    const long long c = k >> 9;
-    if (j == 0 || (P.skeys[j - 1] >> 9) != c) {
-        P.cstart[c] = (int)j;
+    const long long c = nn_mark_runs(P.G, P.skeys, j, P.npairs);
+    if (c >= 0)
         for (int d = 0; d < 3; ++d) P.crep[3 * c + d] = P.tri[9 * fi + d];
-    }
-    if (j == P.npairs - 1 || (P.skeys[j + 1] >> 9) != c) P.cend[c] = (int)(j + 1);
 }
 
 struct MdBest { double d2; long long f; double x, y, z; int cand; };
@@ -253,7 +239,7 @@ NSR_DEV double md_box_near2(const MdParams &P, const double q[3], const int c0[3
 
 // the fine cells of coarse cell k whose box can hold a point at or below the current bound min(B.d2, U2)
 NSR_DEV void md_scan_coarse(const MdParams &P, const double q[3], long long k, double U2, double slack, MdBest &B) {
-    const NnParams &G = P.G;
+    const NnGrid &G = P.G;
     const int kz = (int)(k % G.nc[2]), ky = (int)((k / G.nc[2]) % G.nc[1]), kx = (int)(k / ((long long)G.nc[2] * G.nc[1]));
     const int c0[3] = {kx * kNnLocal, ky * kNnLocal, kz * kNnLocal};
     int c1[3];
@@ -267,7 +253,7 @@ NSR_DEV void md_scan_coarse(const MdParams &P, const double q[3], long long k, d
         for (int y = c0[1]; y < c1[1]; ++y)
             for (int z = c0[2]; z < c1[2]; ++z) {
                 const long long f = nn_fine_id(G, x, y, z);
-                const int s = P.fstart[f], e = P.fend[f];
+                const int s = G.fstart[f], e = G.fend[f];
                 if (s >= e) continue;
                 const int f0[3] = {x, y, z}, f1[3] = {x + 1, y + 1, z + 1};
                 const double lim2 = B.d2 < U2 ? B.d2 : U2;
@@ -276,73 +262,37 @@ NSR_DEV void md_scan_coarse(const MdParams &P, const double q[3], long long k, d
             }
 }
 
+struct MdFaceSink {                                             // the table is pface: the faces of every cell in key order
+    const MdParams &P;
+    MdBest &B;
+    NSR_DEV void scan(const double q[3], int s, int e) const { md_scan(P, q[0], q[1], q[2], s, e, B); }
+    NSR_DEV double best2() const { return B.d2; }
+};
+
 // one thread per query, in key order (P.qorder), so that a wave's lanes walk neighbouring cells
 NSR_KERNEL void md_query_kernel(const MdParams P) {
     const long long t = (long long)bid_x() * nthreads() + tid();
     if (t >= P.n) return;
     const long long qi = P.qorder ? P.qorder[t] : t;
     if (qi < 0 || qi >= P.n) return;
-    const NnParams &G = P.G;
-    double q[3];
+    const NnGrid &G = P.G;
+    double q[3], slack;
     nn_load(P.q, P.qfp64, qi, q[0], q[1], q[2]);
-    int c[3];
-    double o[3], o2 = 0.0, qabs = 0.0;
-    for (int d = 0; d < 3; ++d) {
-        c[d] = nn_cell(G, d, q[d]);
-        const double below = G.lo[d] - q[d], above = q[d] - G.hi[d];
-        o[d] = below > 0.0 ? below : (above > 0.0 ? above : 0.0);    // distance to the mesh's box along d
-        o2 += o[d] * o[d];
-        qabs += fabs(q[d]);
-    }
-    const double slack = G.slack + 1e-12 * qabs;
     MdBest B{__builtin_huge_val(), -1, 0.0, 0.0, 0.0, 0};
     for (long long k = 0; k < P.nover; ++k) md_try(P, q[0], q[1], q[2], P.olist[k], B);
-    bool done = P.npairs == 0;
-    for (int r = 0; r < kMdShells && !done; ++r) {
-        const int x0 = c[0] - r > 0 ? c[0] - r : 0, x1 = c[0] + r < G.nd[0] - 1 ? c[0] + r : G.nd[0] - 1;
-        const int y0 = c[1] - r > 0 ? c[1] - r : 0, y1 = c[1] + r < G.nd[1] - 1 ? c[1] + r : G.nd[1] - 1;
-        const int z0 = c[2] - r > 0 ? c[2] - r : 0, z1 = c[2] + r < G.nd[2] - 1 ? c[2] + r : G.nd[2] - 1;
-        for (int x = x0; x <= x1; ++x)
-            for (int y = y0; y <= y1; ++y)
-                for (int z = z0; z <= z1; ++z) {
-                    const int ax = abs(x - c[0]), ay = abs(y - c[1]), az = abs(z - c[2]);
-                    const int cheb = ax > ay ? (ax > az ? ax : az) : (ay > az ? ay : az);
-                    if (cheb != r) continue;
-                    const long long f = nn_fine_id(G, x, y, z);
-                    md_scan(P, q[0], q[1], q[2], P.fstart[f], P.fend[f], B);
-                }
-        // every part of a face outside the walked box lies beyond one of its sides (along d: a gap g_d) and, along the other
-        // axes, at least as far as the mesh's box is: |x - q|^2 >= g_d^2 + sum_{e != d} o_e^2
-        double L2 = __builtin_huge_val();
-        for (int d = 0; d < 3; ++d) {
-            const double rest = o2 - o[d] * o[d] > 0.0 ? o2 - o[d] * o[d] : 0.0;
-            if (c[d] - r > 0) {
-                double g = q[d] - (G.lo[d] + (double)(c[d] - r) * G.h);
-                g = g > 0.0 ? g : 0.0;
-                L2 = g * g + rest < L2 ? g * g + rest : L2;
-            }
-            if (c[d] + r + 1 < G.nd[d]) {
-                double g = (G.lo[d] + (double)(c[d] + r + 1) * G.h) - q[d];
-                g = g > 0.0 ? g : 0.0;
-                L2 = g * g + rest < L2 ? g * g + rest : L2;
-            }
-        }
-        if (L2 == __builtin_huge_val()) { done = true; break; }      // the walked box covers the whole grid
-        const double L = sqrt(L2) - slack;
-        done = L > 0.0 && L * L > B.d2 * (1.0 + 1e-12);
-    }
-    if (!done) {
+    MdFaceSink sink{P, B};
+    if (P.npairs != 0 && !nn_walk(G, q, sink, slack)) {
         // coarse route: an upper bound on the answer from one corner of one face of every occupied coarse cell, then a scan of
         // the fine cells, coarse cell by coarse cell, whose box can hold a point at or below the current bound
         double U2 = B.d2;
         for (long long k = 0; k < G.ncoarse; ++k) {
-            if (P.cstart[k] >= P.cend[k]) continue;
+            if (G.cstart[k] >= G.cend[k]) continue;
             const double dx = q[0] - P.crep[3 * k], dy = q[1] - P.crep[3 * k + 1], dz = q[2] - P.crep[3 * k + 2];
             const double u = (dx * dx + dy * dy) + dz * dz;
             U2 = u < U2 ? u : U2;
         }
         for (long long k = 0; k < G.ncoarse; ++k)
-            if (P.cstart[k] < P.cend[k]) md_scan_coarse(P, q, k, U2, slack, B);
+            if (G.cstart[k] < G.cend[k]) md_scan_coarse(P, q, k, U2, slack, B);
     }
     P.dist[qi] = sqrt(B.d2);
     P.face[qi] = B.f;
@@ -353,18 +303,15 @@ NSR_KERNEL void md_query_kernel(const MdParams P) {
 // ------------------------------------------------------------------------------------------------
 // Normals.  n = (b - a) x (c - a) in the expression order of md_face, divided by sqrt((nx*nx + ny*ny) + nz*nz); the zero
 // vector when that length is not > 0 (a degenerate face).  The statistics pair query normal i with the normal of face[i]:
-// (|n . m|, 1) when neither is the zero vector and the face index is valid, else (0, 0); summed as nsr_dist_stats sums.
+// (|n . m|, 1) when neither is the zero vector and the face index is valid, else (0, 0); summed as nsr_dist_stats sums, by
+// the same kernels (reduce_kernel<kRedNormal>, nsr_recon.h).
 // ------------------------------------------------------------------------------------------------
 struct MdNormalParams {
     const void *verts;
     const int *faces;
     long long nv, nf;
     int vfp64;
-    double *normals;                 // [nf][3] out (face_normals); in (normal_stats)
-    const double *qn;                // [n][3]
-    const long long *face;           // [n]
-    long long n;
-    double *partial;                 // [nblocks][9]
+    double *normals;                 // [nf][3] out
 };
 
 NSR_KERNEL void md_normals_kernel(const MdNormalParams P) {
@@ -381,32 +328,6 @@ NSR_KERNEL void md_normals_kernel(const MdNormalParams P) {
         else { nx = 0.0; ny = 0.0; nz = 0.0; }
     }
     P.normals[3 * f] = nx; P.normals[3 * f + 1] = ny; P.normals[3 * f + 2] = nz;
-}
-
-NSR_KERNEL void md_normal_stats_kernel(const MdNormalParams P) {
-    double *red = reinterpret_cast<double *>(lds_base());          // [2][kRedThreads]
-    const int t = tid();
-    const long long i = (long long)bid_x() * kRedThreads + t;
-    double v0 = 0.0, v1 = 0.0;
-    if (i < P.n) {
-        const long long f = P.face[i];
-        if (f >= 0 && f < P.nf) {
-            const double *a = P.qn + 3 * i, *b = P.normals + 3 * f;
-            const bool za = a[0] == 0.0 && a[1] == 0.0 && a[2] == 0.0, zb = b[0] == 0.0 && b[1] == 0.0 && b[2] == 0.0;
-            if (!za && !zb) { v0 = fabs(md_dot(a[0], a[1], a[2], b[0], b[1], b[2])); v1 = 1.0; }
-        }
-    }
-    red[t] = v0;
-    red[kRedThreads + t] = v1;
-    block_sync();
-    for (int w = kRedThreads / 2; w >= 1; w >>= 1) {
-        if (t < w) {
-            red[t] = red[t] + red[t + w];
-            red[kRedThreads + t] = red[kRedThreads + t] + red[kRedThreads + t + w];
-        }
-        block_sync();
-    }
-    if (t < 2) P.partial[9 * bid_x() + t] = red[t * kRedThreads];
 }
 
 }  // namespace nsr

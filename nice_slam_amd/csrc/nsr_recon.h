@@ -15,9 +15,11 @@ namespace nsr {
 // key of a point is (coarse cell id) * 512 + (fine cell inside its coarse cell), so that sorting by key makes every fine cell
 // AND every coarse cell a contiguous run.  A query walks shells of fine cells at Chebyshev radius 0..kNnFineShells-1 around its
 // (clamped) cell and stops as soon as the exact lower bound on the distance to any cell outside the walked box exceeds its best
-// distance; a query that is still open after that (far from the set, or in an empty region) scans the occupied coarse cells by
-// their bounding boxes instead: bounded by the number of coarse cells, never by an unbounded shell walk.
+// distance (nn_walk); a query that is still open after that (far from the set, or in an empty region) scans the occupied coarse
+// cells by their bounding boxes instead: bounded by the number of coarse cells, never by an unbounded shell walk.
 // Distances: fp64, dx*dx + dy*dy + dz*dz in that order (no contraction), correctly rounded sqrt; ties -> smallest index.
+// The grid (NnGrid), its keys, the clear and the run marking of its tables, and the walk (nn_walk<Sink>) are also the
+// mesh-distance index's (nsr_meshdist.h), which supplies a sink of its own and its own coarse route.
 // ------------------------------------------------------------------------------------------------
 constexpr int kNnLocal = 8;                     // fine cells per coarse cell along each axis (key = coarse * 512 + local)
 constexpr int kNnFineShells = 3;
@@ -25,20 +27,27 @@ constexpr int kNnBoundBlocks = 256;
 // plan layout (doubles), written by nsr_nn_plan
 enum { kNnLo = 0, kNnHi = 3, kNnH = 6, kNnDim = 7, kNnCDim = 10, kNnCells = 13, kNnCoarse = 14, kNnSlack = 15, kNnPlanSize = 16 };
 
+// The grid of an index, whatever it holds (reference points here, (cell, face) pairs in nsr_meshdist.h): the plan's geometry
+// and the runs of every fine and coarse cell in the index's key-ordered table.
+struct NnGrid {
+    int nd[3], nc[3];                // fine and coarse grid dimensions
+    double lo[3], hi[3], h, slack;   // bounding box of the indexed set, cell edge, absolute slack of the pruning bounds
+    long long ncell, ncoarse;
+    int *fstart, *fend;              // [ncell] fine-cell runs in key order
+    int *cstart, *cend;              // [ncoarse] coarse-cell runs
+};
+
 struct NnParams {
+    NnGrid G;
     const void *pts;                 // [n][3] fp32 or fp64 (ref for bounds / keys / build, query for keys / query)
     long long n;
     int fp64;
-    int nd[3], nc[3];                // fine and coarse grid dimensions
-    double lo[3], hi[3], h, slack;   // bounding box of the reference set, cell edge, absolute slack of the pruning bounds
-    long long ncell, ncoarse, m;     // m: reference points
+    long long m;                     // reference points
     double *bounds;                  // [1 + kNnBoundBlocks][6] (nn_bounds)
     long long *keys;                 // [n] (nn_keys out; nn_build in: sorted)
     const long long *order;          // [m] reference permutation that sorts the keys (nn_build); query order (nn_query)
     double *sref;                    // [m][3] reference points in key order, fp64
     long long *sidx;                 // [m] their original index
-    int *fstart, *fend;              // [ncell] fine-cell runs in key order
-    int *cstart, *cend;              // [ncoarse] coarse-cell runs
     double *cbox;                    // [ncoarse][6] bounding box of a coarse cell's points
     double *dist;                    // [n] out
     long long *idx;                  // [n] out
@@ -86,44 +95,58 @@ NSR_KERNEL void nn_bounds_final_kernel(const NnParams P) {
     P.bounds[t] = v;
 }
 
-NSR_DEV int nn_cell(const NnParams &P, int d, double x) {
-    double f = floor((x - P.lo[d]) / P.h);
+NSR_DEV int nn_cell(const NnGrid &G, int d, double x) {
+    double f = floor((x - G.lo[d]) / G.h);
     if (!(f >= 0.0)) f = 0.0;                                      // below the box, or NaN
-    if (f > (double)(P.nd[d] - 1)) f = (double)(P.nd[d] - 1);
+    if (f > (double)(G.nd[d] - 1)) f = (double)(G.nd[d] - 1);
     return (int)f;
 }
 
-NSR_DEV long long nn_key(const NnParams &P, int cx, int cy, int cz) {
-    const long long coarse = ((long long)(cx / kNnLocal) * P.nc[1] + cy / kNnLocal) * P.nc[2] + cz / kNnLocal;
+NSR_DEV long long nn_key(const NnGrid &G, int cx, int cy, int cz) {
+    const long long coarse = ((long long)(cx / kNnLocal) * G.nc[1] + cy / kNnLocal) * G.nc[2] + cz / kNnLocal;
     return coarse * 512 + (cx % kNnLocal) * 64 + (cy % kNnLocal) * 8 + cz % kNnLocal;
 }
 
-NSR_DEV long long nn_fine_id(const NnParams &P, int cx, int cy, int cz) { return ((long long)cx * P.nd[1] + cy) * P.nd[2] + cz; }
+NSR_DEV long long nn_fine_id(const NnGrid &G, int cx, int cy, int cz) { return ((long long)cx * G.nd[1] + cy) * G.nd[2] + cz; }
 
 NSR_KERNEL void nn_keys_kernel(const NnParams P) {
     const long long i = (long long)bid_x() * nthreads() + tid();
     if (i >= P.n) return;
     double x, y, z;
     nn_load(P.pts, P.fp64, i, x, y, z);
-    P.keys[i] = nn_key(P, nn_cell(P, 0, x), nn_cell(P, 1, y), nn_cell(P, 2, z));
+    P.keys[i] = nn_key(P.G, nn_cell(P.G, 0, x), nn_cell(P.G, 1, y), nn_cell(P.G, 2, z));
 }
 
-NSR_KERNEL void nn_clear_kernel(const NnParams P) {
+NSR_KERNEL void nn_clear_kernel(const NnGrid G) {
     const long long i = (long long)bid_x() * nthreads() + tid();
-    if (i < P.ncell) { P.fstart[i] = 0; P.fend[i] = 0; }
-    if (i < P.ncoarse) { P.cstart[i] = 0; P.cend[i] = 0; }
+    if (i < G.ncell) { G.fstart[i] = 0; G.fend[i] = 0; }
+    if (i < G.ncoarse) { G.cstart[i] = 0; G.cend[i] = 0; }
 }
 
 // decode a key into its fine-cell id; -1 for a key outside the plan (the table is never written out of range)
-NSR_DEV long long nn_key_fine(const NnParams &P, long long key) {
+NSR_DEV long long nn_key_fine(const NnGrid &G, long long key) {
     if (key < 0) return -1;
     const long long c = key >> 9;
     const int l = (int)(key & 511);
-    if (c >= P.ncoarse) return -1;
-    const int cz = (int)(c % P.nc[2]), cy = (int)((c / P.nc[2]) % P.nc[1]), cx = (int)(c / ((long long)P.nc[2] * P.nc[1]));
+    if (c >= G.ncoarse) return -1;
+    const int cz = (int)(c % G.nc[2]), cy = (int)((c / G.nc[2]) % G.nc[1]), cx = (int)(c / ((long long)G.nc[2] * G.nc[1]));
     const int fx = cx * kNnLocal + (l >> 6), fy = cy * kNnLocal + ((l >> 3) & 7), fz = cz * kNnLocal + (l & 7);
-    if (fx >= P.nd[0] || fy >= P.nd[1] || fz >= P.nd[2]) return -1;
-    return nn_fine_id(P, fx, fy, fz);
+    if (fx >= G.nd[0] || fy >= G.nd[1] || fz >= G.nd[2]) return -1;
+    return nn_fine_id(G, fx, fy, fz);
+}
+
+// position j of n sorted keys: the fine-cell and coarse-cell runs that start or end there are marked in the run tables.
+// Returns the coarse cell whose run starts at j, -1 if none does (or the key is outside the plan: nothing is marked).
+NSR_DEV long long nn_mark_runs(const NnGrid &G, const long long *keys, long long j, long long n) {
+    const long long k = keys[j], f = nn_key_fine(G, k);
+    if (f < 0) return -1;
+    if (j == 0 || keys[j - 1] != k) G.fstart[f] = (int)j;
+    if (j == n - 1 || keys[j + 1] != k) G.fend[f] = (int)(j + 1);
+    const long long c = k >> 9;
+    const bool starts = j == 0 || (keys[j - 1] >> 9) != c;
+    if (starts) G.cstart[c] = (int)j;
+    if (j == n - 1 || (keys[j + 1] >> 9) != c) G.cend[c] = (int)(j + 1);
+    return starts ? c : -1;
 }
 
 // reference points in key order (fp64) + the runs of every fine and coarse cell
@@ -136,23 +159,74 @@ NSR_KERNEL void nn_gather_kernel(const NnParams P) {
     nn_load(P.pts, P.fp64, o, x, y, z);
     P.sref[3 * j] = x; P.sref[3 * j + 1] = y; P.sref[3 * j + 2] = z;
     P.sidx[j] = o;
-    const long long k = P.keys[j], f = nn_key_fine(P, k);
-    if (f < 0) return;
-    if (j == 0 || P.keys[j - 1] != k) P.fstart[f] = (int)j;
-    if (j == P.m - 1 || P.keys[j + 1] != k) P.fend[f] = (int)(j + 1);
-    const long long c = k >> 9;
-    if (j == 0 || (P.keys[j - 1] >> 9) != c) P.cstart[c] = (int)j;
-    if (j == P.m - 1 || (P.keys[j + 1] >> 9) != c) P.cend[c] = (int)(j + 1);
+    nn_mark_runs(P.G, P.keys, j, P.m);
 }
 
 NSR_KERNEL void nn_box_kernel(const NnParams P) {
     const long long c = (long long)bid_x() * nthreads() + tid();
-    if (c >= P.ncoarse) return;
+    if (c >= P.G.ncoarse) return;
     double b[6] = {__builtin_huge_val(), __builtin_huge_val(), __builtin_huge_val(),
                    -__builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val()};
-    for (int j = P.cstart[c]; j < P.cend[c]; ++j)
+    for (int j = P.G.cstart[c]; j < P.G.cend[c]; ++j)
         for (int d = 0; d < 3; ++d) { b[d] = nn_min(b[d], P.sref[3ll * j + d]); b[3 + d] = nn_max(b[3 + d], P.sref[3ll * j + d]); }
     for (int k = 0; k < 6; ++k) P.cbox[6 * c + k] = b[k];
+}
+
+// The walk both searches share.  One query q walks the shells of fine cells at Chebyshev radius 0..kNnFineShells-1 around its
+// (clamped) cell and hands every cell's run [fstart, fend) of the key-ordered table to the sink; after each shell it stops if
+// the walked box covers the grid, or if the exact lower bound on the distance to anything outside the walked box, less the
+// slack, exceeds the sink's best distance.  Returns whether the query is closed; an open one takes the caller's coarse route,
+// which prunes with the same slack (handed back).  What a run holds is the sink's business:
+//   scan(q, s, e)      examine the entries [s, e) of the table;
+//   best2()            the smallest squared distance found so far (huge before any).
+// Both are resolved at compile time: NnPointSink below, MdFaceSink in nsr_meshdist.h.
+template <class Sink>
+NSR_DEV bool nn_walk(const NnGrid &G, const double q[3], Sink &sink, double &slack) {
+    int c[3];
+    double o[3], o2 = 0.0, qabs = 0.0;
+    for (int d = 0; d < 3; ++d) {
+        c[d] = nn_cell(G, d, q[d]);
+        const double below = G.lo[d] - q[d], above = q[d] - G.hi[d];
+        o[d] = below > 0.0 ? below : (above > 0.0 ? above : 0.0);    // distance to the grid's box along d
+        o2 += o[d] * o[d];
+        qabs += fabs(q[d]);
+    }
+    slack = G.slack + 1e-12 * qabs;
+    for (int r = 0; r < kNnFineShells; ++r) {
+        const int x0 = c[0] - r > 0 ? c[0] - r : 0, x1 = c[0] + r < G.nd[0] - 1 ? c[0] + r : G.nd[0] - 1;
+        const int y0 = c[1] - r > 0 ? c[1] - r : 0, y1 = c[1] + r < G.nd[1] - 1 ? c[1] + r : G.nd[1] - 1;
+        const int z0 = c[2] - r > 0 ? c[2] - r : 0, z1 = c[2] + r < G.nd[2] - 1 ? c[2] + r : G.nd[2] - 1;
+        for (int x = x0; x <= x1; ++x)
+            for (int y = y0; y <= y1; ++y)
+                for (int z = z0; z <= z1; ++z) {
+                    const int ax = abs(x - c[0]), ay = abs(y - c[1]), az = abs(z - c[2]);
+                    const int cheb = ax > ay ? (ax > az ? ax : az) : (ay > az ? ay : az);
+                    if (cheb != r) continue;
+                    const long long f = nn_fine_id(G, x, y, z);
+                    sink.scan(q, G.fstart[f], G.fend[f]);
+                }
+        // everything outside the walked box (a point; the part of a face in a cell out there) lies beyond one of its sides (along
+        // d: a gap g_d) and, along the other axes, at least as far as the grid's box is: |p - q|^2 >= g_d^2 + sum_{e != d} o_e^2
+        double L2 = __builtin_huge_val();
+        for (int d = 0; d < 3; ++d) {
+            const double rest = o2 - o[d] * o[d] > 0.0 ? o2 - o[d] * o[d] : 0.0;
+            const int b0 = c[d] - r, b1 = c[d] + r + 1;                // the walked box along d, in cells: [b0, b1)
+            if (b0 > 0) {
+                double g = q[d] - (G.lo[d] + (double)b0 * G.h);
+                g = g > 0.0 ? g : 0.0;
+                L2 = g * g + rest < L2 ? g * g + rest : L2;
+            }
+            if (b1 < G.nd[d]) {
+                double g = (G.lo[d] + (double)b1 * G.h) - q[d];
+                g = g > 0.0 ? g : 0.0;
+                L2 = g * g + rest < L2 ? g * g + rest : L2;
+            }
+        }
+        if (L2 == __builtin_huge_val()) return true;                 // the walked box covers the whole grid
+        const double L = sqrt(L2) - slack;
+        if (L > 0.0 && L * L > sink.best2() * (1.0 + 1e-12)) return true;
+    }
+    return false;
 }
 
 struct NnBest { double d2; long long i; int cand; };
@@ -167,65 +241,29 @@ NSR_DEV void nn_scan(const NnParams &P, const double q[3], int s, int e, NnBest 
     }
 }
 
+struct NnPointSink {                                            // the table is sref / sidx: the reference points in key order
+    const NnParams &P;
+    NnBest &B;
+    NSR_DEV void scan(const double q[3], int s, int e) const { nn_scan(P, q, s, e, B); }
+    NSR_DEV double best2() const { return B.d2; }
+};
+
 // one thread per query, in key order (P.order), so that a wave's lanes walk neighbouring cells
 NSR_KERNEL void nn_query_kernel(const NnParams P) {
     const long long t = (long long)bid_x() * nthreads() + tid();
     if (t >= P.n) return;
     const long long qi = P.order ? P.order[t] : t;
     if (qi < 0 || qi >= P.n) return;
-    double q[3];
+    double q[3], slack;
     nn_load(P.pts, P.fp64, qi, q[0], q[1], q[2]);
-    int c[3];
-    double o[3], o2 = 0.0, qabs = 0.0;
-    for (int d = 0; d < 3; ++d) {
-        c[d] = nn_cell(P, d, q[d]);
-        const double below = P.lo[d] - q[d], above = q[d] - P.hi[d];
-        o[d] = below > 0.0 ? below : (above > 0.0 ? above : 0.0);    // distance to the reference box along d
-        o2 += o[d] * o[d];
-        qabs += fabs(q[d]);
-    }
-    const double slack = P.slack + 1e-12 * qabs;
     NnBest B{__builtin_huge_val(), -1, 0};
-    bool done = false;
-    for (int r = 0; r < kNnFineShells && !done; ++r) {
-        const int x0 = c[0] - r > 0 ? c[0] - r : 0, x1 = c[0] + r < P.nd[0] - 1 ? c[0] + r : P.nd[0] - 1;
-        const int y0 = c[1] - r > 0 ? c[1] - r : 0, y1 = c[1] + r < P.nd[1] - 1 ? c[1] + r : P.nd[1] - 1;
-        const int z0 = c[2] - r > 0 ? c[2] - r : 0, z1 = c[2] + r < P.nd[2] - 1 ? c[2] + r : P.nd[2] - 1;
-        for (int x = x0; x <= x1; ++x)
-            for (int y = y0; y <= y1; ++y)
-                for (int z = z0; z <= z1; ++z) {
-                    const int ax = abs(x - c[0]), ay = abs(y - c[1]), az = abs(z - c[2]);
-                    const int cheb = ax > ay ? (ax > az ? ax : az) : (ay > az ? ay : az);
-                    if (cheb != r) continue;
-                    const long long f = nn_fine_id(P, x, y, z);
-                    nn_scan(P, q, P.fstart[f], P.fend[f], B);
-                }
-        // every point outside the walked box lies beyond one of its faces (along d: a gap g_d) and, along the other axes, at
-        // least as far as the reference box is: |p - q|^2 >= g_d^2 + sum_{e != d} o_e^2
-        double L2 = __builtin_huge_val();
-        for (int d = 0; d < 3; ++d) {
-            const double rest = o2 - o[d] * o[d] > 0.0 ? o2 - o[d] * o[d] : 0.0;
-            if (c[d] - r > 0) {
-                double g = q[d] - (P.lo[d] + (double)(c[d] - r) * P.h);
-                g = g > 0.0 ? g : 0.0;
-                L2 = g * g + rest < L2 ? g * g + rest : L2;
-            }
-            if (c[d] + r + 1 < P.nd[d]) {
-                double g = (P.lo[d] + (double)(c[d] + r + 1) * P.h) - q[d];
-                g = g > 0.0 ? g : 0.0;
-                L2 = g * g + rest < L2 ? g * g + rest : L2;
-            }
-        }
-        if (L2 == __builtin_huge_val()) { done = true; break; }      // the walked box covers the whole grid
-        const double L = sqrt(L2) - slack;
-        done = L > 0.0 && L * L > B.d2 * (1.0 + 1e-12);
-    }
-    if (!done) {
+    NnPointSink sink{P, B};
+    if (!nn_walk(P.G, q, sink, slack)) {
         // coarse fallback: an upper bound on the answer from the farthest corner of every occupied coarse box, then a scan of
         // every coarse cell whose box can hold a point at or below the current bound
         double U2 = B.d2;
-        for (long long k = 0; k < P.ncoarse; ++k) {
-            if (P.cstart[k] >= P.cend[k]) continue;
+        for (long long k = 0; k < P.G.ncoarse; ++k) {
+            if (P.G.cstart[k] >= P.G.cend[k]) continue;
             const double *bx = P.cbox + 6 * k;
             double far2 = 0.0;
             for (int d = 0; d < 3; ++d) {
@@ -234,8 +272,8 @@ NSR_KERNEL void nn_query_kernel(const NnParams P) {
             }
             U2 = far2 < U2 ? far2 : U2;
         }
-        for (long long k = 0; k < P.ncoarse; ++k) {
-            if (P.cstart[k] >= P.cend[k]) continue;
+        for (long long k = 0; k < P.G.ncoarse; ++k) {
+            if (P.G.cstart[k] >= P.G.cend[k]) continue;
             const double *bx = P.cbox + 6 * k;
             double near2 = 0.0;
             for (int d = 0; d < 3; ++d) {
@@ -245,7 +283,7 @@ NSR_KERNEL void nn_query_kernel(const NnParams P) {
             }
             const double lim2 = B.d2 < U2 ? B.d2 : U2;
             const double nr = sqrt(near2) - slack;
-            if (nr <= 0.0 || nr * nr <= lim2 * (1.0 + 1e-12)) nn_scan(P, q, P.cstart[k], P.cend[k], B);
+            if (nr <= 0.0 || nr * nr <= lim2 * (1.0 + 1e-12)) nn_scan(P, q, P.G.cstart[k], P.G.cend[k], B);
         }
     }
     P.dist[qi] = sqrt(B.d2);
@@ -341,30 +379,39 @@ NSR_KERNEL void surf_point_kernel(const SurfSampleParams P) {
 //   DIST: (dist, dist < th)                                          -> mean distance, completion ratio (eval_recon.py:24-43)
 //   ICP1: inliers dist < th: (1, |s - t|^2, s, t)                    -> count, squared error, centroids
 //   ICP2: inliers: (t - mu_t)(s - mu_s)^T, mu from ICP1's output     -> the cross-covariance of Umeyama's estimate
+//   NORMAL: (|s . t|, 1) unless s or t is the zero vector, t = tgt[idx] -> nsr_normal_stats (nsr_meshdist.h, "Normals");
+//           finished as DIST is
 // ------------------------------------------------------------------------------------------------
 constexpr int kRedThreads = 256;
-enum { kRedDist = 0, kRedIcp1 = 1, kRedIcp2 = 2 };
+enum { kRedDist = 0, kRedIcp1 = 1, kRedIcp2 = 2, kRedNormal = 3 };
+constexpr int red_width(int mode) { return mode == kRedDist || mode == kRedNormal ? 2 : (mode == kRedIcp1 ? 8 : 9); }
 
 struct RedParams {
-    const double *dist;              // [n]
-    const double *src;               // [n][3] (ICP)
-    const double *tgt;               // [m][3] (ICP)
-    const long long *idx;            // [n] into tgt (ICP)
+    const double *dist;              // [n] (not NORMAL)
+    const double *src;               // [n][3] (ICP, NORMAL)
+    const double *tgt;               // [m][3] (ICP, NORMAL)
+    const long long *idx;            // [n] into tgt (ICP, NORMAL)
     long long n, m, nblocks;
     double th;
     double *partial;                 // [nblocks][9]
-    double *out;                     // DIST: [2]; ICP: [17] count, sse, mu_s[3], mu_t[3], cov[9]
+    double *out;                     // DIST, NORMAL: [2]; ICP: [17] count, sse, mu_s[3], mu_t[3], cov[9]
 };
 
 template <int MODE>
 NSR_KERNEL void reduce_kernel(const RedParams P) {
-    constexpr int V = MODE == kRedDist ? 2 : (MODE == kRedIcp1 ? 8 : 9);
+    constexpr int V = red_width(MODE);
     double *red = reinterpret_cast<double *>(lds_base());          // [V][kRedThreads]
     const int t = tid();
     const long long i = (long long)bid_x() * kRedThreads + t;
     double v[V];
     for (int k = 0; k < V; ++k) v[k] = 0.0;
-    if (i < P.n) {
+    if (MODE == kRedNormal) {
+        if (i < P.n && P.idx[i] >= 0 && P.idx[i] < P.m) {
+            const double *a = P.src + 3 * i, *b = P.tgt + 3 * P.idx[i];
+            const bool za = a[0] == 0.0 && a[1] == 0.0 && a[2] == 0.0, zb = b[0] == 0.0 && b[1] == 0.0 && b[2] == 0.0;
+            if (!za && !zb) { v[0] = fabs((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]); v[1] = 1.0; }
+        }
+    } else if (i < P.n) {
         const double dd = P.dist[i];
         if (MODE == kRedDist) {
             v[0] = dd;
@@ -394,7 +441,7 @@ NSR_KERNEL void reduce_kernel(const RedParams P) {
 
 template <int MODE>
 NSR_KERNEL void reduce_final_kernel(const RedParams P) {
-    constexpr int V = MODE == kRedDist ? 2 : (MODE == kRedIcp1 ? 8 : 9);
+    constexpr int V = red_width(MODE);
     const int t = tid();
     if (t >= V) return;
     double acc = 0.0;

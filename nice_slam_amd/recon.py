@@ -57,6 +57,30 @@ __all__ = ["nearest", "accuracy", "completion", "completion_ratio", "recon_metri
 # --------------------------------------------------------------------------------------------------
 # nearest neighbour
 # --------------------------------------------------------------------------------------------------
+def _grid_plan(E: Engine, pts: torch.Tensor, plan_entry: str, count: int):
+    """the host's grid plan (``plan_entry``: nsr_nn_plan or nsr_meshdist_plan, for ``count`` entries) over the box of ``pts``"""
+    bounds = torch.empty(6 * 257, dtype=torch.float64, device=E.device)
+    E.call("nsr_nn_bounds", pts.data_ptr(), pts.shape[0], int(pts.dtype == torch.float64), bounds.data_ptr())
+    plan = (C.c_double * 16)()
+    E.lib.call(plan_entry, c_doubles(bounds[:6].cpu().numpy()), count, plan)
+    return plan
+
+
+def _query_tensor(E: Engine, q, who: str):
+    """(``q`` as a finite [N, 3] tensor on the device, N, its fp64 flag)"""
+    qt = E.tensor(q, what=f"{who}: query")
+    if qt.shape[0] and not bool(torch.isfinite(qt).all()):
+        raise ValueError(f"{who}: query coordinates must be finite")
+    return qt, qt.shape[0], int(qt.dtype == torch.float64)
+
+
+def _key_order(E: Engine, plan, qt: torch.Tensor, fp64: int) -> torch.Tensor:
+    """the order that sorts the queries by their cell key, so that a wave's lanes walk neighbouring cells"""
+    keys = torch.empty(qt.shape[0], dtype=torch.int64, device=E.device)
+    E.call("nsr_nn_keys", qt.data_ptr(), qt.shape[0], fp64, plan, keys.data_ptr())
+    return torch.sort(keys, stable=True)[1].contiguous()
+
+
 class NNIndex:
     """Exact nearest-neighbour index over ``ref`` [M, 3] (fp32 or fp64): a uniform cell grid built on the device.
     ``query(q)`` -> (dist fp64 [N], idx int64 [N]) as ``scipy.spatial.cKDTree(ref).query(q)``; distances in fp64,
@@ -71,11 +95,7 @@ class NNIndex:
             raise ValueError("nearest: the reference set is empty")
         self.fp64 = int(r.dtype == torch.float64)
         with torch.no_grad(), E.guard():
-            bounds = torch.empty(6 * 257, dtype=torch.float64, device=E.device)
-            E.call("nsr_nn_bounds", r.data_ptr(), M, self.fp64, bounds.data_ptr())
-            b = bounds[:6].cpu().numpy()
-            self.plan = (C.c_double * 16)()
-            lib.call("nsr_nn_plan", c_doubles(b), M, self.plan)
+            self.plan = _grid_plan(E, r, "nsr_nn_plan", M)
             nbytes = lib.nsr_nn_workspace_bytes(self.plan, M)
             if nbytes < 0:
                 raise _capi.NsrError("nearest: invalid grid plan")
@@ -87,19 +107,13 @@ class NNIndex:
 
     def query(self, q, with_candidates: bool = False):
         E = self.engine
-        qt = E.tensor(q, what="nearest: query")
-        N = qt.shape[0]
+        qt, N, fp64 = _query_tensor(E, q, "nearest")
         dist = torch.empty(N, dtype=torch.float64, device=E.device)
         idx = torch.empty(N, dtype=torch.int64, device=E.device)
         ncand = torch.empty(N, dtype=torch.int32, device=E.device) if with_candidates else None
         if N:
-            if not bool(torch.isfinite(qt).all()):
-                raise ValueError("nearest: query coordinates must be finite")
-            fp64 = int(qt.dtype == torch.float64)
             with torch.no_grad(), E.guard():
-                keys = torch.empty(N, dtype=torch.int64, device=E.device)
-                E.call("nsr_nn_keys", qt.data_ptr(), N, fp64, self.plan, keys.data_ptr())
-                qorder = torch.sort(keys, stable=True)[1].contiguous()
+                qorder = _key_order(E, self.plan, qt, fp64)
                 E.call("nsr_nn_query", qt.data_ptr(), N, fp64, qorder.data_ptr(), self.plan, self.ws.data_ptr(), self.m, dist.data_ptr(),
                        idx.data_ptr(), None if ncand is None else ncand.data_ptr())
         return (dist, idx, ncand) if with_candidates else (dist, idx)
@@ -275,10 +289,7 @@ class MeshIndex:
         self.fp64 = int(v.dtype == torch.float64)
         mesh = (v.data_ptr(), V, self.fp64, f.data_ptr(), F)
         with torch.no_grad(), E.guard():
-            bounds = torch.empty(6 * 257, dtype=torch.float64, device=E.device)
-            E.call("nsr_nn_bounds", v.data_ptr(), V, self.fp64, bounds.data_ptr())
-            self.plan = (C.c_double * 16)()
-            lib.call("nsr_meshdist_plan", c_doubles(bounds[:6].cpu().numpy()), F, self.plan)
+            self.plan = _grid_plan(E, v, "nsr_meshdist_plan", F)
             count = torch.empty(F, dtype=torch.int64, device=E.device)
             over = torch.empty(F, dtype=torch.int64, device=E.device)
             E.call("nsr_meshdist_count", *mesh, self.plan, count.data_ptr(), over.data_ptr())
@@ -298,20 +309,14 @@ class MeshIndex:
     def query(self, points, with_candidates: bool = False):
         """(dist, face, closest[, ncand int32 [N]: faces examined, repeats counted])"""
         E = self.engine
-        qt = E.tensor(points, what="mesh_distance: query")
-        N = qt.shape[0]
+        qt, N, fp64 = _query_tensor(E, points, "mesh_distance")
         dist = torch.empty(N, dtype=torch.float64, device=E.device)
         face = torch.empty(N, dtype=torch.int64, device=E.device)
         closest = torch.empty((N, 3), dtype=torch.float64, device=E.device)
         ncand = torch.empty(N, dtype=torch.int32, device=E.device) if with_candidates else None
         if N:
-            if not bool(torch.isfinite(qt).all()):
-                raise ValueError("mesh_distance: query coordinates must be finite")
-            fp64 = int(qt.dtype == torch.float64)
             with torch.no_grad(), E.guard():
-                keys = torch.empty(N, dtype=torch.int64, device=E.device)
-                E.call("nsr_nn_keys", qt.data_ptr(), N, fp64, self.plan, keys.data_ptr())
-                qorder = torch.sort(keys, stable=True)[1].contiguous()
+                qorder = _key_order(E, self.plan, qt, fp64)
                 E.call("nsr_meshdist_query", qt.data_ptr(), N, fp64, qorder.data_ptr(), self.plan, self.ws.data_ptr(), self.nf, self.npairs,
                        self.nover, dist.data_ptr(), face.data_ptr(), closest.data_ptr(), None if ncand is None else ncand.data_ptr())
         return (dist, face, closest, ncand) if with_candidates else (dist, face, closest)

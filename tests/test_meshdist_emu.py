@@ -105,9 +105,14 @@ def cases():
     for F, N in ((63, 65), (64, 64), (65, 63), (255, 257), (256, 256), (257, 255)):
         v = rng.uniform(-1, 1, (F, 1, 3)) + rng.uniform(-0.15, 0.15, (F, 3, 3))
         out[f"sizes_F{F}_N{N}"] = (rng.uniform(-1.2, 1.2, (N, 3)), v.reshape(-1, 3), np.arange(3 * F, dtype=np.int32).reshape(F, 3))
+    # the box again, whose grid is ragged (test_grid_walk.py checks the plan): the first INSIDE queries sit at its empty middle,
+    # the next len(far) far outside: these FAR_RAGGED come first, then queries around the box
+    inside = np.array([0.5, 0.4, 0.3]) + rng.uniform(-0.02, 0.02, (INSIDE, 3))
+    out["far_ragged"] = (np.concatenate([inside, far, rng.uniform(-0.2, 1.2, (40, 3))]), bv, bf)
     return out
 
 
+INSIDE, FAR_RAGGED = 15, 75
 CASES = cases()
 
 
@@ -394,6 +399,10 @@ def test_kernels_use_no_scratch():
     from nice_slam_amd import build
     res = json.load(open(build.RESOURCES))
     md = {k: v for k, v in res.items() if "md_" in k and "MdParams" in k or "MdNormalParams" in k}
-    assert len(md) == 8
+    assert len(md) == 6
+    # the kernels it shares with the point search (nsr_recon.h): the clear of the run tables, the normal statistic's reduction
+    shared = {k: v for k, v in res.items() if "nn_clear_kernel" in k and "NnGrid" in k or "reduce_kernel" in k and "ILi3E" in k}
+    assert len(shared) == 2
+    md.update(shared)
     for k, v in md.items():
         assert v["scratch_bytes_per_lane"] == 0, (k, v)

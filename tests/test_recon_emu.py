@@ -42,7 +42,7 @@ def brute(q, ref):
 
 def check_nn(E, q, ref):
     d, i, nc = recon.NNIndex(ref, E).query(q, with_candidates=True)
-    d, i = d.numpy(), i.numpy()
+    d, i = d.cpu().numpy(), i.cpu().numpy()
     bd, bi, d2 = brute(q, ref)
     assert np.array_equal(d, bd)                                   # bit for bit
     unique = (d2 == d2[np.arange(len(q)), bi][:, None]).sum(1) == 1
@@ -51,7 +51,7 @@ def check_nn(E, q, ref):
     if len(q):
         kd = cKDTree(np.asarray(ref, np.float64)).query(np.asarray(q, np.float64))[0]
         assert np.all(np.abs(d - kd) <= np.spacing(np.maximum(d, kd)))
-    return nc.numpy()
+    return nc.cpu().numpy()
 
 
 def cases():
@@ -62,7 +62,7 @@ def cases():
     far = 100.0 * far / np.linalg.norm(far, axis=1, keepdims=True)
     one_cell = 0.3 + 1e-7 * rng.uniform(size=(200, 3))
     dup = np.repeat(rng.uniform(size=(60, 3)), 4, 0)
-    return {
+    out = {
         "one_point": (rng.normal(size=(50, 3)), np.array([[0.1, -0.2, 0.3]])),
         "zero_queries": (np.zeros((0, 3)), rng.uniform(size=(100, 3))),
         "one_cell": (np.concatenate([rng.uniform(0.2, 0.4, (80, 3)), one_cell[:20]]), one_cell),
@@ -72,6 +72,19 @@ def cases():
         "plane": (rng.uniform(-1.2, 1.2, (150, 3)), plane),
         "uniform_fp32": (rng.uniform(-1, 1, (300, 3)).astype(np.float32), rng.uniform(-1, 1, (3000, 3)).astype(np.float32)),
     }
+    # M and N on both sides of a wave (64) and of a block (256)
+    for M, N in ((63, 65), (64, 64), (65, 63), (255, 257), (256, 256), (257, 255)):
+        out[f"sizes_M{M}_N{N}"] = (rng.uniform(-1.2, 1.2, (N, 3)), rng.uniform(-1, 1, (M, 3)))
+    # points on the six sides of a box whose grid is ragged (test_grid_walk.py checks the plan); the first INSIDE queries sit
+    # at its empty middle, the next len(far) far outside: these FAR_RAGGED come first, then queries around the box
+    shell = rng.uniform(0, 1, (1500, 3))
+    shell[np.arange(1500), rng.integers(0, 3, 1500)] = rng.integers(0, 2, 1500)
+    inside = 0.5 + rng.uniform(-0.04, 0.04, (INSIDE, 3))
+    out["far_ragged"] = (np.concatenate([inside, far, rng.uniform(-0.1, 1.1, (100, 3))]) * [1.0, 0.7, 0.45], shell * [1.0, 0.7, 0.45])
+    return out
+
+
+INSIDE, FAR_RAGGED = 15, 40
 
 
 @pytest.mark.parametrize("name", list(cases()))
