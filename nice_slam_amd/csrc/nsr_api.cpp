@@ -79,6 +79,31 @@ constexpr int kFwdWeight = 10;
 inline int fwd_fine_weight(int stage) { return stage == NSR_STAGE_FINE ? 12 : 14; }
 
 inline int round16(int bytes) { return (bytes + 15) & ~15; }
+inline unsigned nblk(long long n, int tb) { return (unsigned)((n + tb - 1) / tb); }
+
+// ---- caller-allocated workspaces ---------------------------------------------------------------------------------------------
+inline long long pad16(long long bytes) { return (bytes + 15) & ~15ll; }
+
+// a workspace is described ONCE, by a function that takes its pieces from a Carve in order: without a base it measures (the
+// size entry returns `at`), with the caller's pointer it binds (the working entries)
+struct Carve {
+    char *base;
+    long long at = 0;
+    explicit Carve(const void *workspace = nullptr) : base(static_cast<char *>(const_cast<void *>(workspace))) {}
+    // `count` elements; the next piece starts 16-byte aligned
+    template <typename T> T *take(long long count) {
+        T *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
+        at += pad16(count * (long long)sizeof(T));
+        return p;
+    }
+};
+// the bytes of the workspace that `describe` lays out for P, bound to P where the caller's workspace is given
+template <typename Params>
+long long carve(void (*describe)(Params &, Carve &), Params &P, const void *workspace = nullptr) {
+    Carve c(workspace);
+    describe(P, c);
+    return c.at;
+}
 
 // forward: up to 12 tiles (768 threads, 3 waves/SIMD, <=168 VGPRs)
 int rays_per_block(int S) {
@@ -868,19 +893,28 @@ int nsr_camera_from_tensor(const float *cam, int64_t n, float *rt, const float *
 namespace {
 constexpr int kMcThreads = 256;
 
+// the lattice's sizes into P; false: a lattice the kernels do not take
+bool mc_sizes(nsr::McParams &P, int32_t nx, int32_t ny, int32_t nz) {
+    std::memset(&P, 0, sizeof(P));
+    if (nx < 2 || ny < 2 || nz < 2) return false;
+    P.nx = nx; P.ny = ny; P.nz = nz; P.n = (long long)nx * ny * nz;
+    if (P.n > (1ll << 31)) return false;
+    P.nblocks = (int)((P.n + kMcThreads - 1) / kMcThreads);
+    return true;
+}
+
+void mc_carve(nsr::McParams &P, Carve &c) {
+    P.code = c.take<unsigned char>(P.n);
+    P.voff = c.take<int>(P.n);
+    P.blk = c.take<long long>(2ll * P.nblocks);
+}
+
 int mc_setup(nsr::McParams &P, const float *vol, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace, const char *what) {
     if (nx < 2 || ny < 2 || nz < 2) return fail(std::string(what) + ": every lattice dimension must be at least 2");
-    const long long n = (long long)nx * ny * nz;
-    if (n > (1ll << 31)) return fail(std::string(what) + ": lattice larger than 2^31 points");
+    if (!mc_sizes(P, nx, ny, nz)) return fail(std::string(what) + ": lattice larger than 2^31 points");
     if (!vol || !workspace) return fail(std::string(what) + ": null pointer");
-    std::memset(&P, 0, sizeof(P));
-    P.vol = vol; P.nx = nx; P.ny = ny; P.nz = nz; P.n = n; P.level = level;
-    P.nblocks = (int)((n + kMcThreads - 1) / kMcThreads);
-    char *ws = static_cast<char *>(workspace);
-    const long long code_bytes = (n + 15) & ~15ll;
-    P.code = reinterpret_cast<unsigned char *>(ws);
-    P.voff = reinterpret_cast<int *>(ws + code_bytes);
-    P.blk = reinterpret_cast<long long *>(ws + code_bytes + ((4 * n + 15) & ~15ll));
+    P.vol = vol; P.level = level;
+    carve(mc_carve, P, workspace);
     return 0;
 }
 }  // namespace
@@ -888,11 +922,9 @@ int mc_setup(nsr::McParams &P, const float *vol, int32_t nx, int32_t ny, int32_t
 extern "C" {
 
 int64_t nsr_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
-    if (nx < 2 || ny < 2 || nz < 2) return -1;
-    const long long n = (long long)nx * ny * nz;
-    if (n > (1ll << 31)) return -1;
-    const long long nb = (n + kMcThreads - 1) / kMcThreads;
-    return ((n + 15) & ~15ll) + ((4 * n + 15) & ~15ll) + 16 * nb;
+    nsr::McParams P;
+    if (!mc_sizes(P, nx, ny, nz)) return -1;
+    return carve(mc_carve, P);
 }
 
 int nsr_mc_count(const float *vol, int32_t nx, int32_t ny, int32_t nz, float level, void *workspace, int64_t *counts, void *stream) {
@@ -1005,38 +1037,20 @@ int nsr_segment_sums(const double *values, const int64_t *order, const int64_t *
 // ---- reconstruction evaluation (include/nsr.h, "Reconstruction evaluation") ----
 namespace {
 
-inline long long align16(long long b) { return (b + 15) & ~15ll; }
-
-// the four run tables of a grid (nsr::NnGrid) inside an index's workspace: byte offsets from `at`, each 16-byte aligned
-struct RunLayout { long long fstart, fend, cstart, cend, end; };
-
-RunLayout run_layout(long long at, const nsr::NnGrid &G) {
-    RunLayout R;
-    R.fstart = at;
-    R.fend = R.fstart + align16(4 * G.ncell);
-    R.cstart = R.fend + align16(4 * G.ncell);
-    R.cend = R.cstart + align16(4 * G.ncoarse);
-    R.end = R.cend + align16(4 * G.ncoarse);
-    return R;
+// the four run tables of a grid inside an index's workspace
+void carve_runs(Carve &c, nsr::NnGrid &G) {
+    G.fstart = c.take<int>(G.ncell);
+    G.fend = c.take<int>(G.ncell);
+    G.cstart = c.take<int>(G.ncoarse);
+    G.cend = c.take<int>(G.ncoarse);
 }
 
-void bind_runs(nsr::NnGrid &G, char *w, const RunLayout &R) {
-    G.fstart = reinterpret_cast<int *>(w + R.fstart);
-    G.fend = reinterpret_cast<int *>(w + R.fend);
-    G.cstart = reinterpret_cast<int *>(w + R.cstart);
-    G.cend = reinterpret_cast<int *>(w + R.cend);
-}
-
-struct NnLayout { long long sref, sidx; RunLayout runs; long long cbox, total; };
-
-NnLayout nn_layout(long long m, const nsr::NnGrid &G) {
-    NnLayout L;
-    L.sref = 0;
-    L.sidx = L.sref + align16(24 * m);
-    L.runs = run_layout(L.sidx + align16(8 * m), G);
-    L.cbox = L.runs.end;
-    L.total = L.cbox + align16(48 * G.ncoarse);
-    return L;
+// workspace of nsr_nn_build / nsr_nn_query
+void nn_carve(nsr::NnParams &P, Carve &c) {
+    P.sref = c.take<double>(3 * P.m);
+    P.sidx = c.take<long long>(P.m);
+    carve_runs(c, P.G);
+    P.cbox = c.take<double>(6 * P.G.ncoarse);
 }
 
 // the plan as a grid (its run tables unbound); false if it is not one nsr_nn_plan could have written for m points (m < 0: for
@@ -1067,17 +1081,6 @@ bool nn_from_plan(nsr::NnParams &P, const double *plan, long long m) {
     P.m = m;
     return grid_from_plan(P.G, plan, m);
 }
-
-void nn_bind_workspace(nsr::NnParams &P, void *workspace) {
-    const NnLayout L = nn_layout(P.m, P.G);
-    char *w = static_cast<char *>(workspace);
-    P.sref = reinterpret_cast<double *>(w + L.sref);
-    P.sidx = reinterpret_cast<long long *>(w + L.sidx);
-    bind_runs(P.G, w, L.runs);
-    P.cbox = reinterpret_cast<double *>(w + L.cbox);
-}
-
-inline unsigned nblk(long long n, int tb) { return (unsigned)((n + tb - 1) / tb); }
 
 }  // namespace
 
@@ -1145,7 +1148,7 @@ int nsr_nn_plan(const double *bounds, int64_t n_ref, double *plan) {
 int64_t nsr_nn_workspace_bytes(const double *plan, int64_t n_ref) {
     nsr::NnParams P;
     if (!nn_from_plan(P, plan, n_ref)) return -1;
-    return nn_layout(P.m, P.G).total;
+    return carve(nn_carve, P);
 }
 
 int nsr_nn_keys(const void *pts, int64_t n, int32_t fp64, const double *plan, int64_t *keys, void *stream) {
@@ -1164,7 +1167,7 @@ int nsr_nn_build(const void *ref, int64_t n_ref, int32_t fp64, const double *pla
     nsr::NnParams P;
     if (!nn_from_plan(P, plan, n_ref)) return fail("nsr_nn_build: invalid plan for this reference set");
     if (!ref || !sorted_keys || !order || !workspace) return fail("nsr_nn_build: null pointer");
-    nn_bind_workspace(P, workspace);
+    carve(nn_carve, P, workspace);
     P.pts = ref; P.n = n_ref; P.fp64 = fp64 ? 1 : 0;
     P.keys = const_cast<long long *>(reinterpret_cast<const long long *>(sorted_keys));
     P.order = reinterpret_cast<const long long *>(order);
@@ -1182,7 +1185,7 @@ int nsr_nn_query(const void *query, int64_t n_query, int32_t fp64, const int64_t
     if (!nn_from_plan(P, plan, n_ref)) return fail("nsr_nn_query: invalid plan for this reference set");
     if (n_query == 0) return 0;
     if (!query || !workspace || !dist || !idx) return fail("nsr_nn_query: null pointer");
-    nn_bind_workspace(P, const_cast<void *>(workspace));
+    carve(nn_carve, P, workspace);
     P.pts = query; P.n = n_query; P.fp64 = fp64 ? 1 : 0;
     P.order = reinterpret_cast<const long long *>(qorder);
     P.dist = dist; P.idx = reinterpret_cast<long long *>(idx); P.ncand = ncand;
@@ -1192,7 +1195,7 @@ int nsr_nn_query(const void *query, int64_t n_query, int32_t fp64, const int64_t
 
 int64_t nsr_sample_workspace_bytes(int64_t nf) {
     if (nf < 0) return -1;
-    return align16(8 * nf) + 8 * ((nf + nsr::kSurfTile - 1) / nsr::kSurfTile + 1);
+    return pad16(8 * nf) + 8 * ((nf + nsr::kSurfTile - 1) / nsr::kSurfTile + 1);
 }
 
 int nsr_sample_surface(const double *verts, int64_t nv, const int32_t *faces, int64_t nf, int64_t n, const double *uniforms,
@@ -1207,7 +1210,7 @@ int nsr_sample_surface(const double *verts, int64_t nv, const int32_t *faces, in
     P.verts = verts; P.faces = faces; P.nv = nv; P.nf = nf; P.n = n;
     P.ntiles = (nf + nsr::kSurfTile - 1) / nsr::kSurfTile;
     P.cum = static_cast<double *>(workspace);
-    P.tile = reinterpret_cast<double *>(static_cast<char *>(workspace) + align16(8 * nf));
+    P.tile = reinterpret_cast<double *>(static_cast<char *>(workspace) + pad16(8 * nf));
     P.uniforms = uniforms; P.seed = seed; P.points = points; P.face_index = reinterpret_cast<long long *>(face_index);
     NSR_LAUNCH(nsr::surf_tile_kernel, dim3(nblk(P.ntiles, 64)), dim3(64), 0, stream, P);
     NSR_LAUNCH(nsr::surf_tile_scan_kernel, dim3(1), dim3(64), 0, stream, P);
@@ -1285,18 +1288,13 @@ int nsr_cull_vertices(const void *verts, int64_t n, int32_t fp64, const float *w
 // ---- point-to-mesh distance (include/nsr.h, "Point-to-mesh distance") ----
 namespace {
 
-// workspace of nsr_meshdist_build / nsr_meshdist_query (byte offsets, each 16-byte aligned)
-struct MdLayout { long long tri, pface, olist; RunLayout runs; long long crep, total; };
-
-MdLayout md_layout(long long nf, long long npairs, long long nover, const nsr::NnGrid &G) {
-    MdLayout L;
-    L.tri = 0;
-    L.pface = L.tri + align16(72 * nf);
-    L.olist = L.pface + align16(4 * npairs);
-    L.runs = run_layout(L.olist + align16(4 * nover), G);
-    L.crep = L.runs.end;
-    L.total = L.crep + align16(24 * G.ncoarse);
-    return L;
+// workspace of nsr_meshdist_build / nsr_meshdist_query
+void md_carve(nsr::MdParams &P, Carve &c) {
+    P.tri = c.take<double>(9 * P.nf);
+    P.pface = c.take<int>(P.npairs);
+    P.olist = c.take<int>(P.nover);
+    carve_runs(c, P.G);
+    P.crep = c.take<double>(3 * P.G.ncoarse);
 }
 
 // the mesh and its grid as MdParams; false with the error set
@@ -1316,16 +1314,6 @@ bool md_counts_ok(const char *who, int64_t nf, int64_t npairs, int64_t nover) {
     return true;
 }
 
-void md_bind_workspace(nsr::MdParams &P, void *workspace) {
-    const MdLayout L = md_layout(P.nf, P.npairs, P.nover, P.G);
-    char *w = static_cast<char *>(workspace);
-    P.tri = reinterpret_cast<double *>(w + L.tri);
-    P.pface = reinterpret_cast<int *>(w + L.pface);
-    P.olist = reinterpret_cast<int *>(w + L.olist);
-    bind_runs(P.G, w, L.runs);
-    P.crep = reinterpret_cast<double *>(w + L.crep);
-}
-
 }  // namespace
 
 extern "C" {
@@ -1338,9 +1326,11 @@ int nsr_meshdist_plan(const double *bounds, int64_t nf, double *plan) {
 }
 
 int64_t nsr_meshdist_workspace_bytes(const double *plan, int64_t nf, int64_t n_pairs, int64_t n_over) {
-    nsr::NnGrid G;
-    if (nf < 1 || !grid_from_plan(G, plan, nf) || !md_counts_ok("nsr_meshdist_workspace_bytes", nf, n_pairs, n_over)) return -1;
-    return md_layout(nf, n_pairs, n_over, G).total;
+    nsr::MdParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (nf < 1 || !grid_from_plan(P.G, plan, nf) || !md_counts_ok("nsr_meshdist_workspace_bytes", nf, n_pairs, n_over)) return -1;
+    P.nf = nf; P.npairs = n_pairs; P.nover = n_over;
+    return carve(md_carve, P);
 }
 
 int nsr_meshdist_count(const void *verts, int64_t nv, int32_t fp64, const int32_t *faces, int64_t nf, const double *plan, int64_t *count,
@@ -1375,7 +1365,7 @@ int nsr_meshdist_build(const void *verts, int64_t nv, int32_t fp64, const int32_
     if (!verts || !faces || !over || !over_cum || !workspace || (n_pairs > 0 && (!sorted_keys || !order || !pair_face)))
         return fail("nsr_meshdist_build: null pointer");
     P.npairs = n_pairs; P.nover = n_over;
-    md_bind_workspace(P, workspace);
+    carve(md_carve, P, workspace);
     P.skeys = reinterpret_cast<const long long *>(sorted_keys); P.order = reinterpret_cast<const long long *>(order);
     P.pairs = reinterpret_cast<const long long *>(pair_face);
     P.over = const_cast<long long *>(reinterpret_cast<const long long *>(over)); P.ocum = reinterpret_cast<const long long *>(over_cum);
@@ -1397,7 +1387,7 @@ int nsr_meshdist_query(const void *query, int64_t n_query, int32_t fp64, const i
     if (n_query == 0) return 0;
     if (!query || !workspace || !dist || !face || !closest) return fail("nsr_meshdist_query: null pointer");
     P.nf = nf; P.npairs = n_pairs; P.nover = n_over;
-    md_bind_workspace(P, const_cast<void *>(workspace));
+    carve(md_carve, P, workspace);
     P.q = query; P.n = n_query; P.qfp64 = fp64 ? 1 : 0; P.qorder = reinterpret_cast<const long long *>(qorder);
     P.dist = dist; P.face = reinterpret_cast<long long *>(face); P.closest = closest; P.ncand = ncand;
     NSR_LAUNCH(nsr::md_query_kernel, dim3(nblk(n_query, 64)), dim3(64), 0, stream, P);
@@ -1472,14 +1462,12 @@ bool tsdf_box(nsr::TsdfParams &P, const int32_t *box) {
     return true;
 }
 
-long long tsdf_ws_bytes(const nsr::TsdfParams &P) { return align16(4 * P.nwords) + align16(4 * P.nwords) + align16(8 * P.nwblocks) + 16; }
-
-void tsdf_bind(nsr::TsdfParams &P, void *workspace) {
-    char *w = static_cast<char *>(workspace);
-    P.bitmap = reinterpret_cast<unsigned *>(w);
-    P.wprefix = reinterpret_cast<int *>(w + align16(4 * P.nwords));
-    P.bsum = reinterpret_cast<long long *>(w + 2 * align16(4 * P.nwords));
-    P.nunits = reinterpret_cast<long long *>(w + 2 * align16(4 * P.nwords) + align16(8 * P.nwblocks));
+// workspace of the unit bitmap (tsdf_box's sizes)
+void tsdf_carve(nsr::TsdfParams &P, Carve &c) {
+    P.bitmap = c.take<unsigned>(P.nwords);
+    P.wprefix = c.take<int>(P.nwords);
+    P.bsum = c.take<long long>(P.nwblocks);
+    P.nunits = c.take<long long>(1);
 }
 
 }  // namespace
@@ -1502,7 +1490,7 @@ int64_t nsr_tsdf_workspace_bytes(const int32_t *box) {
     nsr::TsdfParams P;
     std::memset(&P, 0, sizeof(P));
     if (!tsdf_box(P, box)) return -1;
-    return tsdf_ws_bytes(P);
+    return carve(tsdf_carve, P);
 }
 
 int nsr_tsdf_touch_count(const float *depth, int32_t K, int32_t H, int32_t W, const double *c2w, double fx, double fy, double cx, double cy,
@@ -1511,7 +1499,7 @@ int nsr_tsdf_touch_count(const float *depth, int32_t K, int32_t H, int32_t W, co
     if (int rc = tsdf_setup(P, depth, K, H, W, c2w, nullptr, fx, fy, cx, cy, voxel_length, sdf_trunc, "nsr_tsdf_touch_count")) return rc;
     if (!tsdf_box(P, box)) return fail("nsr_tsdf_touch_count: empty unit box, or more than 2^31 units in it");
     if (!depth || !c2w || !workspace || !n_units) return fail("nsr_tsdf_touch_count: null pointer");
-    tsdf_bind(P, workspace);
+    carve(tsdf_carve, P, workspace);
     P.nunits = reinterpret_cast<long long *>(n_units);
     NSR_LAUNCH(nsr::tsdf_clear_kernel, dim3(nblk(P.nwords, 256)), dim3(256), 0, stream, P);
     NSR_LAUNCH(nsr::tsdf_mark_kernel, dim3(nblk(P.npts, 256)), dim3(256), 0, stream, P);
@@ -1530,7 +1518,7 @@ int nsr_tsdf_touch_emit(const float *depth, int32_t K, int32_t H, int32_t W, con
     if (n_units < 0 || n_units > P.nbits) return fail("nsr_tsdf_touch_emit: unit count out of range");
     if (n_units == 0) return 0;
     if (!depth || !c2w || !workspace || !units || !touch) return fail("nsr_tsdf_touch_emit: null pointer");
-    tsdf_bind(P, const_cast<void *>(workspace));
+    carve(tsdf_carve, P, workspace);
     P.n_units = n_units; P.units = units; P.touch = touch;
     NSR_LAUNCH(nsr::tsdf_units_kernel, dim3(nblk(P.nwords, 256)), dim3(256), 0, stream, P);
     NSR_LAUNCH(nsr::tsdf_touch_kernel, dim3(nblk(P.npts, 256)), dim3(256), 0, stream, P);
@@ -1558,7 +1546,7 @@ int nsr_tsdf_surface_count(const int32_t *box, const void *workspace, const int3
     if (n_units < 0 || n_units > P.nbits) return fail("nsr_tsdf_surface_count: unit count out of range");
     if (!counts) return fail("nsr_tsdf_surface_count: null pointer");
     if (n_units > 0 && (!workspace || !units || !tsdf || !weight)) return fail("nsr_tsdf_surface_count: null pointer");
-    tsdf_bind(P, const_cast<void *>(workspace));
+    carve(tsdf_carve, P, workspace);
     P.units = const_cast<int *>(units); P.n_units = n_units;
     P.tsdf = const_cast<float *>(tsdf); P.weight = const_cast<float *>(weight); P.counts = reinterpret_cast<long long *>(counts);
     if (n_units > 0)
@@ -1576,7 +1564,7 @@ int nsr_tsdf_surface_emit(const int32_t *box, const void *workspace, const int32
     if (!(voxel_length > 0.0) || !std::isfinite(voxel_length)) return fail("nsr_tsdf_surface_emit: voxel_length must be positive");
     if (n_points == 0 || n_units == 0) return 0;
     if (!workspace || !units || !tsdf || !weight || !counts || !points) return fail("nsr_tsdf_surface_emit: null pointer");
-    tsdf_bind(P, const_cast<void *>(workspace));
+    carve(tsdf_carve, P, workspace);
     P.units = const_cast<int *>(units); P.n_units = n_units;
     P.tsdf = const_cast<float *>(tsdf); P.weight = const_cast<float *>(weight);
     P.counts = const_cast<long long *>(reinterpret_cast<const long long *>(counts)); P.points = points;
@@ -1665,8 +1653,6 @@ int nsr_hull_contains(const void *pts, int64_t n, int32_t fp64, const double *pl
 // ---- depth rasterization and the 2-D depth metric (include/nsr.h, "Depth rasterization") ----
 namespace {
 
-struct RasterLayout { long long cam, rect, counts, start, total; };
-
 bool raster_sizes(nsr::RasterParams &P, int64_t nv, int64_t nf, int32_t K, int32_t H, int32_t W) {
     if (nv < 1 || nf < 1 || K < 1 || H < 1 || W < 1 || H > nsr::kRasterMaxTiles || W > nsr::kRasterMaxTiles) return false;
     if (nv > 2147483647ll || nf > 2147483647ll) return false;
@@ -1678,14 +1664,12 @@ bool raster_sizes(nsr::RasterParams &P, int64_t nv, int64_t nf, int32_t K, int32
     return true;
 }
 
-RasterLayout raster_layout(const nsr::RasterParams &P) {
-    RasterLayout L;
-    L.cam = 0;
-    L.rect = L.cam + align16(16ll * P.K * P.nv);
-    L.counts = L.rect + align16(8ll * P.K * P.nf);
-    L.start = L.counts + align16(4ll * P.K * P.ntiles * P.nchunks);
-    L.total = L.start + align16(8ll * ((long long)P.K * P.ntiles + 1));
-    return L;
+// workspace of nsr_raster_bin, read by nsr_raster_depth and nsr_view_mesh (raster_sizes' sizes)
+void raster_carve(nsr::RasterParams &P, Carve &c) {
+    P.cam = c.take<float>(4ll * P.K * P.nv);
+    P.rect = c.take<int>(2ll * P.K * P.nf);
+    P.counts = c.take<int>((long long)P.K * P.ntiles * P.nchunks);
+    P.tile_start = c.take<long long>((long long)P.K * P.ntiles + 1);
 }
 
 int raster_setup(nsr::RasterParams &P, const float *verts, int64_t nv, const int32_t *faces, int64_t nf, const float *w2c, int32_t K,
@@ -1702,14 +1686,12 @@ int raster_setup(nsr::RasterParams &P, const float *verts, int64_t nv, const int
     P.verts = verts; P.faces = faces; P.w2c = w2c;
     P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.near = near; P.far = far;
     P.fxf = (float)fx; P.fyf = (float)fy; P.cxf = (float)cx; P.cyf = (float)cy; P.nearf = (float)near; P.farf = (float)far;
-    const RasterLayout L = raster_layout(P);
-    char *w = static_cast<char *>(workspace);
-    P.cam = reinterpret_cast<float *>(w + L.cam);
-    P.rect = reinterpret_cast<int *>(w + L.rect);
-    P.counts = reinterpret_cast<int *>(w + L.counts);
-    P.tile_start = reinterpret_cast<long long *>(w + L.start);
+    carve(raster_carve, P, workspace);
     return 0;
 }
+
+// partial sums per view of nsr_depth_error: one per block of pixels
+long long depth_error_blocks(long long n_pixels) { return (n_pixels + nsr::kRasterThreads - 1) / nsr::kRasterThreads; }
 
 }  // namespace
 
@@ -1719,7 +1701,7 @@ int64_t nsr_raster_workspace_bytes(int64_t n_verts, int64_t n_faces, int32_t K, 
     nsr::RasterParams P;
     std::memset(&P, 0, sizeof(P));
     if (!raster_sizes(P, n_verts, n_faces, K, H, W)) return -1;
-    return raster_layout(P).total;
+    return carve(raster_carve, P);
 }
 
 int nsr_raster_bin(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *w2c, int32_t K, int32_t H,
@@ -1755,7 +1737,7 @@ int nsr_raster_depth(const float *verts, int64_t n_verts, const int32_t *faces, 
 
 int64_t nsr_depth_error_partial_doubles(int32_t K, int64_t n_pixels) {
     if (K < 1 || n_pixels < 1) return -1;
-    return (long long)K * ((n_pixels + nsr::kRasterThreads - 1) / nsr::kRasterThreads);
+    return (long long)K * depth_error_blocks(n_pixels);
 }
 
 int nsr_depth_error(const float *a, const float *b, int32_t K, int64_t n_pixels, double *partial, double *out, void *stream) {
@@ -1764,7 +1746,7 @@ int nsr_depth_error(const float *a, const float *b, int32_t K, int64_t n_pixels,
     nsr::L1Params P;
     std::memset(&P, 0, sizeof(P));
     P.a = a; P.b = b; P.n = n_pixels; P.K = K; P.partial = partial; P.out = out;
-    P.nblocks = (n_pixels + nsr::kRasterThreads - 1) / nsr::kRasterThreads;
+    P.nblocks = depth_error_blocks(n_pixels);
     const int T = nsr::kRasterThreads;
     NSR_LAUNCH(nsr::raster_l1_kernel, dim3((unsigned)P.nblocks, K), dim3(T), 8 * T, stream, P);
     NSR_LAUNCH(nsr::raster_l1_final_kernel, dim3(nblk(K, T)), dim3(T), 0, stream, P);
@@ -1893,6 +1875,9 @@ bool imgmetrics_tiles(int32_t B, int32_t H, int32_t W, int &tx, int &ty) {
     return true;
 }
 
+// the tiles' partial sums (doubles)
+long long imgmetrics_bytes(int32_t B, int tx, int ty) { return 8ll * nsr::kImPartials * B * tx * ty; }
+
 }  // namespace
 
 extern "C" {
@@ -1900,7 +1885,7 @@ extern "C" {
 int64_t nsr_image_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W) {
     int tx = 0, ty = 0;
     if (!imgmetrics_tiles(B, H, W, tx, ty)) return -1;
-    return 8ll * nsr::kImPartials * B * tx * ty;
+    return imgmetrics_bytes(B, tx, ty);
 }
 
 int nsr_image_metrics(const float *color, const float *gt_color, const float *depth, const float *gt_depth, int32_t B, int32_t H, int32_t W,
@@ -1913,7 +1898,7 @@ int nsr_image_metrics(const float *color, const float *gt_color, const float *de
     if (B == 0) return 0;
     if (!color || !gt_color || !depth || !gt_depth || !result || !workspace) return fail("nsr_image_metrics: null pointer");
     P.ntiles = P.tx * P.ty;
-    if (workspace_bytes < 8ll * nsr::kImPartials * B * P.ntiles)
+    if (workspace_bytes < imgmetrics_bytes(B, P.tx, P.ty))
         return fail("nsr_image_metrics: workspace too small (nsr_image_metrics_workspace_bytes)");
     P.color = color; P.gt_color = gt_color; P.depth = depth; P.gt_depth = gt_depth;
     P.B = B; P.H = H; P.W = W;
@@ -2022,14 +2007,8 @@ int nsr_depth_colorize(const float *depth, int32_t B, int32_t H, int32_t W, cons
 // ---- JPEG encoding (include/nsr.h, "JPEG encoding") ----
 namespace {
 
-struct JpegLayout {
-    long long o_coef, o_bitoff, o_raw, o_ibits, o_nff, o_ioff, o_ftot, ws_bytes, out_bytes;
-};
-
-inline long long round16ll(long long v) { return (v + 15) & ~15ll; }
-
-// nullptr: the sizes are valid and P's geometry and L are filled; else what is wrong with them
-const char *jpeg_geometry(int32_t n, int32_t H, int32_t W, int32_t subsampling, nsr::JpegParams &P, JpegLayout &L) {
+// nullptr: the sizes are valid, P's geometry is filled and out_bytes is the output's capacity; else what is wrong with them
+const char *jpeg_geometry(int32_t n, int32_t H, int32_t W, int32_t subsampling, nsr::JpegParams &P, long long &out_bytes) {
     if (n < 0 || n > 65535) return "the batch size must be in [0, 65535]";
     if (H < 1 || W < 1 || H > 65535 || W > 65535) return "image sizes must be in [1, 65535]";
     if (subsampling != 0 && subsampling != 2) return "subsampling must be 0 (4:4:4) or 2 (4:2:0)";
@@ -2045,17 +2024,19 @@ const char *jpeg_geometry(int32_t n, int32_t H, int32_t W, int32_t subsampling, 
     if (nint > 2147483647ll || P.nblocks > 2147483647ll) return "too many blocks for one call";
     P.nint = (int)nint;
     const long long rawcap = ((long long)P.BI * nsr::kJpgBlockBits + 7) / 8;
-    P.rawstride = (unsigned)round16ll(rawcap);
-    L.o_coef = 0;
-    L.o_bitoff = L.o_coef + 128 * P.nblocks;
-    L.o_raw = L.o_bitoff + round16ll(4 * P.nblocks);
-    L.o_ibits = L.o_raw + nint * P.rawstride;
-    L.o_nff = L.o_ibits + round16ll(4 * nint);
-    L.o_ioff = L.o_nff + round16ll(4 * nint);
-    L.o_ftot = L.o_ioff + round16ll(8 * nint);
-    L.ws_bytes = L.o_ftot + round16ll(8ll * n);
-    L.out_bytes = n * (P.mcuy * 2 * rawcap + 2ll * (P.mcuy - 1));
+    P.rawstride = (unsigned)pad16(rawcap);
+    out_bytes = n * (P.mcuy * 2 * rawcap + 2ll * (P.mcuy - 1));
     return nullptr;
+}
+
+void jpeg_carve(nsr::JpegParams &P, Carve &c) {
+    P.coef = c.take<short>(64 * P.nblocks);
+    P.bitoff = c.take<unsigned>(P.nblocks);
+    P.raw = c.take<unsigned char>((long long)P.nint * P.rawstride);
+    P.ibits = c.take<unsigned>(P.nint);
+    P.nff = c.take<unsigned>(P.nint);
+    P.ioff = c.take<long long>(P.nint);
+    P.ftot = c.take<long long>(P.n);
 }
 
 }  // namespace
@@ -2064,25 +2045,25 @@ extern "C" {
 
 int nsr_jpeg_size(int32_t n, int32_t H, int32_t W, int32_t subsampling, int64_t *workspace_bytes, int64_t *out_bytes) {
     nsr::JpegParams P;
-    JpegLayout L;
+    long long cap = 0;
     std::memset(&P, 0, sizeof(P));
-    if (const char *e = jpeg_geometry(n, H, W, subsampling, P, L)) return fail(std::string("nsr_jpeg_size: ") + e);
+    if (const char *e = jpeg_geometry(n, H, W, subsampling, P, cap)) return fail(std::string("nsr_jpeg_size: ") + e);
     if (!workspace_bytes || !out_bytes) return fail("nsr_jpeg_size: null pointer");
-    *workspace_bytes = L.ws_bytes;
-    *out_bytes = L.out_bytes;
+    *workspace_bytes = carve(jpeg_carve, P);
+    *out_bytes = cap;
     return 0;
 }
 
 int nsr_jpeg_encode(const uint8_t *images, int32_t n, int32_t H, int32_t W, int32_t quality, int32_t subsampling, void *workspace,
                     int64_t workspace_bytes, uint8_t *out, int64_t out_bytes, int64_t *offsets, void *stream) {
     nsr::JpegParams P;
-    JpegLayout L;
+    long long cap = 0;
     std::memset(&P, 0, sizeof(P));
-    if (const char *e = jpeg_geometry(n, H, W, subsampling, P, L)) return fail(std::string("nsr_jpeg_encode: ") + e);
+    if (const char *e = jpeg_geometry(n, H, W, subsampling, P, cap)) return fail(std::string("nsr_jpeg_encode: ") + e);
     if (quality < 1 || quality > 100) return fail("nsr_jpeg_encode: quality must be in [1, 100]");
     if (n == 0) return 0;
     if (!images || !workspace || !out || !offsets) return fail("nsr_jpeg_encode: null pointer");
-    if (workspace_bytes < L.ws_bytes || out_bytes < L.out_bytes) return fail("nsr_jpeg_encode: workspace or output smaller than nsr_jpeg_size reports");
+    if (workspace_bytes < carve(jpeg_carve, P, workspace) || out_bytes < cap) return fail("nsr_jpeg_encode: workspace or output smaller than nsr_jpeg_size reports");
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail("nsr_jpeg_encode: the workspace must be 16-byte aligned");
     const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
     for (int c = 0; c < 2; ++c)
@@ -2090,15 +2071,7 @@ int nsr_jpeg_encode(const uint8_t *images, int32_t n, int32_t H, int32_t W, int3
             const int v = (nsr::kJpgQuantBase[c][nsr::kJpgZigzag[k]] * scale + 50) / 100;
             P.q[c][k] = (unsigned char)(v < 1 ? 1 : (v > 255 ? 255 : v));
         }
-    char *ws = static_cast<char *>(workspace);
     P.img = images;
-    P.coef = reinterpret_cast<short *>(ws + L.o_coef);
-    P.bitoff = reinterpret_cast<unsigned *>(ws + L.o_bitoff);
-    P.raw = reinterpret_cast<unsigned char *>(ws + L.o_raw);
-    P.ibits = reinterpret_cast<unsigned *>(ws + L.o_ibits);
-    P.nff = reinterpret_cast<unsigned *>(ws + L.o_nff);
-    P.ioff = reinterpret_cast<long long *>(ws + L.o_ioff);
-    P.ftot = reinterpret_cast<long long *>(ws + L.o_ftot);
     P.out = out;
     P.offsets = reinterpret_cast<long long *>(offsets);
     const int T = nsr::kJpgThreads, scan_lds = nsr::kJpgScanLds;
@@ -2118,13 +2091,8 @@ int nsr_jpeg_encode(const uint8_t *images, int32_t n, int32_t H, int32_t W, int3
 // ---- JPEG decoding (include/nsr.h, "JPEG decoding") ----
 namespace {
 
-struct JpegDecLayout {
-    long long o_coef, o_planes, o_istart, o_nfound, o_mflags, o_cstat, ws_bytes;
-};
-
-// nullptr: the sizes are valid and P's geometry and L are filled; else what is wrong with them
-const char *jpegdec_geometry(int32_t n, int32_t H, int32_t W, int32_t sampling, int32_t subsequence_bytes, nsr::JpegDecParams &P,
-                             JpegDecLayout &L) {
+// nullptr: the sizes are valid and P's geometry is filled; else what is wrong with them
+const char *jpegdec_geometry(int32_t n, int32_t H, int32_t W, int32_t sampling, int32_t subsequence_bytes, nsr::JpegDecParams &P) {
     if (n < 0 || n > 65535) return "the batch size must be in [0, 65535]";
     if (H < 1 || W < 1 || H > 65535 || W > 65535) return "image sizes must be in [1, 65535]";
     if (sampling < NSR_JPEG_444 || sampling > NSR_JPEG_GREY) return "sampling must be 0 (4:4:4), 1 (4:2:2), 2 (4:2:0) or 3 (one component)";
@@ -2147,14 +2115,16 @@ const char *jpegdec_geometry(int32_t n, int32_t H, int32_t W, int32_t sampling, 
     P.ch = (H + P.vs - 1) / P.vs;
     P.poff_c = (long long)P.pw_y * P.mcuy * P.vs * 8;
     P.plane_bytes = P.poff_c + (P.ncomp == 3 ? 2ll * P.pw_c * P.ph_c : 0ll);
-    L.o_coef = 0;
-    L.o_planes = L.o_coef + 128ll * n * P.nblk;
-    L.o_istart = L.o_planes + round16ll(n * P.plane_bytes);
-    L.o_nfound = L.o_istart + round16ll(4ll * n * (M + 1));
-    L.o_mflags = L.o_nfound + round16ll(4ll * n);
-    L.o_cstat = L.o_mflags + round16ll(4ll * n);
-    L.ws_bytes = L.o_cstat + round16ll(4ll * n * M);
     return nullptr;
+}
+
+void jpegdec_carve(nsr::JpegDecParams &P, Carve &c) {
+    P.coef = c.take<short>(64 * P.n * P.nblk);
+    P.planes = c.take<unsigned char>(P.n * P.plane_bytes);
+    P.istart = c.take<int>((long long)P.n * (P.M + 1));
+    P.nfound = c.take<int>(P.n);
+    P.mflags = c.take<int>(P.n);
+    P.cstat = c.take<int>((long long)P.n * P.M);
 }
 
 }  // namespace
@@ -2164,35 +2134,26 @@ extern "C" {
 int nsr_jpegdec_size(int32_t n, int32_t H, int32_t W, int32_t sampling, int64_t max_scan_bytes, int32_t subsequence_bytes,
                      int64_t *workspace_bytes) {
     nsr::JpegDecParams P;
-    JpegDecLayout L;
     std::memset(&P, 0, sizeof(P));
-    if (const char *e = jpegdec_geometry(n, H, W, sampling, subsequence_bytes, P, L)) return fail(std::string("nsr_jpegdec_size: ") + e);
+    if (const char *e = jpegdec_geometry(n, H, W, sampling, subsequence_bytes, P)) return fail(std::string("nsr_jpegdec_size: ") + e);
     if (max_scan_bytes < 0 || max_scan_bytes > nsr::kJpdMaxScan) return fail("nsr_jpegdec_size: max_scan_bytes must be in [0, 2^28]");
     if (!workspace_bytes) return fail("nsr_jpegdec_size: null pointer");
-    *workspace_bytes = L.ws_bytes;
+    *workspace_bytes = carve(jpegdec_carve, P);
     return 0;
 }
 
 int nsr_jpegdec_decode(const uint8_t *files, const nsr_jpegdec_frame *descriptors, int32_t n, int32_t H, int32_t W, int32_t sampling,
                        int32_t subsequence_bytes, void *workspace, int64_t workspace_bytes, uint8_t *out, int32_t *status, void *stream) {
     nsr::JpegDecParams P;
-    JpegDecLayout L;
     std::memset(&P, 0, sizeof(P));
-    if (const char *e = jpegdec_geometry(n, H, W, sampling, subsequence_bytes, P, L)) return fail(std::string("nsr_jpegdec_decode: ") + e);
+    if (const char *e = jpegdec_geometry(n, H, W, sampling, subsequence_bytes, P)) return fail(std::string("nsr_jpegdec_decode: ") + e);
     if (n == 0) return 0;
     if (!files || !descriptors || !workspace || !out || !status) return fail("nsr_jpegdec_decode: null pointer");
-    if (workspace_bytes < L.ws_bytes) return fail("nsr_jpegdec_decode: workspace smaller than nsr_jpegdec_size reports");
+    if (workspace_bytes < carve(jpegdec_carve, P, workspace)) return fail("nsr_jpegdec_decode: workspace smaller than nsr_jpegdec_size reports");
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail("nsr_jpegdec_decode: the workspace must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(descriptors) & 7) return fail("nsr_jpegdec_decode: the descriptors must be 8-byte aligned");
-    char *ws = static_cast<char *>(workspace);
     P.files = files;
     P.desc = descriptors;
-    P.coef = reinterpret_cast<short *>(ws + L.o_coef);
-    P.planes = reinterpret_cast<unsigned char *>(ws + L.o_planes);
-    P.istart = reinterpret_cast<int *>(ws + L.o_istart);
-    P.nfound = reinterpret_cast<int *>(ws + L.o_nfound);
-    P.mflags = reinterpret_cast<int *>(ws + L.o_mflags);
-    P.cstat = reinterpret_cast<int *>(ws + L.o_cstat);
     P.out = out;
     P.status = status;
     const int T = nsr::kJpgThreads, scan_lds = nsr::kJpgScanLds + 16;
@@ -2244,6 +2205,9 @@ const char *frame_geometry(const nsr_frame_desc *d, FrameGeometry &G) {
     return nullptr;
 }
 
+// the undistorted colour frames (nothing without distortion)
+long long frame_ws_bytes(const nsr_frame_desc *d, int32_t B) { return d->has_distortion ? 3ll * B * d->color_h * d->color_w : 0; }
+
 }  // namespace
 
 extern "C" {
@@ -2260,7 +2224,7 @@ int nsr_frame_out_size(const nsr_frame_desc *desc, int32_t *H, int32_t *W) {
 int64_t nsr_frame_workspace_bytes(const nsr_frame_desc *desc, int32_t B) {
     FrameGeometry G;
     if (B < 0 || frame_geometry(desc, G)) return -1;
-    return desc->has_distortion ? 3ll * B * desc->color_h * desc->color_w : 0;
+    return frame_ws_bytes(desc, B);
 }
 
 int nsr_frame_prepare(const void *color_raw, const void *depth_raw, const nsr_frame_desc *desc, int32_t B, float *color, float *depth,
@@ -2270,7 +2234,7 @@ int nsr_frame_prepare(const void *color_raw, const void *depth_raw, const nsr_fr
     if (B < 0) return fail("nsr_frame_prepare: negative batch size");
     if (B == 0) return 0;
     if (!color_raw || !depth_raw || !color || !depth) return fail("nsr_frame_prepare: null pointer");
-    const long long need = desc->has_distortion ? 3ll * B * desc->color_h * desc->color_w : 0;
+    const long long need = frame_ws_bytes(desc, B);
     if (need > 0 && !workspace) return fail("nsr_frame_prepare: null pointer (workspace, needed with distortion)");
     if (workspace_bytes < need) return fail("nsr_frame_prepare: workspace too small (nsr_frame_workspace_bytes)");
     const int T = nsr::kFrThreads;
