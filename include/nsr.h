@@ -125,8 +125,8 @@ typedef struct nsr_render_args {
      * ABI 6).  nsr_acts_floats(stage, n_rays, n_samples + n_surface) floats, device, uninitialised: nsr_render_fwd (given acts, zvals
      * and raw) runs as sample placement -> decoder passes -> compositor and writes, per decoder pass and 16-point tile of the sample list,
      * the five hidden states, the decoder's grid features and the relu masks (13 KB), the sample positions (fp64 and fp32) and, with the
-     * fused loss, d raw; nsr_render_bwd, given the SAME pointer, runs dX / dW / finalize over them.  NULL: forward only (one launch,
-     * nothing saved); nsr_render_bwd then fails. */
+     * fused loss, d raw; nsr_render_bwd, given the SAME pointer, runs dX / dW / finalize over them.  NULL, or given without zvals
+     * or raw: forward only (one launch, nothing saved, the buffer stays untouched); nsr_render_bwd then fails. */
     float *acts;
     void *ev_pass_start;      /* ABI 6, optional hipEvent_t pair recorded on `stream` right before / after the decoder-pass kernel of */
     void *ev_pass_stop;       /* a differentiated forward (the forward's dominant kernel); NULL = no timing                           */

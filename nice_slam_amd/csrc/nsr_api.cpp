@@ -193,9 +193,9 @@ int build_params(const nsr_render_args *a, nsr::RenderParams &P, bool need_rays,
     P.rays_d = a->rays_d;
     P.acts = a->acts;
     P.acts_masks_only = a->acts_masks_only & 15;
-    if (!bwd && a->acts && a->zvals) {
-        // activation buffer: the forward leaves the sample positions (and, with the fused loss, d raw) for the split backward;
-        // the three-launch forward (nsr_fwd2.h) keeps its per-sample scratch there
+    if (!bwd && a->acts && a->zvals && a->raw) {
+        // activation buffer of the three-launch forward (nsr_fwd2.h): it leaves the sample positions (and, with the fused loss,
+        // d raw) for the split backward and keeps its per-sample scratch there
         const SplitLayout L = split_layout(P.stage, P.n_rays, P.S);
         P.draw = a->acts + L.o_draw;
         P.pf = a->acts + L.o_pf;

@@ -56,31 +56,12 @@ NSR_KERNEL void comp_bwd_kernel(const RenderParams P) {
     const double z = act ? P.zvals[gp] : 0.0;
     const Comp cw = comp_weights(rw.w, act, lane);
     const double dz = z - dep;
-    const double s1 = wave_sum_d((double)cw.w * dz);
-    const float Gz = (float)(gD * z + gV * (dz * dz - 2.0 * s1 * z));
-    const float Gw = Gz + fmaf(gb, rw.z, fmaf(gg, rw.y, gr * rw.x));
-    float v = act ? Gw * cw.w : 0.f;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float o = shfl_down(v, d);
-        if (lane + d < 64) v += o;
-    }
-    float suffix = shfl_down(v, 1);
-    if (lane == 63) suffix = 0.f;
-    const float dalpha = Gw * cw.T - suffix / cw.t;
-    float docc = 10.f * (dalpha * ((1.f - cw.alpha) * cw.alpha));
-    // pts = o + d z in fp64 (Renderer.py:172-174); outside the un-enlarged bound the occupancy is overridden and its
-    // gradient cut (Renderer.py:57)
-    const double px = (double)P.rays_o[ray * 3 + 0] + (double)P.rays_d[ray * 3 + 0] * z;
-    const double py = (double)P.rays_o[ray * 3 + 1] + (double)P.rays_d[ray * 3 + 1] * z;
-    const double pz = (double)P.rays_o[ray * 3 + 2] + (double)P.rays_d[ray * 3 + 2] * z;
-    const bool inside = (px > P.blo[0]) && (px < P.bhi[0]) && (py > P.blo[1]) && (py < P.bhi[1]) && (pz > P.blo[2]) && (pz < P.bhi[2]);
-    if (!inside) docc = 0.f;
+    float docc = comp_docc(cw, rw, z, dz, gD, gV, gr, gg, gb, act, lane);
+    const Pos p = sample_pos(P, ray, z);
+    if (!in_bound(P, p.x, p.y, p.z)) docc = 0.f;
     if (act) {
         st4(P.draw + gp * 4, F4{cw.w * gr, cw.w * gg, cw.w * gb, docc});
-        double *q = P.pd + gp * 4;
-        q[0] = px; q[1] = py; q[2] = pz; q[3] = z;
-        st4(P.pf + gp * 4, F4{(float)px, (float)py, (float)pz, 0.f});       // float32(p): what the embedding sees (decoder.py:189)
+        store_pos(P, gp, p, z);
     }
 }
 

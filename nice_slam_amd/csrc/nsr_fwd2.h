@@ -7,16 +7,16 @@
 // When the call saves activations for the split backward (nsr_render_args.acts + zvals) the forward takes the split
 // backward's shape instead:
 //   fwd_sample_kernel        one wave per ray (lane = sample): sample placement (Renderer.py:88-170) and the fp64 sample
-//                            positions (Renderer.py:172-174) -> zvals, pd, pf.  The same expressions as compute_z / the
-//                            position code of render_fwd_kernel, operation by operation.
+//                            positions (Renderer.py:172-174) -> zvals, pd, pf: sample_candidate, stable_rank and sample_pos
+//                            (nsr_kernels.h), the functions compute_z and render_fwd_kernel place their samples with.
 //   render_fwd_pass_kernel   grid = (blocks, decoder passes): a block stages ONE decoder's stream once and its waves walk the
 //                            16-point tiles of the pass independently -- no barrier after the staging.  Feature gather,
 //                            decoder (mlp_xyz_fwd / mlp_nox_fwd with the activation sink), the decoder's output per sample:
 //                            occupancy parts into the (still unused) d raw array of the workspace, colours into `raw`.
 //   fwd_composite_kernel     one wave per ray: occupancy = fine + middle (decoder.py:333,341), bound override
-//                            (Renderer.py:57), raw, compositor (common.py:231-244), depth / variance / colour, and the fused
-//                            mapping loss with d raw for the split backward (Mapper.py:487-493) -- the second half of
-//                            render_fwd_kernel, unchanged.
+//                            (Renderer.py:57), raw, compositor (common.py:231-244), depth / variance / colour (composite) and the
+//                            fused mapping loss (mapping_loss_ray, Mapper.py:487-493) like the second half of render_fwd_kernel,
+//                            then d raw for the split backward: comp_docc, the function comp_bwd_kernel runs.
 // Small batches gain twice: the decoder passes of the tracker's 200 rays run side by side on different CUs instead of one
 // after the other in 50 blocks.
 #pragma once
@@ -36,44 +36,12 @@ NSR_KERNEL void fwd_sample_kernel(const RenderParams P) {
     // (rays the pre-filter removed are placed too: a tile that straddles a removed and a kept ray is evaluated as a whole)
     const bool act = lane < S;
     const int k = act ? lane : 0;
-    const bool guided = (P.gt_depth != nullptr) && (P.stage != NSR_STAGE_COARSE);
-    double z = 0.0;
-    {
-        const double far_bb = ray_far_bb(P, ray);
-        if (!guided) {
-            const float tk = P.t_uniform[k];
-            const float near_part = 0.01f * (1.f - tk);
-            z = (double)near_part + far_bb * (double)tk;
-        } else {
-            const float gdep = P.gt_depth[ray];
-            const float gmax = P.gt_max[0];
-            if (k < P.n_samples) {
-                const float tk = P.t_uniform[k];
-                const double cap = (double)(gmax * 1.2f);
-                const double far = tmin(tmax(far_bb, 0.0), cap);
-                const float near = gdep * 0.01f;
-                z = (double)(near * (1.f - tk)) + far * (double)tk;
-            } else {
-                const double s = P.t_surface[k - P.n_samples];
-                if (gdep > 0.f) {
-                    const double e0 = (double)(0.95f * gdep), e1 = (double)(1.05f * gdep);
-                    z = e0 * (1.0 - s) + e1 * s;
-                } else {
-                    z = 0.001 * (1.0 - s) + (double)gmax * s;
-                }
-            }
-        }
-    }
+    const bool guided = depth_guided(P);
+    double z = sample_candidate(P, ray, k, guided);
     if (P.n_surface > 0 && guided) {
-        // rank sort of the S candidates (torch.sort, Renderer.py:168-170): stable, like compute_z
         if (act) zw[lane] = z;
         wave_fence();
-        int rank = 0;
-#pragma unroll 16
-        for (int j = 0; j < S; ++j) {          // unrolled: 16 LDS reads in flight instead of one latency per compare
-            const double u = zw[j];
-            rank += (u < z || (u == z && j < k)) ? 1 : 0;
-        }
+        const int rank = stable_rank(zw, S, k, z);
         wave_fence();
         if (act) zw[rank] = z;
         wave_fence();
@@ -81,14 +49,8 @@ NSR_KERNEL void fwd_sample_kernel(const RenderParams P) {
     }
     if (!act) return;
     const long long gq = ray * S + lane;
-    // pts = o + d*z in fp64 (Renderer.py:172-174)
-    const double qx = (double)P.rays_o[ray * 3 + 0] + (double)P.rays_d[ray * 3 + 0] * z;
-    const double qy = (double)P.rays_o[ray * 3 + 1] + (double)P.rays_d[ray * 3 + 1] * z;
-    const double qz = (double)P.rays_o[ray * 3 + 2] + (double)P.rays_d[ray * 3 + 2] * z;
     P.zvals[gq] = z;
-    double *pq = P.pd + gq * 4;
-    pq[0] = qx; pq[1] = qy; pq[2] = qz; pq[3] = z;
-    st4(P.pf + gq * 4, F4{(float)qx, (float)qy, (float)qz, 0.f});
+    store_pos(P, gq, sample_pos(P, ray, z), z);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -221,57 +183,29 @@ NSR_KERNEL void fwd_composite_kernel(const RenderParams P) {
             float occ = scr[0];
             if (STAGE >= NSR_STAGE_FINE) occ = scr[1] + scr[0];                             // decoder.py:333,341
             if (STAGE == NSR_STAGE_COLOR) { const float *rc = P.raw + gq * 4; rw.x = rc[0]; rw.y = rc[1]; rw.z = rc[2]; }
-            ins = (qx > P.blo[0]) && (qx < P.bhi[0]) && (qy > P.blo[1]) && (qy < P.bhi[1]) && (qz > P.blo[2]) && (qz < P.bhi[2]);
+            ins = in_bound(P, qx, qy, qz);
             rw.w = ins ? occ : 100.f;                                                       // Renderer.py:57
             st4(P.raw + gq * 4, rw);
         }
         const Comp c = comp_weights(rw.w, act, lane);
-        const float cr = wave_sum(c.w * rw.x), cg = wave_sum(c.w * rw.y), cb = wave_sum(c.w * rw.z);
-        const double depth = wave_sum_d((double)c.w * zq);
-        const double dz = zq - depth;
-        const double var = wave_sum_d(((double)c.w * dz) * dz);
+        const RayOut o = composite(c, rw, zq);
         if (lane == 0) {
-            P.depth[rayq] = depth;
-            P.var[rayq] = var;
-            P.rgb[rayq * 3 + 0] = cr; P.rgb[rayq * 3 + 1] = cg; P.rgb[rayq * 3 + 2] = cb;
+            P.depth[rayq] = o.depth;
+            P.var[rayq] = o.var;
+            P.rgb[rayq * 3 + 0] = o.cr; P.rgb[rayq * 3 + 1] = o.cg; P.rgb[rayq * 3 + 2] = o.cb;
         }
         if (P.loss) {
-            // Mapper.py:487-493 on the rays the pre-filter keeps, and its derivative w.r.t. this ray's outputs (see
-            // render_fwd_kernel: the same expressions)
-            double gD = 0.0;
-            float g3[3] = {0.f, 0.f, 0.f};
-            if (kp && gd > 0.f) {
-                const double df = depth - (double)gd;
-                lterm += fabs(df);
-                gD = df > 0.0 ? 1.0 : (df < 0.0 ? -1.0 : 0.0);
-            }
-            if (kp && STAGE == NSR_STAGE_COLOR && P.gt_color) {
-                const float e[3] = {cr - gtc[0], cg - gtc[1], cb - gtc[2]};
-                lterm += (double)(P.w_color * ((fabsf(e[0]) + fabsf(e[1])) + fabsf(e[2])));
-#pragma unroll
-                for (int q = 0; q < 3; ++q) g3[q] = e[q] > 0.f ? P.w_color : (e[q] < 0.f ? -P.w_color : 0.f);
-            }
+            const RayLoss L = mapping_loss_ray<STAGE>(P, kp, gd, gtc, o.depth, o.cr, o.cg, o.cb);
+            lterm = L.term;
             if (lane == 0) {
-                if (P.dl_depth) P.dl_depth[rayq] = gD;
-                if (P.dl_rgb) { P.dl_rgb[rayq * 3 + 0] = g3[0]; P.dl_rgb[rayq * 3 + 1] = g3[1]; P.dl_rgb[rayq * 3 + 2] = g3[2]; }
+                if (P.dl_depth) P.dl_depth[rayq] = L.gD;
+                if (P.dl_rgb) { P.dl_rgb[rayq * 3 + 0] = L.g3[0]; P.dl_rgb[rayq * 3 + 1] = L.g3[1]; P.dl_rgb[rayq * 3 + 2] = L.g3[2]; }
             }
             if (P.dl_depth) {
-                // d raw per sample for the split backward (comp_bwd_kernel's expressions, d var = 0)
-                const double s1 = wave_sum_d((double)c.w * dz);
-                const float Gz = (float)(gD * zq + 0.0 * (dz * dz - 2.0 * s1 * zq));
-                const float Gw = Gz + fmaf(g3[2], rw.z, fmaf(g3[1], rw.y, g3[0] * rw.x));
-                float v = act ? Gw * c.w : 0.f;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const float o_ = shfl_down(v, d);
-                    if (lane + d < 64) v += o_;
-                }
-                float suffix = shfl_down(v, 1);
-                if (lane == 63) suffix = 0.f;
-                const float dalpha = Gw * c.T - suffix / c.t;
-                float docc = 10.f * (dalpha * ((1.f - c.alpha) * c.alpha));
+                // d raw per sample for the split backward: what comp_bwd_kernel writes for these gradients and d var = 0
+                float docc = comp_docc(c, rw, zq, o.dz, L.gD, 0.0, L.g3[0], L.g3[1], L.g3[2], act, lane);
                 if (!ins) docc = 0.f;
-                if (act) st4(P.draw + gq * 4, F4{c.w * g3[0], c.w * g3[1], c.w * g3[2], docc});
+                if (act) st4(P.draw + gq * 4, F4{c.w * L.g3[0], c.w * L.g3[1], c.w * L.g3[2], docc});
             }
         }
     }

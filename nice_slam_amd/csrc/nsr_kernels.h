@@ -238,55 +238,82 @@ NSR_DEV double ray_far_bb(const RenderParams &P, long long ray) {
     return far + 0.01;
 }
 
+// Is the call depth-guided (uniform samples up to the 1.2 gt_max cap plus surface samples, Renderer.py:107-166)?
+NSR_DEV bool depth_guided(const RenderParams &P) { return (P.gt_depth != nullptr) && (P.stage != NSR_STAGE_COARSE); }
+
+// The unsorted depth of candidate k of a ray: uniform in [0.01, far_bb] (Renderer.py:88-105); guided: uniform between
+// 0.01 gt and min(far_bb, 1.2 gt_max) for k < n_samples, else the surface interval [0.95 gt, 1.05 gt] (no depth: [0.001, gt_max])
+NSR_DEV double sample_candidate(const RenderParams &P, long long ray, int k, bool guided) {
+    const double far_bb = ray_far_bb(P, ray);
+    if (!guided) {
+        const float tk = P.t_uniform[k];
+        const float near_part = 0.01f * (1.f - tk);
+        return (double)near_part + far_bb * (double)tk;
+    }
+    const float g = P.gt_depth[ray];
+    const float gmax = P.gt_max[0];
+    if (k < P.n_samples) {
+        const float tk = P.t_uniform[k];
+        const double cap = (double)(gmax * 1.2f);
+        const double far = tmin(tmax(far_bb, 0.0), cap);
+        const float near = g * 0.01f;
+        return (double)(near * (1.f - tk)) + far * (double)tk;
+    }
+    const double s = P.t_surface[k - P.n_samples];
+    if (g > 0.f) {
+        const double e0 = (double)(0.95f * g), e1 = (double)(1.05f * g);
+        return e0 * (1.0 - s) + e1 * s;
+    }
+    return 0.001 * (1.0 - s) + (double)gmax * s;
+}
+
+// Where torch.sort (Renderer.py:168-170, stable) puts candidate k, of depth v, among the S candidates zr[0..S) of its ray
+NSR_DEV int stable_rank(const double *zr, int S, int k, double v) {
+    int rank = 0;
+#pragma unroll 16
+    for (int j = 0; j < S; ++j) {      // unrolled: 16 LDS reads in flight instead of one latency per compare
+        const double u = zr[j];
+        rank += (u < v || (u == v && j < k)) ? 1 : 0;
+    }
+    return rank;
+}
+
+// pts = o + d z in fp64 (Renderer.py:172-174)
+struct Pos { double x, y, z; };
+NSR_DEV Pos sample_pos(const RenderParams &P, long long ray, double z) {
+    Pos p;
+    p.x = (double)P.rays_o[ray * 3 + 0] + (double)P.rays_d[ray * 3 + 0] * z;
+    p.y = (double)P.rays_o[ray * 3 + 1] + (double)P.rays_d[ray * 3 + 1] * z;
+    p.z = (double)P.rays_o[ray * 3 + 2] + (double)P.rays_d[ray * 3 + 2] * z;
+    return p;
+}
+// Strictly inside the un-enlarged bound?  Outside it the occupancy is overridden and its gradient cut (Renderer.py:57)
+NSR_DEV bool in_bound(const RenderParams &P, double x, double y, double z) {
+    return (x > P.blo[0]) && (x < P.bhi[0]) && (y > P.blo[1]) && (y < P.bhi[1]) && (z > P.blo[2]) && (z < P.bhi[2]);
+}
+// The position record of sample gq in the activation buffer: pd = (p, depth) in fp64, pf = (float32(p), 0): what the embedding
+// sees (decoder.py:189)
+NSR_DEV void store_pos(const RenderParams &P, long long gq, const Pos &p, double z) {
+    double *q = P.pd + gq * 4;
+    q[0] = p.x; q[1] = p.y; q[2] = p.z; q[3] = z;
+    st4(P.pf + gq * 4, F4{(float)p.x, (float)p.y, (float)p.z, 0.f});
+}
+
 // Fills zbuf[rays_per_block][S] (sorted ascending per ray).  ztmp is scratch of the same size.
 NSR_DEV void compute_z(const RenderParams &P, long long ray0, double *ztmp, double *zbuf) {
     const int S = P.S, npts = P.rays_per_block * S;
-    const bool guided = (P.gt_depth != nullptr) && (P.stage != NSR_STAGE_COARSE);
+    const bool guided = depth_guided(P);
     for (int t = tid(); t < npts; t += nthreads()) {
         const int r = t / S, k = t - r * S;
         const long long ray = ray0 + r;
-        double z = 0.0;
-        if (ray < P.n_rays) {
-            const double far_bb = ray_far_bb(P, ray);
-            if (!guided) {
-                const float tk = P.t_uniform[k];
-                const float near_part = 0.01f * (1.f - tk);
-                z = (double)near_part + far_bb * (double)tk;
-            } else {
-                const float g = P.gt_depth[ray];
-                const float gmax = P.gt_max[0];
-                if (k < P.n_samples) {
-                    const float tk = P.t_uniform[k];
-                    const double cap = (double)(gmax * 1.2f);
-                    const double far = tmin(tmax(far_bb, 0.0), cap);
-                    const float near = g * 0.01f;
-                    z = (double)(near * (1.f - tk)) + far * (double)tk;
-                } else {
-                    const double s = P.t_surface[k - P.n_samples];
-                    if (g > 0.f) {
-                        const double e0 = (double)(0.95f * g), e1 = (double)(1.05f * g);
-                        z = e0 * (1.0 - s) + e1 * s;
-                    } else {
-                        z = 0.001 * (1.0 - s) + (double)gmax * s;
-                    }
-                }
-            }
-        }
-        ztmp[t] = z;
+        ztmp[t] = ray < P.n_rays ? sample_candidate(P, ray, k, guided) : 0.0;
     }
     block_sync();
     if (P.n_surface > 0 && guided) {
-        // rank sort of the S candidates of each ray (torch.sort, Renderer.py:168-170)
         for (int t = tid(); t < npts; t += nthreads()) {
             const int r = t / S, k = t - r * S;
             const double v = ztmp[t];
-            int rank = 0;
-#pragma unroll 16
-            for (int j = 0; j < S; ++j) {      // unrolled: 16 LDS reads in flight instead of one latency per compare
-                const double u = ztmp[r * S + j];
-                rank += (u < v || (u == v && j < k)) ? 1 : 0;
-            }
-            zbuf[r * S + rank] = v;
+            zbuf[r * S + stable_rank(ztmp + r * S, S, k, v)] = v;
         }
     } else {
         for (int t = tid(); t < npts; t += nthreads()) zbuf[t] = ztmp[t];
@@ -872,6 +899,57 @@ NSR_DEV double wave_sum_d(double v) {
     return v;
 }
 
+// The outputs of a wave's ray from its samples' weights: colour, depth, variance (common.py:238-244); dz = z - depth per lane
+struct RayOut { float cr, cg, cb; double depth, dz, var; };
+NSR_DEV RayOut composite(const Comp &c, const F4 &rw, double zq) {
+    RayOut o;
+    o.cr = wave_sum(c.w * rw.x); o.cg = wave_sum(c.w * rw.y); o.cb = wave_sum(c.w * rw.z);
+    o.depth = wave_sum_d((double)c.w * zq);
+    o.dz = zq - o.depth;
+    o.var = wave_sum_d(((double)c.w * o.dz) * o.dz);
+    return o;
+}
+
+// Mapper.py:487-493 for one ray that the pre-filter keeps (kp), and its derivative w.r.t. the ray's outputs:
+// d|gt - depth| = sign(depth - gt) where gt > 0, w_color * sign(rgb - gt_rgb) in the colour stage
+// (every lane of the wave evaluates the same scalars)
+struct RayLoss { double term, gD; float g3[3]; };
+template <int STAGE>
+NSR_DEV RayLoss mapping_loss_ray(const RenderParams &P, bool kp, float gd, const float (&gtc)[3], double depth, float cr, float cg, float cb) {
+    RayLoss L = {0.0, 0.0, {0.f, 0.f, 0.f}};
+    if (kp && gd > 0.f) {
+        const double df = depth - (double)gd;
+        L.term += fabs(df);
+        L.gD = df > 0.0 ? 1.0 : (df < 0.0 ? -1.0 : 0.0);
+    }
+    if (kp && STAGE == NSR_STAGE_COLOR && P.gt_color) {
+        const float e[3] = {cr - gtc[0], cg - gtc[1], cb - gtc[2]};
+        L.term += (double)(P.w_color * ((fabsf(e[0]) + fabsf(e[1])) + fabsf(e[2])));
+#pragma unroll
+        for (int q = 0; q < 3; ++q) L.g3[q] = e[q] > 0.f ? P.w_color : (e[q] < 0.f ? -P.w_color : 0.f);
+    }
+    return L;
+}
+
+// Compositor backward (common.py:231-244 differentiated): d occupancy of the lane's sample, before the bound cut, from the
+// gradients of the ray's depth (gD), variance (gV) and colour (gr, gg, gb); dz = z - depth.  The forward's loss epilogue passes
+// gV = 0.0: the product stays in the expression (0.0 * x propagates NaN / inf like the backward kernel's does).
+NSR_DEV float comp_docc(const Comp &c, const F4 &rw, double z, double dz, double gD, double gV, float gr, float gg, float gb, bool act, int lane) {
+    const double s1 = wave_sum_d((double)c.w * dz);
+    const float Gz = (float)(gD * z + gV * (dz * dz - 2.0 * s1 * z));
+    const float Gw = Gz + fmaf(gb, rw.z, fmaf(gg, rw.y, gr * rw.x));
+    float v = act ? Gw * c.w : 0.f;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const float o = shfl_down(v, d);
+        if (lane + d < 64) v += o;
+    }
+    float suffix = shfl_down(v, 1);
+    if (lane == 63) suffix = 0.f;
+    const float dalpha = Gw * c.T - suffix / c.t;
+    return 10.f * (dalpha * ((1.f - c.alpha) * c.alpha));
+}
+
 // NICE.forward for the tile of this wave with the packed weights staged in LDS, one decoder after the other
 // (block-wide barriers inside: EVERY wave of the block must call it).  On entry `wl` holds the first decoder of the
 // stage (coarse or middle); on exit the last one.  Returns (r,g,b,occ) before the out-of-bound override.
@@ -963,13 +1041,9 @@ NSR_KERNEL NSR_BOUNDS(768) void render_fwd_kernel(const RenderParams P) {
         const bool active = (pidx < npts) && (ray < P.n_rays);
         const long long rr = active ? ray : 0;
         const double z = active ? zbuf[pidx] : 0.0;
-        // pts = o + d*z in fp64 (Renderer.py:172-174)
-        const double px = (double)P.rays_o[rr * 3 + 0] + (double)P.rays_d[rr * 3 + 0] * z;
-        const double py = (double)P.rays_o[rr * 3 + 1] + (double)P.rays_d[rr * 3 + 1] * z;
-        const double pz = (double)P.rays_o[rr * 3 + 2] + (double)P.rays_d[rr * 3 + 2] * z;
-        const bool inside = (px > P.blo[0]) && (px < P.bhi[0]) && (py > P.blo[1]) && (py < P.bhi[1]) &&
-                            (pz > P.blo[2]) && (pz < P.bhi[2]);
-        F4 raw = decode_tile_lds<STAGE>(P, aux, wl, px, py, pz, lane);
+        const Pos p = sample_pos(P, rr, z);
+        const bool inside = in_bound(P, p.x, p.y, p.z);
+        F4 raw = decode_tile_lds<STAGE>(P, aux, wl, p.x, p.y, p.z, lane);
         dbg.stamp(6);
         if (!inside) raw.w = 100.f;                                         // Renderer.py:57
         if (active && g == 0) {
@@ -986,69 +1060,22 @@ NSR_KERNEL NSR_BOUNDS(768) void render_fwd_kernel(const RenderParams P) {
             const F4 rw = act ? rawbuf[rq * S + lane] : F4{0.f, 0.f, 0.f, 0.f};
             const double zq = act ? zbuf[rq * S + lane] : 0.0;
             const Comp c = comp_weights(rw.w, act, lane);
-            const float cr = wave_sum(c.w * rw.x), cg = wave_sum(c.w * rw.y), cb = wave_sum(c.w * rw.z);
-            const double depth = wave_sum_d((double)c.w * zq);
-            const double dz = zq - depth;
-            const double var = wave_sum_d(((double)c.w * dz) * dz);
+            const RayOut o = composite(c, rw, zq);
             if (lane == 0) {
-                P.depth[rayq] = depth;
-                P.var[rayq] = var;
-                P.rgb[rayq * 3 + 0] = cr; P.rgb[rayq * 3 + 1] = cg; P.rgb[rayq * 3 + 2] = cb;
+                P.depth[rayq] = o.depth;
+                P.var[rayq] = o.var;
+                P.rgb[rayq * 3 + 0] = o.cr; P.rgb[rayq * 3 + 1] = o.cg; P.rgb[rayq * 3 + 2] = o.cb;
             }
-            if (P.loss) {
-                // Mapper.py:487-493 on the rays the pre-filter keeps, and its derivative w.r.t. this ray's outputs:
-                // d|gt - depth| = sign(depth - gt) where gt > 0, w_color * sign(rgb - gt_rgb) in the colour stage
-                // (every lane of the wave evaluates the same scalars; lane 0 publishes them)
+            if (P.loss) {                          // (lane 0 publishes the ray's loss term and derivatives)
                 const bool kp = !P.keep || P.keep[rayq];
                 const float gd = P.loss_depth ? P.loss_depth[rayq] : 0.f;
-                double gD = 0.0, lterm = 0.0;
-                float g3[3] = {0.f, 0.f, 0.f};
-                if (kp && gd > 0.f) {
-                    const double df = depth - (double)gd;
-                    lterm += fabs(df);
-                    gD = df > 0.0 ? 1.0 : (df < 0.0 ? -1.0 : 0.0);
-                }
-                if (kp && STAGE == NSR_STAGE_COLOR && P.gt_color) {
-                    const float e[3] = {cr - P.gt_color[rayq * 3 + 0], cg - P.gt_color[rayq * 3 + 1], cb - P.gt_color[rayq * 3 + 2]};
-                    lterm += (double)(P.w_color * ((fabsf(e[0]) + fabsf(e[1])) + fabsf(e[2])));
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) g3[q] = e[q] > 0.f ? P.w_color : (e[q] < 0.f ? -P.w_color : 0.f);
-                }
+                float gtc[3] = {0.f, 0.f, 0.f};
+                if (kp && STAGE == NSR_STAGE_COLOR && P.gt_color) { gtc[0] = P.gt_color[rayq * 3 + 0]; gtc[1] = P.gt_color[rayq * 3 + 1]; gtc[2] = P.gt_color[rayq * 3 + 2]; }
+                const RayLoss L = mapping_loss_ray<STAGE>(P, kp, gd, gtc, o.depth, o.cr, o.cg, o.cb);
                 if (lane == 0) {
-                    loss_acc += lterm;
-                    if (P.dl_depth) P.dl_depth[rayq] = gD;
-                    if (P.dl_rgb) { P.dl_rgb[rayq * 3 + 0] = g3[0]; P.dl_rgb[rayq * 3 + 1] = g3[1]; P.dl_rgb[rayq * 3 + 2] = g3[2]; }
-                }
-                if (P.draw) {
-                    // ... and, for the split backward (nsr_bwd2.h), what its compositor-backward kernel would compute from
-                    // them: d raw per sample, the sample's position and bound test -- one launch fewer per iteration.  Same
-                    // expressions as comp_bwd_kernel (d var = 0).
-                    const double dzc = zq - depth;
-                    const double s1 = wave_sum_d((double)c.w * dzc);
-                    const float Gz = (float)(gD * zq + 0.0 * (dzc * dzc - 2.0 * s1 * zq));
-                    const float Gw = Gz + fmaf(g3[2], rw.z, fmaf(g3[1], rw.y, g3[0] * rw.x));
-                    float v = act ? Gw * c.w : 0.f;
-#pragma unroll
-                    for (int d = 1; d < 64; d <<= 1) {
-                        const float o_ = shfl_down(v, d);
-                        if (lane + d < 64) v += o_;
-                    }
-                    float suffix = shfl_down(v, 1);
-                    if (lane == 63) suffix = 0.f;
-                    const float dalpha = Gw * c.T - suffix / c.t;
-                    float docc = 10.f * (dalpha * ((1.f - c.alpha) * c.alpha));
-                    const double qx = (double)P.rays_o[rayq * 3 + 0] + (double)P.rays_d[rayq * 3 + 0] * zq;
-                    const double qy = (double)P.rays_o[rayq * 3 + 1] + (double)P.rays_d[rayq * 3 + 1] * zq;
-                    const double qz = (double)P.rays_o[rayq * 3 + 2] + (double)P.rays_d[rayq * 3 + 2] * zq;
-                    const bool ins = (qx > P.blo[0]) && (qx < P.bhi[0]) && (qy > P.blo[1]) && (qy < P.bhi[1]) && (qz > P.blo[2]) && (qz < P.bhi[2]);
-                    if (!ins) docc = 0.f;
-                    if (act) {
-                        const long long gq = rayq * S + lane;
-                        st4(P.draw + gq * 4, F4{c.w * g3[0], c.w * g3[1], c.w * g3[2], docc});
-                        double *pq = P.pd + gq * 4;
-                        pq[0] = qx; pq[1] = qy; pq[2] = qz; pq[3] = zq;
-                        st4(P.pf + gq * 4, F4{(float)qx, (float)qy, (float)qz, 0.f});
-                    }
+                    loss_acc += L.term;
+                    if (P.dl_depth) P.dl_depth[rayq] = L.gD;
+                    if (P.dl_rgb) { P.dl_rgb[rayq * 3 + 0] = L.g3[0]; P.dl_rgb[rayq * 3 + 1] = L.g3[1]; P.dl_rgb[rayq * 3 + 2] = L.g3[2]; }
                 }
             }
         }
@@ -1080,8 +1107,7 @@ NSR_KERNEL NSR_BOUNDS(768) void eval_points_kernel(const RenderParams P) {
         const long long pp = active ? pi : 0;
         const double px = P.points[pp * 3 + 0], py = P.points[pp * 3 + 1], pz = P.points[pp * 3 + 2];
         F4 raw = decode_tile_lds<STAGE>(P, aux, wl, px, py, pz, lane);
-        const bool inside = (px > P.blo[0]) && (px < P.bhi[0]) && (py > P.blo[1]) && (py < P.bhi[1]) &&
-                            (pz > P.blo[2]) && (pz < P.bhi[2]);
+        const bool inside = in_bound(P, px, py, pz);
         if (!inside) raw.w = 100.f;                                         // Renderer.py:57
         if (active && (lane >> 4) == 0) st4(P.out_points + pi * 4, raw);
         block_sync();                                                       // before the next group re-stages the weights

@@ -874,6 +874,79 @@ def test_fused_forward_leaves_d_raw_for_the_split_backward(emu, stage):
         assert rel_err(edited[k], -3.0 * v) < 1e-5, (stage, k)
 
 
+def _glue_scene():
+    """21 rays, the fused loss with a ray mask: the inputs of the two tests below"""
+    s = make_scene(seed=122, n_rays=21, small=True)
+    g = torch.Generator().manual_seed(5)
+    keep = (torch.rand((21,), generator=g) < 0.8).numpy().astype(np.uint8)
+    return s, keep
+
+
+def _acts_tail(acts, stage, npts):
+    """The end of nsr_render_args.acts behind the saved activations and dY: (all of it, d raw [npad][4] f32, pf [npad][4] f32,
+    pd [npad][4] f64) as views"""
+    npad = (npts + 15) // 16 * 16
+    passes = max(1, STAGES.index(stage))
+    beg = passes * 23 * npad * 16                      # 13 activation + 10 dY slots of [npad][16] floats per decoder pass
+    assert acts.size == beg + npad * 16
+    tail = acts[beg:]
+    return tail, tail[:npad * 4].reshape(npad, 4), tail[npad * 4:npad * 8].reshape(npad, 4), tail[npad * 8:].view(np.float64).reshape(npad, 4)
+
+
+def _same_bytes(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("skip", [False, True])
+@pytest.mark.parametrize("stage,n_samples,n_surface", [("coarse", 32, 16), ("middle", 32, 16), ("fine", 32, 5), ("color", 32, 16),
+                                                       ("color", 32, 5), ("color", 1, 1), ("fine", 60, 3)])
+def test_forward_epilogue_and_comp_bwd_write_the_same_bytes(emu, stage, n_samples, n_surface, skip):
+    """The split backward reads d raw and the sample positions either from the fused forward's epilogue or from comp_bwd_kernel:
+    both call comp_docc / sample_pos / in_bound / store_pos (nsr_kernels.h), so for the forward's own dl_* arrays and no gradient
+    scale the two leave the SAME BYTES on every sample of every ray that is part of the batch, and zeros as d raw of the rays
+    skip_masked removed."""
+    s, keep = _glue_scene()
+    sc = _host_scene(emu, s["grids"], s["params"], s["bound"].numpy())
+    sc.n_samples, sc.n_surface = n_samples, n_surface
+    fl = {"gt_color": s["gt_color"].numpy(), "keep": keep, "w_color": 0.2, "skip_masked": skip}
+    fwd = sc.forward(stage, s["rays_o"].numpy(), s["rays_d"].numpy(), s["gt_depth"].numpy(), fused_loss=fl)
+    S = fwd["_ctx"][5]
+    tail, draw, pf, pd = _acts_tail(fwd["acts"], stage, 21 * S)
+    first = [draw.copy(), pf.copy(), pd.copy()]
+    tail[:] = np.nan
+    sc.backward(stage, fwd, None, None, None, in_place=True)          # same dl_* pointers, flag off: comp_bwd_kernel runs
+    live = np.repeat(keep.astype(bool) if skip else np.ones(21, dtype=bool), S)
+    for name, a, b in zip(("draw", "pf", "pd"), first, (draw, pf, pd)):
+        a, b = a[:21 * S][live], b[:21 * S][live]
+        assert not np.isnan(a).any() and not np.isnan(b).any(), name
+        assert _same_bytes(a, b), (name, np.abs(a - b).max())
+    if skip:
+        assert (~live).any() and not first[0][:21 * S][~live].any() and not draw[:21 * S][~live].any()
+
+
+@pytest.mark.parametrize("stage,n_samples,n_surface", [("coarse", 32, 16), ("middle", 32, 16), ("fine", 32, 5), ("color", 32, 16),
+                                                       ("color", 1, 1), ("fine", 60, 3)])
+def test_the_two_forwards_agree_with_the_fused_loss(emu, stage, n_samples, n_surface):
+    """The one-launch forward and the three-launch forward place, composite and score a ray with the same functions
+    (sample_candidate, stable_rank, sample_pos, composite, mapping_loss_ray): byte-equal outputs and loss derivatives; the loss
+    itself is summed in another block order."""
+    s, keep = _glue_scene()
+    fl = {"gt_color": s["gt_color"].numpy(), "keep": keep, "w_color": 0.2}
+    res = {}
+    for mode in (True, False):
+        sc = _host_scene(emu, s["grids"], s["params"], s["bound"].numpy())
+        sc.n_samples, sc.n_surface = n_samples, n_surface
+        sc.save_acts = mode
+        res[mode] = sc.forward(stage, s["rays_o"].numpy(), s["rays_d"].numpy(), s["gt_depth"].numpy(), fused_loss=fl)
+        assert ("acts" in res[mode]) == mode
+    for k in ("depth", "var", "rgb", "raw", "zvals", "dl_depth") + (("dl_rgb",) if stage == "color" else ()):
+        assert not np.isnan(res[True][k]).any(), k
+        assert _same_bytes(res[True][k], res[False][k]), k
+    l1, l0 = res[True]["loss"][0], res[False]["loss"][0]
+    assert l0 > 0 and abs(l1 - l0) <= 1e-12 * abs(l0), (l1, l0)
+
+
 @pytest.mark.parametrize("stage,n_surface,n_samples", [("coarse", 16, 32), ("middle", 16, 32), ("color", 16, 32), ("color", 5, 32),
                                                        ("middle", 0, 1), ("color", 1, 1), ("fine", 3, 60)])
 def test_masked_rays_are_removed_from_the_batch(emu, stage, n_surface, n_samples):

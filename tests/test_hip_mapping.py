@@ -626,3 +626,41 @@ def test_stepped_decoders_only(stepped, fused):
         assert rel_err(g1[k], g0[k]) < 1e-5, k
     for a, b in zip(c0, c1):
         assert rel_err(b, a) < 1e-5
+
+
+def test_forward_epilogue_and_comp_bwd_write_the_same_bytes():
+    """A fused mapping iteration's backward starts from the d raw / position records the forward's loss epilogue left in the
+    activation buffer; handed the same dl_* arrays WITHOUT the from-forward flag it runs comp_bwd_kernel instead.  Both call one
+    set of functions (comp_docc, sample_pos, in_bound, store_pos: csrc/nsr_kernels.h): the records of every kept ray are the
+    same bytes.  48 samples per ray, and 37 (N_surface = 5): tiles that straddle rays, a ragged last tile."""
+    import nice_slam_amd as nsa
+    from nice_slam_amd.renderer import render_backward
+    sc = make_scene(seed=82, n_rays=8, small=True)
+    H, W = sc["intr"][:2]
+    K, n = 2, 23
+    idx = torch.randint(H * W, (K * n,), generator=torch.Generator().manual_seed(5))
+    for n_surface in (16, 5):
+        renderer, dec, grids_dev = build_product(sc, DEV, n_surface=n_surface)
+        frames = _frames(sc, K, DEV, grad=True)
+        c = {k: v.detach().clone(memory_format=torch.preserve_format).requires_grad_(True) for k, v in grids_dev.items()}
+        for p in dec.parameters():
+            p.requires_grad_(True); p.grad = None
+        out = {}
+        loss = nsa.mapping_loss(renderer, c, dec, frames, n, "color", w_color=0.2, indices=idx, out=out)
+        st = loss.grad_fn.state
+        acts = st.call.hold[-1]
+        S, N = 32 + n_surface, K * n
+        npad = (N * S + 15) // 16 * 16
+        beg = 3 * 23 * npad * 16                       # 13 activation + 10 dY slots of [npad][16] floats for each of the three passes
+        assert acts.dtype == torch.float32 and acts.numel() == beg + npad * 16
+        tail = acts[beg:]                              # d raw [npad][4] f32 | pf [npad][4] f32 | pd [npad][4] f64
+        first = tail.clone()
+        tail.fill_(float("nan"))
+        render_backward(st.call, st.need, st.dl_depth, None, st.dl_rgb)      # flag off: comp_bwd_kernel runs
+        live = out["keep"].bool().repeat_interleave(S)
+        assert 0 < int(live.sum()) and live.numel() == N * S
+        for name, lo, hi, dt in (("draw", 0, npad * 4, torch.float32), ("pf", npad * 4, npad * 8, torch.float32), ("pd", npad * 8, npad * 16, torch.float64)):
+            a = first[lo:hi].view(dt).view(npad, 4)[:N * S][live]
+            b = tail[lo:hi].view(dt).view(npad, 4)[:N * S][live]
+            assert not torch.isnan(a).any() and not torch.isnan(b).any(), (n_surface, name)
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (n_surface, name, float((a - b).abs().max()))
