@@ -1,4 +1,5 @@
 // nsr_api.cpp -- the C ABI of libnsr.so (see include/nsr.h).  Compiled as HIP for gfx950.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -6,6 +7,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 
 #include "nsr_rt.h"
@@ -78,7 +80,6 @@ constexpr int kFinThreads = 1024;
 constexpr int kFwdWeight = 10;
 inline int fwd_fine_weight(int stage) { return stage == NSR_STAGE_FINE ? 12 : 14; }
 
-inline int round16(int bytes) { return (bytes + 15) & ~15; }
 inline unsigned nblk(long long n, int tb) { return (unsigned)((n + tb - 1) / tb); }
 
 // ---- caller-allocated workspaces ---------------------------------------------------------------------------------------------
@@ -105,61 +106,130 @@ long long carve(void (*describe)(Params &, Carve &), Params &P, const void *work
     return c.at;
 }
 
-// forward: up to 12 tiles (768 threads, 3 waves/SIMD, <=168 VGPRs)
-int rays_per_block(int S) {
-    const int rb = (kMaxTiles * nsr::kTile) / S;
-    return rb < 1 ? 1 : rb;
+int finish(const char *what) {
+    if (const char *e = nsr::rt_check_last()) return fail(std::string(what) + ": " + e);
+    return 0;
 }
 
-int stage_passes(int stage) { return stage == NSR_STAGE_COARSE ? 1 : 3; }
+// ---- a render stage: its decoder slots and passes -----------------------------------------------------------------------------
+// The coarse stage runs the coarse decoder alone; the middle, fine and colour stages run the decoders from the middle one up to
+// their own (middle 1, fine 2, colour 3), one decoder pass each: pass p is slot first + p.  A block of the pass, dX and dW kernels
+// serves ONE pass -- that decoder's operand stream sits in its LDS.
+struct StageSlots {
+    int first, last, passes;
+    explicit StageSlots(int stage)
+        : first(stage == NSR_STAGE_COARSE ? NSR_COARSE : NSR_MIDDLE), last(stage == NSR_STAGE_COARSE ? NSR_COARSE : stage), passes(last - first + 1) {}
+    int slot(int pass) const { return first + pass; }
+    int pass_of(int slot) const { return slot - first; }
+    // the largest f(slot) over the stage's slots
+    template <typename F> int most(F f) const { int m = 0; for (int s = first; s <= last; ++s) m = std::max(m, (int)f(s)); return m; }
+};
+// floats between two partial images of the gradient blob: the coarse decoder's count, else the fine decoder's (the largest)
+int partial_stride(int stage) { return nsr::param_total(stage == NSR_STAGE_COARSE ? NSR_COARSE : NSR_FINE); }
 
-int max_param_count(int stage) {
-    return stage == NSR_STAGE_COARSE ? nsr::param_total(0) : nsr::param_total(2);
+inline long long tiles_of(long long n_points) { return (n_points + nsr::kTile - 1) / nsr::kTile; }
+
+// ---- the block deal -------------------------------------------------------------------------------------------------------------
+// `total` blocks over the decoder passes in proportion to a weight: blocks [beg[p], beg[p + 1]) serve pass p.  A share is
+// floor(total * w / sum of w) -- or, for the last pass with `remainder_to_last`, what the others left --, raised to 1, clamped
+// to `tiles`; 0 where w == 0 or p >= passes.  (Raised shares can push the sum past `total`: the callers that size a workspace by
+// `total` check beg[3], see deal_bwd.)
+void deal_blocks(int beg[4], int total, const int wgt[3], int passes, long long tiles, bool remainder_to_last) {
+    int wsum = 0, used = 0;
+    for (int p = 0; p < passes; ++p) wsum += wgt[p];
+    beg[0] = 0;
+    for (int p = 0; p < 3; ++p) {
+        long long n = 0;
+        if (p < passes && wgt[p] > 0) {
+            n = remainder_to_last && p == passes - 1 ? total - used : (long long)total * wgt[p] / wsum;
+            if (n < 1) n = 1;
+            if (n > tiles) n = tiles;
+        }
+        used += (int)n;
+        beg[p + 1] = beg[p] + (int)n;
+    }
 }
 
-// Decoder passes of one backward launch: a block serves ONE pass -- that decoder's operand stream sits in its LDS.
-int bwd_passes(int stage) { return stage == NSR_STAGE_COARSE ? 1 : stage; }     // middle 1, fine 2, colour 3
+// ---- launches -----------------------------------------------------------------------------------------------------------------
+// raise the dynamic-LDS limit of a kernel once per (kernel, device, size): not a stream operation, but kept out of the
+// steady state so that a captured hipGraph contains kernel launches only.  Keyed by the kernel's ADDRESS (all render
+// kernels share one function-pointer type) and the current device.
+template <typename K>
+int launch_cfg(K kernel, int lds_bytes, const char *what) {
+    if (lds_bytes > kLdsLimit) return fail(std::string(what) + ": LDS budget exceeded");
+    if (lds_bytes <= 48 * 1024) return 0;
+    static std::mutex mu;
+    static std::map<std::pair<const void *, int>, int> granted;
+    const std::pair<const void *, int> key(reinterpret_cast<const void *>(kernel), nsr::rt_current_device());
+    std::lock_guard<std::mutex> lock(mu);
+    int &g = granted[key];
+    if (lds_bytes > g) {
+        if (const char *e = nsr::rt_allow_lds(kernel, lds_bytes)) return fail(std::string(what) + ": " + e);
+        g = lds_bytes;
+    }
+    return 0;
+}
+// a kernel with dynamic LDS: the grant, then the launch
+template <typename Params>
+int launch_kernel(void (*kernel)(Params), dim3 grid, dim3 block, int lds_bytes, const char *what, void *stream, const Params &P) {
+    if (int rc = launch_cfg(kernel, lds_bytes, what)) return rc;
+    NSR_LAUNCH(kernel, grid, block, lds_bytes, stream, P);
+    return 0;
+}
+// the run-time stage (or decoder slot) as a compile-time constant: f(Int<stage>()), ST() inside f
+template <int N> using Int = std::integral_constant<int, N>;
+template <typename F> int with_stage(int stage, F f) {
+    return stage == 0 ? f(Int<0>()) : stage == 1 ? f(Int<1>()) : stage == 2 ? f(Int<2>()) : f(Int<3>());
+}
+
+// ---- LDS bytes of a block -----------------------------------------------------------------------------------------------------
+// the largest need over the stage's decoders.  One-launch forward and eval_points: three aux tables, the block's own bytes, the
+// operand stream; pass kernels: aux table, stream, tile counter; dX: aux table, transposed stream, a staging area per wave, tile
+// counter (the hot-voxel table and the coarse grid: launch_dx)
+int fwd_lds_bytes(int stage, int own_bytes) { return (int)pad16(3 * nsr::AUX_FLOATS * 4) + own_bytes + StageSlots(stage).most(nsr::packed_total) * 4; }
+int pass_lds_bytes(int stage) { return (nsr::AUX_FLOATS + StageSlots(stage).most(nsr::packed_total) + 4) * 4; }
+int dx_lds_bytes(int stage, int waves) { return (nsr::AUX_FLOATS + StageSlots(stage).most(nsr::packedT_total) + waves * nsr::kDxStg + 4) * 4; }
+int dw_lds_bytes(int stage) { return StageSlots(stage).most(nsr::dw_lds_bytes); }
+
+// ---- nsr_render_args.acts ------------------------------------------------------------------------------------------------------
+// [passes][tiles][kActSlots][16][16] saved by the forward | [passes][tiles][kDySlots][16][16] dY (dX kernel -> dW kernel) |
+// [npad][4] d raw | [npad][4] fp32 positions | [npad][4] doubles: position + depth.  npad = 16 * tiles = the sample points rounded
+// up to whole 16-point tiles (DMA pieces of 1 KB): every piece is a multiple of 256 bytes.  Reads P.stage, P.n_rays, P.S.
+void describe_acts(nsr::RenderParams &P, Carve &c) {
+    const long long passes = StageSlots(P.stage).passes;
+    P.act_tiles = tiles_of(P.n_rays * P.S);
+    const long long npad = P.act_tiles * nsr::kTile, slot = npad * 16;      // slot: floats between two slots
+    c.take<float>(passes * nsr::kActSlots * slot);                           // (= P.acts itself)
+    P.dy = c.take<float>(passes * nsr::kDySlots * slot);
+    P.draw = c.take<float>(npad * 4);
+    P.pf = c.take<float>(npad * 4);
+    P.pd = c.take<double>(npad * 4);
+}
+// the pieces behind the saved activations (null without a buffer) and P.act_tiles; dY is the backward's alone
+void bind_acts(nsr::RenderParams &P, const float *acts, bool bwd) {
+    carve(describe_acts, P, acts);
+    if (!bwd) P.dy = nullptr;
+}
 
 // ---- split backward over saved activations (nsr_bwd2.h) -----------------------------------------------------------------
-// layout of nsr_render_args.acts (floats): [passes][tiles][kActSlots][16][16] saved by the forward | [passes][tiles][kDySlots]
-// [16][16] dY (dX kernel -> dW kernel) | [npad][4] d raw | [npad][4] fp32 positions | [npad][4] doubles: position + depth.  npad = 16 * tiles = the
-// sample points rounded up to whole 16-point tiles (DMA pieces of 1 KB).
-struct SplitLayout {
-    long long npts, npad, stride;      // stride: floats between two slots
-    long long o_dy, o_draw, o_pf, o_pd, total;
-};
-SplitLayout split_layout(int stage, long long n_rays, int S) {
-    SplitLayout L;
-    const int passes = bwd_passes(stage);
-    L.npts = n_rays * S;
-    L.npad = (L.npts + nsr::kTile - 1) / nsr::kTile * nsr::kTile;
-    L.stride = L.npad * 16;
-    L.o_dy = (long long)passes * nsr::kActSlots * L.stride;
-    L.o_draw = L.o_dy + (long long)passes * nsr::kDySlots * L.stride;
-    L.o_pf = L.o_draw + L.npad * 4;
-    L.o_pd = L.o_pf + L.npad * 4;
-    L.total = L.o_pd + L.npad * 8;
-    return L;
-}
 // launch geometry: the dX kernel runs `nb` blocks of `waves` waves per decoder pass (one block per CU over all passes,
 // fewer waves per block when the batch is small: every CU gets work); the dW kernel `nimg` blocks per pass, each of which
 // leaves one partial image of the gradient blob.
 struct SplitGeo { int nb, waves, nimg; };             // dX: blocks per pass, waves per block; dW: images per pass
 SplitGeo split_geo(int stage, long long n_rays, int S, int max_blocks) {
+    const long long tiles = tiles_of(n_rays * S), per_pass = std::max(1, (max_blocks > 0 ? max_blocks : kDefaultBwdBlocks) / StageSlots(stage).passes);
     SplitGeo G;
-    const int passes = bwd_passes(stage);
-    const long long tiles = (n_rays * S + nsr::kTile - 1) / nsr::kTile;
-    const int cap = max_blocks > 0 ? max_blocks : kDefaultBwdBlocks;
-    int per_pass = cap / passes;
-    if (per_pass < 1) per_pass = 1;
-    long long w = (tiles + per_pass - 1) / per_pass;
-    G.waves = (int)(w < 1 ? 1 : (w > nsr::kDxMaxWaves ? nsr::kDxMaxWaves : w));
-    const long long nb = (tiles + G.waves - 1) / G.waves;
-    G.nb = (int)(nb < 1 ? 1 : (nb > per_pass ? per_pass : nb));
-    long long ni = per_pass;
-    if (ni > tiles) ni = tiles;
-    G.nimg = (int)(ni < 1 ? 1 : ni);
+    G.waves = (int)std::clamp<long long>((tiles + per_pass - 1) / per_pass, 1, nsr::kDxMaxWaves);
+    G.nb = (int)std::clamp<long long>((tiles + G.waves - 1) / G.waves, 1, per_pass);
+    G.nimg = (int)std::clamp<long long>(tiles, 1, per_pass);
     return G;
+}
+// nsr_bwd_args.workspace (floats): [passes][nimg] partial images of the dW kernel, partial_stride floats each | [passes][nb][kDbPart]
+// d _B partials of the dX kernel.  (Not a Carve: an image is no multiple of 16 bytes.)
+struct BwdWorkspace { long long dbpart, floats; };     // where the d _B partials start, the whole
+BwdWorkspace bwd_workspace(int stage, const SplitGeo &G) {
+    const long long passes = StageSlots(stage).passes, dbpart = passes * G.nimg * partial_stride(stage);
+    return {dbpart, dbpart + passes * G.nb * nsr::kDbPart};
 }
 
 // validate + translate the public argument block
@@ -181,36 +251,27 @@ int build_params(const nsr_render_args *a, nsr::RenderParams &P, bool need_rays,
         if (a->n_rays > 0 && (!a->rays_o || !a->rays_d)) return fail("nsr: null ray pointers");
     }
     P.s_magic = P.S > 1 ? (unsigned)(((1ull << 32) + (unsigned)P.S - 1) / (unsigned)P.S) : 0u;     // (S = 1: nsr_kernels.h::ray_of_point)
-    P.rays_per_block = rays_per_block(P.S);
-    if (!bwd && kFwdSmallBlocks) {         // (launch policy above)
-        long long want = (P.n_rays + kDefaultBwdBlocks - 1) / kDefaultBwdBlocks;
-        if (want < 1) want = 1;
-        if (want < P.rays_per_block) P.rays_per_block = (int)want;
-    }
+    // blocks of render_fwd_kernel (its plan, passed on by every entry): up to 12 tiles (768 threads, 3 waves/SIMD, <=168 VGPRs), for
+    // small batches fewer (launch policy above)
+    const long long want = !bwd && kFwdSmallBlocks ? (P.n_rays + kDefaultBwdBlocks - 1) / kDefaultBwdBlocks : kMaxTiles * nsr::kTile;
+    P.rays_per_block = (int)std::max(1ll, std::min<long long>(want, (kMaxTiles * nsr::kTile) / P.S));
     P.tiles_per_block = (P.rays_per_block * P.S + nsr::kTile - 1) / nsr::kTile;
     P.n_groups = (P.n_rays + P.rays_per_block - 1) / P.rays_per_block;
     P.rays_o = a->rays_o;
     P.rays_d = a->rays_d;
     P.acts = a->acts;
     P.acts_masks_only = a->acts_masks_only & 15;
-    if (!bwd && a->acts && a->zvals && a->raw) {
-        // activation buffer of the three-launch forward (nsr_fwd2.h): it leaves the sample positions (and, with the fused loss,
-        // d raw) for the split backward and keeps its per-sample scratch there
-        const SplitLayout L = split_layout(P.stage, P.n_rays, P.S);
-        P.draw = a->acts + L.o_draw;
-        P.pf = a->acts + L.o_pf;
-        P.pd = reinterpret_cast<double *>(a->acts + L.o_pd);
-    }
+    // activation buffer of the three-launch forward (nsr_fwd2.h): it leaves the sample positions (and, with the fused loss,
+    // d raw) for the split backward and keeps its per-sample scratch there
+    bind_acts(P, bwd || (a->zvals && a->raw) ? a->acts : nullptr, bwd);
     P.n_points_total = (long long)P.n_rays * P.S;
-    P.act_tiles = split_layout(P.stage, P.n_rays, P.S).npad / nsr::kTile;
     P.gt_depth = guided ? a->gt_depth : nullptr;
     P.gt_max = a->gt_max;
     for (int i = 0; i < 3; ++i) { P.blo[i] = a->bound_lo[i]; P.bhi[i] = a->bound_hi[i]; }
     std::memcpy(P.t_uniform, a->t_uniform, sizeof(P.t_uniform));
     std::memcpy(P.t_surface, a->t_surface, sizeof(P.t_surface));
-    const int first = a->stage == NSR_STAGE_COARSE ? NSR_COARSE : NSR_MIDDLE;
-    const int last = a->stage == NSR_STAGE_COARSE ? NSR_COARSE : a->stage;
-    for (int s = first; s <= last; ++s) {
+    const StageSlots st(a->stage);
+    for (int s = st.first; s <= st.last; ++s) {
         const nsr_grid &g = a->grid[s];
         if (!g.feat) return fail("nsr: missing feature grid for this stage");
         if (g.Z < 1 || g.Y < 1 || g.X < 1) return fail("nsr: bad grid shape");
@@ -234,183 +295,130 @@ int build_params(const nsr_render_args *a, nsr::RenderParams &P, bool need_rays,
     return 0;
 }
 
-int finish(const char *what) {
-    if (const char *e = nsr::rt_check_last()) return fail(std::string(what) + ": " + e);
-    return 0;
-}
-
-// raise the dynamic-LDS limit of a kernel once per (kernel, device, size): not a stream operation, but kept out of the
-// steady state so that a captured hipGraph contains kernel launches only.  Keyed by the kernel's ADDRESS (all render
-// kernels share one function-pointer type) and the current device.
-template <typename K>
-int launch_cfg(K kernel, int lds_bytes, const char *what) {
-    if (lds_bytes > kLdsLimit) return fail(std::string(what) + ": LDS budget exceeded");
-    if (lds_bytes <= 48 * 1024) return 0;
-    static std::mutex mu;
-    static std::map<std::pair<const void *, int>, int> granted;
-    const std::pair<const void *, int> key(reinterpret_cast<const void *>(kernel), nsr::rt_current_device());
-    std::lock_guard<std::mutex> lock(mu);
-    int &g = granted[key];
-    if (lds_bytes > g) {
-        if (const char *e = nsr::rt_allow_lds(kernel, lds_bytes)) return fail(std::string(what) + ": " + e);
-        g = lds_bytes;
+// the block ranges of the dX and dW launches, dealt over the decoder passes by a tile's cost (launch policy above)
+int deal_bwd(const nsr::RenderParams &P, const SplitGeo &G, int dx_beg[4], int dw_beg[4]) {
+    const StageSlots st(P.stage);
+    const bool rays = P.d_rays_o != nullptr;
+    int dx_wgt[3] = {0, 0, 0}, dw_wgt[3] = {0, 0, 0};
+    for (int p = 0; p < st.passes; ++p) {
+        const int s = st.slot(p);
+        dx_wgt[p] = (P.dec[s].dparams || rays || P.stage == NSR_STAGE_COARSE) ? kDxFullWeight : kDxLightWeight;
+        dw_wgt[p] = P.dec[s].dparams ? (s == NSR_FINE ? dw_fine_weight(P.stage) : kDwWeight) : 0;
     }
+    // dX: passes * nb blocks; dW: passes * nimg blocks (= partial images) over the decoders that want parameter gradients
+    deal_blocks(dx_beg, st.passes * G.nb, dx_wgt, st.passes, P.act_tiles, true);
+    deal_blocks(dw_beg, st.passes * G.nimg, dw_wgt, st.passes, P.act_tiles, false);
+    // The workspace holds passes * nb d _B partials and passes * nimg partial images.  With the present weights this never fires
+    // (tests/test_render_launch_plan.py holds every recorded backward to it): floored shares sum to at most total, one is raised to
+    // 1 only where its floor is 0, total >= passes, and the dX shares before the last stay below total (each <= 10 / 16 of it with
+    // two passes, 10 / 22 with three).
+    if (dx_beg[3] > st.passes * G.nb || dw_beg[3] > st.passes * G.nimg)
+        return fail("nsr_render_bwd: the block deal exceeds the workspace (launch-policy weights)");
     return 0;
 }
 
-int fwd_lds_bytes(int stage, int npts) {
-    const int wl = stage == NSR_STAGE_COARSE ? nsr::packed_total(0) : (stage == NSR_STAGE_MIDDLE ? nsr::packed_total(1) : nsr::packed_total(2));
-    return round16(3 * nsr::AUX_FLOATS * 4) + npts * (8 + 8 + 16) + wl * 4;
-}
-
-// the backward as comp_bwd -> dX -> dW -> finalize over the activations the forward saved (nsr_bwd2.h)
-int render_bwd_split(const nsr_render_args *a, const nsr_bwd_args *b, nsr::RenderParams &P, bool any_params, void *stream) {
-    const SplitLayout L = split_layout(P.stage, P.n_rays, P.S);
-    if (L.stride * 4 >= (1ll << 31)) return fail("nsr_render_bwd: more than 2^25 sample points in one call (split the ray batch)");
-    const SplitGeo G = split_geo(P.stage, P.n_rays, P.S, b->max_blocks);
-    const int passes = bwd_passes(P.stage);
-    P.dy = P.acts + L.o_dy;
-    P.draw = P.acts + L.o_draw;
-    P.pf = P.acts + L.o_pf;
-    P.pd = reinterpret_cast<double *>(P.acts + L.o_pd);
-    for (int s = 0; s < 4; ++s)
-        if (P.dec[s].dparams && (P.acts_masks_only & (1 | (2 << (s == NSR_COARSE ? 0 : s - NSR_MIDDLE)))))
+// checks, and the workspace
+int bind_bwd(const nsr_bwd_args *b, nsr::RenderParams &P, const SplitGeo &G, bool any_params) {
+    if (P.act_tiles * nsr::kTile * 16 * 4 >= (1ll << 31)) return fail("nsr_render_bwd: more than 2^25 sample points in one call (split the ray batch)");
+    const StageSlots st(P.stage);
+    for (int s = st.first; s <= st.last; ++s)
+        if (P.dec[s].dparams && (P.acts_masks_only & (1 | (2 << st.pass_of(s)))))
             return fail("nsr_render_bwd: the forward saved relu masks only for a decoder whose parameter gradients are asked for (acts_masks_only); they need the full activations");
     // (the fine decoder's input is [c_fine | c_mid], decoder.py:182-187: its dW reads the middle pass's saved features)
     if (P.dec[NSR_FINE].dparams && (P.acts_masks_only & (1 | 2)))
         return fail("nsr_render_bwd: the forward saved relu masks only for the middle decoder (acts_masks_only), whose features the fine decoder's parameter gradients read");
     if (any_params) {
-        const long long need = (long long)passes * ((long long)G.nimg * P.partial_stride + (long long)G.nb * nsr::kDbPart);
-        if (!b->workspace || b->workspace_floats < need) return fail("nsr_render_bwd: workspace too small");
+        const BwdWorkspace W = bwd_workspace(P.stage, G);
+        if (!b->workspace || b->workspace_floats < W.floats) return fail("nsr_render_bwd: workspace too small");
         P.partials = b->workspace;
-        P.dbpart = b->workspace + (long long)passes * G.nimg * P.partial_stride;
+        P.dbpart = b->workspace + W.dbpart;
     }
-    if (b->ev_start) nsr::rt_record(b->ev_start, stream);
-    // the forward's loss epilogue already wrote d raw (for an incoming gradient of 1): used when the caller SAYS that it hands
-    // back exactly the derivative arrays that forward produced, unmodified (nsr_bwd_args.loss_grads_from_forward); else the
-    // compositor backward runs here on d_depth / d_var / d_rgb as given
+    return 0;
+}
+
+// the forward's loss epilogue already wrote d raw (for an incoming gradient of 1): used when the caller SAYS that it hands
+// back exactly the derivative arrays that forward produced, unmodified (nsr_bwd_args.loss_grads_from_forward); else the
+// compositor backward runs here on d_depth / d_var / d_rgb as given
+void launch_comp_bwd(const nsr_render_args *a, const nsr_bwd_args *b, nsr::RenderParams &P, void *stream) {
     const bool draw_ready = b->loss_grads_from_forward && a->loss && a->dl_depth && b->d_depth == a->dl_depth && !b->d_var &&
                             (b->d_rgb == nullptr || b->d_rgb == a->dl_rgb) && (P.stage != NSR_STAGE_COLOR || b->d_rgb == a->dl_rgb || !a->gt_color);
     P.draw_scaled = draw_ready ? 0 : 1;
-    if (!draw_ready) {
-        const int tb = 256, rays_per_block = tb / 64;
-        NSR_LAUNCH(nsr::comp_bwd_kernel, dim3((unsigned)((P.n_rays + rays_per_block - 1) / rays_per_block)), dim3(tb), 0, stream, P);
+    if (draw_ready) return;
+    const int tb = 256, rays_per_block = tb / 64;
+    NSR_LAUNCH(nsr::comp_bwd_kernel, dim3(nblk(P.n_rays, rays_per_block)), dim3(tb), 0, stream, P);
+}
+
+int launch_dx(nsr::RenderParams &P, const SplitGeo &G, const int dx_beg[4], void *stream) {
+    int lds = dx_lds_bytes(P.stage, G.waves);
+    // hot-voxel table of a dX block (launch policy above)
+    P.hot_slots = 0;
+    if (P.stage != NSR_STAGE_COARSE) {
+        int slots = (kLdsLimit - lds) / (nsr::kHotRow * 4);
+        slots = slots > kHotSlotCap ? kHotSlotCap : slots;
+        P.hot_slots = slots < 16 ? 16 : slots;
+        lds += P.hot_slots * nsr::kHotRow * 4;
     }
-    const bool rays = P.d_rays_o != nullptr;
-    {
-        int lds = 0;
-        const int first = P.stage == NSR_STAGE_COARSE ? NSR_COARSE : NSR_MIDDLE, last = P.stage == NSR_STAGE_COARSE ? NSR_COARSE : P.stage;
-        for (int kind = first; kind <= last; ++kind) {
-            const int need = (nsr::AUX_FLOATS + nsr::packedT_total(kind) + G.waves * nsr::kDxStg + 4) * 4;   // + the tile counter
-            lds = need > lds ? need : lds;
-        }
-        // hot-voxel table of a dX block (launch policy above)
-        P.hot_slots = 0;
-        if (P.stage != NSR_STAGE_COARSE) {
-            int slots = (kLdsLimit - lds) / (nsr::kHotRow * 4);
-            slots = slots > kHotSlotCap ? kHotSlotCap : slots;
-            P.hot_slots = slots < 16 ? 16 : slots;
-            lds += P.hot_slots * nsr::kHotRow * 4;
-        }
-        for (int s = 0; s < 4; ++s) {
-            P.hot_z[s] = 0.f;
-            if (s == NSR_COARSE || kHotCells <= 0 || !P.grid[s].dfeat) continue;
-            double cell = 0.0;
-            const int nn[3] = {P.grid[s].X, P.grid[s].Y, P.grid[s].Z};
-            for (int ax = 0; ax < 3; ++ax) { const double c = nn[ax] > 1 ? P.grid[s].ext[ax] / (nn[ax] - 1) : 0.0; cell = c > cell ? c : cell; }
-            P.hot_z[s] = (float)(kHotCells * cell);
-        }
-        P.lds_grid_floats = 0;
-        if (P.stage == NSR_STAGE_COARSE && P.grid[NSR_COARSE].dfeat) {       // a coarse gradient grid that fits next to the rest
-            const long long gf = (long long)P.grid[NSR_COARSE].X * P.grid[NSR_COARSE].Y * P.grid[NSR_COARSE].Z * nsr::kC;
-            if (lds + gf * 4 <= kLdsLimit) { P.lds_grid_floats = (int)gf; lds += (int)gf * 4; }
-        }
-        // the passes * nb blocks dealt over the decoder passes by a tile's cost (launch policy above)
-        {
-            const long long tiles = (P.n_points_total + nsr::kTile - 1) / nsr::kTile;
-            int wgt[3] = {0, 0, 0}, wsum = 0;
-            for (int p = 0; p < passes; ++p) {
-                const int s = P.stage == NSR_STAGE_COARSE ? NSR_COARSE : NSR_MIDDLE + p;
-                wgt[p] = (P.dec[s].dparams || rays || P.stage == NSR_STAGE_COARSE) ? kDxFullWeight : kDxLightWeight;
-                wsum += wgt[p];
-            }
-            // (the blocks sum to at most total = the workspace's d _B partials: a floored share is raised to 1 only where
-            //  total * w / wsum < 1, and with w / wsum <= 10 / 22 for three passes the first two shares never reach total)
-            const int total = passes * G.nb;
-            int used = 0;
-            P.dx_beg[0] = 0;
-            for (int p = 0; p < 3; ++p) {
-                long long n = 0;
-                if (p < passes) {
-                    n = p == passes - 1 ? total - used : (long long)total * wgt[p] / wsum;
-                    if (n < 1) n = 1;
-                    if (n > tiles) n = tiles;
-                }
-                used += (int)n;
-                P.dx_beg[p + 1] = P.dx_beg[p] + (int)n;
-            }
-        }
-        const dim3 grid(P.dx_beg[3]), block(64 * G.waves);
-#define NSR_DX(ST, RY)                                                                                  \
-    if (int rc = launch_cfg(nsr::render_bwd_dx_kernel<ST, RY>, lds, "nsr_render_bwd(dx)")) return rc;   \
-    NSR_LAUNCH((nsr::render_bwd_dx_kernel<ST, RY>), grid, block, lds, stream, P);
-        switch (P.stage) {
-            case 0: if (rays) { NSR_DX(0, true) } else { NSR_DX(0, false) } break;
-            case 1: if (rays) { NSR_DX(1, true) } else { NSR_DX(1, false) } break;
-            case 2: if (rays) { NSR_DX(2, true) } else { NSR_DX(2, false) } break;
-            default: if (rays) { NSR_DX(3, true) } else { NSR_DX(3, false) } break;
-        }
-#undef NSR_DX
+    for (int s = 0; s < 4; ++s) {
+        P.hot_z[s] = 0.f;
+        if (s == NSR_COARSE || kHotCells <= 0 || !P.grid[s].dfeat) continue;
+        double cell = 0.0;
+        const int nn[3] = {P.grid[s].X, P.grid[s].Y, P.grid[s].Z};
+        for (int ax = 0; ax < 3; ++ax) { const double c = nn[ax] > 1 ? P.grid[s].ext[ax] / (nn[ax] - 1) : 0.0; cell = c > cell ? c : cell; }
+        P.hot_z[s] = (float)(kHotCells * cell);
     }
+    P.lds_grid_floats = 0;
+    if (P.stage == NSR_STAGE_COARSE && P.grid[NSR_COARSE].dfeat) {       // a coarse gradient grid that fits next to the rest
+        const long long gf = (long long)P.grid[NSR_COARSE].X * P.grid[NSR_COARSE].Y * P.grid[NSR_COARSE].Z * nsr::kC;
+        if (lds + gf * 4 <= kLdsLimit) { P.lds_grid_floats = (int)gf; lds += (int)gf * 4; }
+    }
+    std::memcpy(P.dx_beg, dx_beg, sizeof(P.dx_beg));
+    return with_stage(P.stage, [&](auto ST) {
+        const auto kernel = P.d_rays_o ? nsr::render_bwd_dx_kernel<ST(), true> : nsr::render_bwd_dx_kernel<ST(), false>;
+        return launch_kernel(kernel, dim3(P.dx_beg[3]), dim3(64 * G.waves), lds, "nsr_render_bwd(dx)", stream, P);
+    });
+}
+
+int launch_dw(nsr::RenderParams &P, const int dw_beg[4], void *stream) {
+    std::memcpy(P.dw_beg, dw_beg, sizeof(P.dw_beg));
+    return with_stage(P.stage, [&](auto ST) {
+        return launch_kernel(nsr::render_bwd_dw_kernel<ST()>, dim3(P.dw_beg[3]), dim3(64 * nsr::kDwWaves), dw_lds_bytes(P.stage), "nsr_render_bwd(dw)", stream, P);
+    });
+}
+
+// dparams (+)= the partial images of its dW blocks and the d _B partials of its dX blocks: one job per decoder with gradients
+void launch_finalize(const nsr_bwd_args *b, const nsr::RenderParams &P, void *stream) {
+    const StageSlots st(P.stage);
+    nsr::FinalParams R;
+    R.stride = P.partial_stride; R.overwrite = b->overwrite_dparams ? 1 : 0;
+    int rows = 0;
+    for (int s = st.first; s <= st.last; ++s) {
+        if (!P.dec[s].dparams) continue;
+        const int pass = st.pass_of(s);
+        nsr::FinalJob &J = R.job[rows++];
+        J.images = P.partials + (long long)P.dw_beg[pass] * P.partial_stride;
+        J.dbpart = P.dbpart + (long long)P.dx_beg[pass] * nsr::kDbPart;
+        J.dparams = P.dec[s].dparams;
+        J.kind = s; J.nimg = P.dw_beg[pass + 1] - P.dw_beg[pass]; J.ndx = P.dx_beg[pass + 1] - P.dx_beg[pass];
+    }
+    for (int r = rows; r < 3; ++r) R.job[r] = nsr::FinalJob{nullptr, nullptr, nullptr, 0, 0, 0};
+    const int nblocks = st.most([&](int s) { return P.dec[s].dparams ? (nsr::param_total(s) + 63) / 64 : 0; });
+    NSR_LAUNCH(nsr::bwd_finalize_kernel, dim3(nblocks, rows), dim3(kFinThreads), kFinThreads * 4, stream, R);
+}
+
+// the backward as comp_bwd -> dX -> dW -> finalize over the activations the forward saved (nsr_bwd2.h)
+int render_bwd_split(const nsr_render_args *a, const nsr_bwd_args *b, nsr::RenderParams &P, bool any_params, void *stream) {
+    const SplitGeo G = split_geo(P.stage, P.n_rays, P.S, b->max_blocks);
+    int dx_beg[4], dw_beg[4];
+    if (int rc = bind_bwd(b, P, G, any_params)) return rc;
+    if (int rc = deal_bwd(P, G, dx_beg, dw_beg)) return rc;
+    if (b->ev_start) nsr::rt_record(b->ev_start, stream);
+    launch_comp_bwd(a, b, P, stream);
+    if (int rc = launch_dx(P, G, dx_beg, stream)) return rc;
     if (b->ev_dx_done) nsr::rt_record(b->ev_dx_done, stream);
     if (any_params) {
-        const int lds = nsr::dw_lds_bytes(P.stage >= NSR_STAGE_FINE ? NSR_FINE : NSR_MIDDLE);
-        // the passes * nimg blocks (= partial images, the workspace's size) dealt over the decoders that want parameter gradients,
-        // in proportion to a tile's measured cost (launch policy above)
-        const long long tiles = (P.n_points_total + nsr::kTile - 1) / nsr::kTile;
-        int wgt[3] = {0, 0, 0}, wsum = 0;
-        for (int p = 0; p < passes; ++p) {
-            const int s = P.stage == NSR_STAGE_COARSE ? NSR_COARSE : NSR_MIDDLE + p;
-            wgt[p] = P.dec[s].dparams ? (s == NSR_FINE ? dw_fine_weight(P.stage) : kDwWeight) : 0;
-            wsum += wgt[p];
-        }
-        const int total = passes * G.nimg;
-        P.dw_beg[0] = 0;
-        for (int p = 0; p < 3; ++p) {
-            long long n = (p < passes && wgt[p]) ? (long long)total * wgt[p] / wsum : 0;
-            if (p < passes && wgt[p] && n < 1) n = 1;
-            if (n > tiles) n = tiles;
-            P.dw_beg[p + 1] = P.dw_beg[p] + (int)n;
-        }
-        const dim3 grid(P.dw_beg[3]), block(64 * nsr::kDwWaves);
-#define NSR_DW(ST)                                                                                  \
-    if (int rc = launch_cfg(nsr::render_bwd_dw_kernel<ST>, lds, "nsr_render_bwd(dw)")) return rc;   \
-    NSR_LAUNCH((nsr::render_bwd_dw_kernel<ST>), grid, block, lds, stream, P);
-        switch (P.stage) {
-            case 0: NSR_DW(0) break;
-            case 1: NSR_DW(1) break;
-            case 2: NSR_DW(2) break;
-            default: NSR_DW(3) break;
-        }
-#undef NSR_DW
+        if (int rc = launch_dw(P, dw_beg, stream)) return rc;
         if (b->ev_dw_done) nsr::rt_record(b->ev_dw_done, stream);
-        const int first = P.stage == NSR_STAGE_COARSE ? NSR_COARSE : NSR_MIDDLE, last = P.stage == NSR_STAGE_COARSE ? NSR_COARSE : P.stage;
-        nsr::FinalParams R;
-        R.stride = P.partial_stride; R.overwrite = b->overwrite_dparams ? 1 : 0;
-        int rows = 0, nblocks = 0;
-        for (int s = first; s <= last; ++s) {
-            if (!P.dec[s].dparams) continue;
-            const int pass = P.stage == NSR_STAGE_COARSE ? 0 : s - NSR_MIDDLE;
-            nsr::FinalJob &J = R.job[rows++];
-            J.images = P.partials + (long long)P.dw_beg[pass] * P.partial_stride;
-            J.dbpart = P.dbpart + (long long)P.dx_beg[pass] * nsr::kDbPart;
-            J.dparams = P.dec[s].dparams;
-            J.kind = s; J.nimg = P.dw_beg[pass + 1] - P.dw_beg[pass]; J.ndx = P.dx_beg[pass + 1] - P.dx_beg[pass];
-            const int nb = (nsr::param_total(s) + 63) / 64;
-            nblocks = nb > nblocks ? nb : nblocks;
-        }
-        for (int r = rows; r < 3; ++r) R.job[r] = nsr::FinalJob{nullptr, nullptr, nullptr, 0, 0, 0};
-        NSR_LAUNCH(nsr::bwd_finalize_kernel, dim3(nblocks, rows), dim3(kFinThreads), kFinThreads * 4, stream, R);
+        launch_finalize(b, P, stream);
     }
     if (b->ev_stop) nsr::rt_record(b->ev_stop, stream);
     return finish("nsr_render_bwd(split)");
@@ -428,28 +436,48 @@ int64_t nsr_packed_count(int slot) { return (slot < 0 || slot > 3) ? -1 : nsr::p
 
 int64_t nsr_acts_floats(int stage, int64_t n_rays, int n_samples_total) {
     if (stage < 0 || stage > 3 || n_rays < 0 || n_samples_total < 1 || n_samples_total > NSR_MAX_SAMPLES) return -1;
-    return split_layout(stage, n_rays, n_samples_total).total;
+    nsr::RenderParams P;
+    P.stage = stage; P.n_rays = n_rays; P.S = n_samples_total;
+    return carve(describe_acts, P) / 4;
 }
 
 int64_t nsr_bwd_workspace_floats(int stage, int64_t n_rays, int n_samples_total, int max_blocks) {
     if (stage < 0 || stage > 3 || n_samples_total < 1 || n_samples_total > NSR_MAX_SAMPLES) return -1;
-    // partial images of the dW kernel + d _B partials of the dX kernel
-    const SplitGeo G = split_geo(stage, n_rays, n_samples_total, max_blocks);
-    const long long split = (long long)bwd_passes(stage) * ((long long)G.nimg * max_param_count(stage) + (long long)G.nb * nsr::kDbPart);
-    return (int64_t)split;
+    return bwd_workspace(stage, split_geo(stage, n_rays, n_samples_total, max_blocks)).floats;
 }
 
 int nsr_pack_params(int slot, const float *params, float *packed, void *stream) {
     if (slot < 0 || slot > 3) return fail("nsr_pack_params: slot out of range");
     if (!params || !packed) return fail("nsr_pack_params: null pointer");
-    const int n = nsr::packed_buf_total(slot), tb = 256, nb = (n + tb - 1) / tb;
-    switch (slot) {
-        case 0: NSR_LAUNCH(nsr::pack_kernel<0>, dim3(nb), dim3(tb), 0, stream, params, packed); break;
-        case 1: NSR_LAUNCH(nsr::pack_kernel<1>, dim3(nb), dim3(tb), 0, stream, params, packed); break;
-        case 2: NSR_LAUNCH(nsr::pack_kernel<2>, dim3(nb), dim3(tb), 0, stream, params, packed); break;
-        default: NSR_LAUNCH(nsr::pack_kernel<3>, dim3(nb), dim3(tb), 0, stream, params, packed); break;
-    }
+    const int tb = 256;
+    with_stage(slot, [&](auto SLOT) {
+        NSR_LAUNCH(nsr::pack_kernel<SLOT()>, dim3(nblk(nsr::packed_buf_total(slot), tb)), dim3(tb), 0, stream, params, packed);
+        return 0;
+    });
     return finish("nsr_pack_params");
+}
+
+// sample placement -> decoder passes -> compositor (nsr_fwd2.h), saving into the activation buffer
+static int render_fwd_split(const nsr_render_args *a, nsr::RenderParams &P, void *stream) {
+    // one block per CU over all passes, dealt in proportion to the measured cost of a tile; waves per block from the largest tile
+    // share, at most nsr::kDxMaxWaves (launch policy above)
+    const StageSlots st(P.stage);
+    const int wgt[3] = {kFwdWeight, fwd_fine_weight(P.stage), kFwdWeight};
+    deal_blocks(P.pass_beg, kDefaultBwdBlocks, wgt, st.passes, P.act_tiles, false);
+    long long most = 1;           // tiles of a block
+    for (int p = 0; p < st.passes; ++p) most = std::max(most, (P.act_tiles + P.pass_beg[p + 1] - P.pass_beg[p] - 1) / (P.pass_beg[p + 1] - P.pass_beg[p]));
+    const int waves = (int)std::min<long long>(most, nsr::kDxMaxWaves), rpb = 4;
+    const dim3 rgrid(nblk(P.n_rays, rpb)), rblock(64 * rpb);
+    NSR_LAUNCH(nsr::fwd_sample_kernel, rgrid, rblock, rpb * 64 * 8, stream, P);
+    const int rc = with_stage(P.stage, [&](auto ST) {
+        if (a->ev_pass_start) nsr::rt_record(a->ev_pass_start, stream);
+        if (int rc = launch_kernel(nsr::render_fwd_pass_kernel<ST(), true>, dim3(P.pass_beg[3]), dim3(64 * waves), pass_lds_bytes(P.stage), "nsr_render_fwd(pass)", stream, P))
+            return rc;
+        if (a->ev_pass_stop) nsr::rt_record(a->ev_pass_stop, stream);
+        NSR_LAUNCH(nsr::fwd_composite_kernel<ST()>, rgrid, rblock, rpb * 8, stream, P);
+        return 0;
+    });
+    return rc ? rc : finish("nsr_render_fwd(split)");
 }
 
 int nsr_render_fwd(const nsr_render_args *a, void *stream) {
@@ -462,67 +490,17 @@ int nsr_render_fwd(const nsr_render_args *a, void *stream) {
     if (P.n_rays == 0) return 0;
     if (a->acts && a->zvals && a->raw) {
         // a call that hands over an activation buffer (with zvals and raw: without them nsr_render_bwd refuses) will be differentiated:
-        // only the three-launch path below saves into it, and the tile / keep arithmetic of the kernels that read it is 32-bit
-        // (tile_live, dw_live_mask, split_layout)
+        // only the three-launch path saves into it, and the tile / keep arithmetic of the kernels that read it is 32-bit
+        // (tile_live, dw_live_mask, describe_acts)
         if (P.n_points_total > (1ll << 25) - 16) return fail("nsr_render_fwd: more than 2^25 sample points in one differentiated call (split the ray batch)");
-        // sample placement -> decoder passes -> compositor (nsr_fwd2.h); the block deal: launch policy above
-        const int passes = bwd_passes(P.stage), rpb = 4;
-        const int w_fine = fwd_fine_weight(P.stage);
-        const long long tiles = (P.n_points_total + nsr::kTile - 1) / nsr::kTile;
-        const int wsum = passes == 1 ? kFwdWeight : (passes == 2 ? kFwdWeight + w_fine : 2 * kFwdWeight + w_fine);
-        long long most = 1;
-        P.pass_beg[0] = 0;
-        for (int p = 0; p < 3; ++p) {
-            int nbp = 0;
-            if (p < passes) {
-                nbp = (int)((long long)kDefaultBwdBlocks * (p == 1 ? w_fine : kFwdWeight) / wsum);
-                if (nbp > tiles) nbp = (int)tiles;
-                if (nbp < 1) nbp = 1;
-                const long long share = (tiles + nbp - 1) / nbp;
-                most = share > most ? share : most;
-            }
-            P.pass_beg[p + 1] = P.pass_beg[p] + nbp;
-        }
-        const int waves = (int)(most > nsr::kDxMaxWaves ? nsr::kDxMaxWaves : most);
-        const dim3 rgrid((unsigned)((P.n_rays + rpb - 1) / rpb)), rblock(64 * rpb);
-        NSR_LAUNCH(nsr::fwd_sample_kernel, rgrid, rblock, rpb * 64 * 8, stream, P);
-        int lds = 0;
-        const int first = P.stage == NSR_STAGE_COARSE ? NSR_COARSE : NSR_MIDDLE, last = P.stage == NSR_STAGE_COARSE ? NSR_COARSE : P.stage;
-        for (int kind = first; kind <= last; ++kind) {
-            const int need = (nsr::AUX_FLOATS + nsr::packed_total(kind) + 4) * 4;
-            lds = need > lds ? need : lds;
-        }
-        const dim3 grid(P.pass_beg[3]), block(64 * waves);
-#define NSR_FWP(ST, SV)                                                                                      \
-    if (int rc = launch_cfg(nsr::render_fwd_pass_kernel<ST, SV>, lds, "nsr_render_fwd(pass)")) return rc;    \
-    if (a->ev_pass_start) nsr::rt_record(a->ev_pass_start, stream);                                          \
-    NSR_LAUNCH((nsr::render_fwd_pass_kernel<ST, SV>), grid, block, lds, stream, P);                          \
-    if (a->ev_pass_stop) nsr::rt_record(a->ev_pass_stop, stream);
-        switch (P.stage) {
-            case 0: NSR_FWP(0, true) NSR_LAUNCH(nsr::fwd_composite_kernel<0>, rgrid, rblock, rpb * 8, stream, P); break;
-            case 1: NSR_FWP(1, true) NSR_LAUNCH(nsr::fwd_composite_kernel<1>, rgrid, rblock, rpb * 8, stream, P); break;
-            case 2: NSR_FWP(2, true) NSR_LAUNCH(nsr::fwd_composite_kernel<2>, rgrid, rblock, rpb * 8, stream, P); break;
-            default: NSR_FWP(3, true) NSR_LAUNCH(nsr::fwd_composite_kernel<3>, rgrid, rblock, rpb * 8, stream, P); break;
-        }
-#undef NSR_FWP
-        return finish("nsr_render_fwd(split)");
+        return render_fwd_split(a, P, stream);
     }
-    const int npts = P.rays_per_block * P.S;
-    const int lds = fwd_lds_bytes(P.stage, npts);
-    const dim3 grid((unsigned)(P.n_groups < (1 << 20) ? P.n_groups : (1 << 20))), block(64 * P.tiles_per_block);
-#define NSR_FWD(ST)                                                                               \
-    if (int rc = launch_cfg(nsr::render_fwd_kernel<ST>, lds, "nsr_render_fwd")) return rc;         \
-    NSR_LAUNCH((nsr::render_fwd_kernel<ST>), grid, block, lds, stream, P);
     // (the one-launch kernel saves nothing: a call that will be differentiated passes acts + zvals + raw and took the branch above)
     P.acts = nullptr;
-    switch (P.stage) {
-        case 0: NSR_FWD(0) break;
-        case 1: NSR_FWD(1) break;
-        case 2: NSR_FWD(2) break;
-        default: NSR_FWD(3) break;
-    }
-#undef NSR_FWD
-    return finish("nsr_render_fwd");
+    const int lds = fwd_lds_bytes(P.stage, P.rays_per_block * P.S * (8 + 8 + 16));
+    const dim3 grid((unsigned)(P.n_groups < (1 << 20) ? P.n_groups : (1 << 20))), block(64 * P.tiles_per_block);
+    const int rc = with_stage(P.stage, [&](auto ST) { return launch_kernel(nsr::render_fwd_kernel<ST()>, grid, block, lds, "nsr_render_fwd", stream, P); });
+    return rc ? rc : finish("nsr_render_fwd");
 }
 
 int nsr_render_bwd(const nsr_render_args *a, const nsr_bwd_args *b, void *stream) {
@@ -539,10 +517,9 @@ int nsr_render_bwd(const nsr_render_args *a, const nsr_bwd_args *b, void *stream
 #ifdef NSR_TS
     if (const char *e = getenv("NSR_DBG_PTR")) P.dbg = reinterpret_cast<long long *>(strtoull(e, nullptr, 16));
 #endif
-    const int passes = bwd_passes(P.stage);
     bool any_params = false;
     for (int s = 0; s < 4; ++s) any_params |= P.dec[s].dparams != nullptr;
-    P.partial_stride = max_param_count(P.stage);
+    P.partial_stride = partial_stride(P.stage);
     if (!P.acts || !a->zvals)
         return fail("nsr_render_bwd: the forward must have been given an activation buffer (nsr_render_args.acts, sized by nsr_acts_floats) and zvals");
     return render_bwd_split(a, b, P, any_params, stream);
@@ -555,20 +532,12 @@ int nsr_eval_points_fwd(const nsr_render_args *a, const double *points, int64_t 
     if (n_points == 0) return 0;
     P.points = points; P.n_points = n_points; P.out_points = out;
     const int waves = kMaxTiles;
-    const int wlf = P.stage == NSR_STAGE_COARSE ? nsr::packed_total(0) : (P.stage == NSR_STAGE_MIDDLE ? nsr::packed_total(1) : nsr::packed_total(2));
-    const int lds = round16(3 * nsr::AUX_FLOATS * 4) + 16 + wlf * 4;
-    const long long tiles = (n_points + nsr::kTile - 1) / nsr::kTile;
-    long long nb = (tiles + waves - 1) / waves;
+    long long nb = (tiles_of(n_points) + waves - 1) / waves;
     if (nb > 2048) nb = 2048;
-    const dim3 grid((unsigned)nb), block(64 * waves);
-#define NSR_EVP(ST)                                                                              \
-    case ST:                                                                                     \
-        if (int rc = launch_cfg(nsr::eval_points_kernel<ST>, lds, "nsr_eval_points_fwd")) return rc; \
-        NSR_LAUNCH(nsr::eval_points_kernel<ST>, grid, block, lds, stream, P);                     \
-        break;
-    switch (P.stage) { NSR_EVP(0) NSR_EVP(1) NSR_EVP(2) NSR_EVP(3) }
-#undef NSR_EVP
-    return finish("nsr_eval_points_fwd");
+    const int rc = with_stage(P.stage, [&](auto ST) {
+        return launch_kernel(nsr::eval_points_kernel<ST()>, dim3((unsigned)nb), dim3(64 * waves), fwd_lds_bytes(P.stage, 16), "nsr_eval_points_fwd", stream, P);
+    });
+    return rc ? rc : finish("nsr_eval_points_fwd");
 }
 
 int nsr_masked_adam(float *p, const float *g, float *m, float *v, const uint8_t *voxel_mask, int64_t n_voxels,

@@ -1,8 +1,11 @@
 // tests/emu/emu_runtime.cpp -- TEST INFRASTRUCTURE: fiber scheduler that runs a HIP-style launch on
 // the CPU.  One OS thread per block (up to NSR_EMU_THREADS at a time), one fiber per GPU thread.
+#include <cxxabi.h>
+#include <dlfcn.h>
 #include <sys/mman.h>
 
 #include <atomic>
+#include <mutex>
 #include <thread>
 #include <vector>
 
@@ -135,5 +138,33 @@ void launch(dim3 grid, dim3 block, int lds_bytes, const std::function<void()> &b
     for (auto &t : pool) t.join();
 }
 
+// ---- launch log (nsr_dev.h) ----------------------------------------------------------------------------------------------------
+int g_log_mode = 0;
+static std::mutex g_log_mu;
+static std::string g_log, g_log_out;
+
+void log_launch(const char *text, const void *fn, dim3 grid, dim3 block, int lds_bytes, const std::string &detail) {
+    std::string name = text;
+    Dl_info info;
+    if (fn && dladdr(fn, &info) && info.dli_sname && info.dli_saddr == fn) {
+        int status = 1;
+        char *d = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &status);
+        name = status == 0 && d ? d : info.dli_sname;
+        std::free(d);
+    }
+    std::string e = "[\"" + name + "\", " + std::to_string(grid.x) + ", " + std::to_string(grid.y) + ", " + std::to_string(block.x) +
+                    ", " + std::to_string(lds_bytes) + (detail.empty() ? "" : ", " + detail) + "]";
+    std::lock_guard<std::mutex> lock(g_log_mu);
+    g_log += (g_log.empty() ? "" : ",\n ") + e;
+}
+
 }  // namespace emu
 }  // namespace nsr
+
+extern "C" const char *nsr_emu_launch_log(int mode) {
+    std::lock_guard<std::mutex> lock(nsr::emu::g_log_mu);
+    nsr::emu::g_log_mode = mode;
+    nsr::emu::g_log_out = "[" + nsr::emu::g_log + "]";
+    nsr::emu::g_log.clear();
+    return nsr::emu::g_log_out.c_str();
+}

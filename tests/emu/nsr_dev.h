@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <string>
 
 #define NSR_DEV inline
 #define NSR_KERNEL
@@ -61,6 +62,52 @@ struct Block {
 extern thread_local Block *B;
 void yield_to_scheduler();
 void launch(dim3 grid, dim3 block, int lds_bytes, const std::function<void()> &body);
+
+// ---- launch log (tests/test_render_launch_plan.py) ---------------------------------------------------------------------------
+// nsr_emu_launch_log(mode) of the emulator library: 0 off, 1 every launch is recorded, 2 recorded and NOT run (dry: the host
+// code never reads device memory, so every pointer argument may then be a dummy).  It returns what was recorded since the last
+// call as a JSON list, one entry per launch: ["kernel", grid x, grid y, block x, LDS bytes] and, where the first kernel
+// argument is a RenderParams, the plan fields the host computed (note_plan below, in that order); for a FinalParams its jobs.
+// "kernel" is the demangled symbol at the kernel's address (the same whoever spells the launch), else the expression's text.
+extern int g_log_mode;
+void log_launch(const char *text, const void *fn, dim3 grid, dim3 block, int lds_bytes, const std::string &detail);
+template <typename K> inline const void *fn_addr(K kernel) { return reinterpret_cast<const void *>(kernel); }
+template <typename T> inline long long float_off(const T *p, const float *base) {       // -1: one of the two is not bound
+    return p && base ? (long long)(reinterpret_cast<const float *>(p) - base) : -1;
+}
+inline void put(std::string &s, long long v) { s += s.empty() ? "[" : ", "; s += std::to_string(v); }
+inline const float *&last_partials() { static thread_local const float *p = nullptr; return p; }
+// (templates over the parameter block's type: RenderParams and FinalParams are defined after this header is read)
+template <typename P> inline auto note_plan(std::string &s, const P &p, int) -> decltype((void)p.pass_beg) {
+    put(s, p.rays_per_block); put(s, p.tiles_per_block); put(s, p.n_groups); put(s, p.act_tiles); put(s, p.partial_stride);
+    for (int i = 0; i < 4; ++i) put(s, p.pass_beg[i]);
+    for (int i = 0; i < 4; ++i) put(s, p.dx_beg[i]);
+    for (int i = 0; i < 4; ++i) put(s, p.dw_beg[i]);
+    put(s, p.hot_slots);
+    for (int i = 0; i < 4; ++i) { unsigned u; std::memcpy(&u, &p.hot_z[i], 4); put(s, u); }       // bit patterns
+    put(s, p.lds_grid_floats); put(s, p.draw_scaled); put(s, p.skip_masked); put(s, p.s_magic);
+    put(s, float_off(p.dy, p.acts)); put(s, float_off(p.draw, p.acts)); put(s, float_off(p.pf, p.acts)); put(s, float_off(p.pd, p.acts));
+    put(s, float_off(p.dbpart, p.partials));
+    last_partials() = p.partials;
+    s += "]";
+}
+// (the finalize jobs: offsets from the workspace base = `partials` of the RenderParams launch before it on this thread)
+template <typename P> inline auto note_plan(std::string &s, const P &r, int) -> decltype((void)r.job) {
+    for (int j = 0; j < 3; ++j) {
+        std::string one;
+        put(one, r.job[j].kind); put(one, r.job[j].nimg); put(one, r.job[j].ndx);
+        put(one, float_off(r.job[j].images, last_partials())); put(one, float_off(r.job[j].dbpart, last_partials()));
+        s += (j ? ", " : "[") + one + "]";
+    }
+    s += "]";
+}
+template <typename P> inline void note_plan(std::string &, const P &, long) {}
+inline std::string describe() { return std::string(); }
+template <typename P, typename... Rest> inline std::string describe(const P &first, const Rest &...) {
+    std::string s;
+    note_plan(s, first, 0);
+    return s;
+}
 
 inline void wave_sync() {
     Block *b = B;
@@ -229,5 +276,9 @@ using ::sqrtf;
 
 }  // namespace nsr
 
-#define NSR_LAUNCH(kernel, grid, block, lds_bytes, stream, ...) \
-    ::nsr::emu::launch(grid, block, lds_bytes, [=]() { kernel(__VA_ARGS__); })
+#define NSR_LAUNCH(kernel, grid, block, lds_bytes, stream, ...)                                                                    \
+    do {                                                                                                                          \
+        if (::nsr::emu::g_log_mode)                                                                                               \
+            ::nsr::emu::log_launch(#kernel, ::nsr::emu::fn_addr(kernel), grid, block, lds_bytes, ::nsr::emu::describe(__VA_ARGS__)); \
+        if (::nsr::emu::g_log_mode != 2) ::nsr::emu::launch(grid, block, lds_bytes, [=]() { kernel(__VA_ARGS__); });                \
+    } while (0)
