@@ -728,6 +728,34 @@ int nsr_jpegdec_size(int32_t n, int32_t H, int32_t W, int32_t sampling, int64_t 
 int nsr_jpegdec_decode(const uint8_t *files, const nsr_jpegdec_frame *descriptors, int32_t n, int32_t H, int32_t W, int32_t sampling,
                        int32_t subsequence_bytes, void *workspace, int64_t workspace_bytes, uint8_t *out, int32_t *status, void *stream);
 
+/* --- PNG decoding (8-bit and 16-bit grey, 8-bit RGB and RGBA; non-interlaced) ----------------------------------------------------
+ * The compressed bytes of n PNG files that are on the device in, their pixels out: what Pillow returns for the file, bit for bit.
+ * The caller walks the chunks and checks their CRCs (nice_slam_amd/png.py) and describes every file by one nsr_png_frame in device
+ * memory (8-byte aligned): its zlib stream -- the IDAT payloads, concatenated -- as a byte range of `streams`.  The device inflates
+ * (RFC 1950 / 1951 as zlib reads them: stored, fixed and dynamic blocks, a 32 KiB window), un-filters (None, Sub, Up, Average,
+ * Paeth) and orders the bytes; the contract is written out in nice_slam_amd/csrc/nsr_png.h.  All frames of a call share H, W in
+ * [1, 32768] and kind; n <= 65535, n = 0 succeeds and launches nothing.  out per kind and out_channels:
+ *   NSR_PNG_GREY8    1: u8 [n][H][W]; 3: u8 [n][H][W][3], the sample three times
+ *   NSR_PNG_GREY16   1: uint16 [n][H][W], host-endian
+ *   NSR_PNG_RGB8     3: u8 [n][H][W][3]
+ *   NSR_PNG_RGBA8    4: u8 [n][H][W][4]; 3: u8 [n][H][W][3], alpha dropped
+ *   nsr_png_size     the bytes of workspace nsr_png_decode needs (the filtered scanlines); nothing is sized by what the files hold.
+ *   nsr_png_decode   workspace 16-byte aligned, workspace_bytes >= the size query's.  status int32 [n] on the device: 0, or bits
+ *                    1 a zlib header, block type or stored-length error, 2 an invalid code set or code, 4 a distance before the
+ *                    start of the output, 8 a stream that ends early or holds more than H (1 + stride) bytes, 16 a filter type
+ *                    above 4; such a frame's pixels are unspecified, the other frames of the batch are not affected.  Every
+ *                    stream fetch stays inside [stream_begin, stream_end), every store inside the frame's own pixels and its own
+ *                    slice of the workspace.  The stream's trailing Adler-32 is neither verified nor required, and
+ *                    distances up to 32768 are taken whatever window the zlib header declares (nsr_png.h).
+ * No atomics on global memory, a fixed order: the same bytes give the same pixels, whatever else is in the batch. */
+enum { NSR_PNG_GREY8 = 0, NSR_PNG_GREY16 = 1, NSR_PNG_RGB8 = 2, NSR_PNG_RGBA8 = 3 };
+typedef struct nsr_png_frame {
+    int64_t stream_begin, stream_end;   /* the zlib stream: bytes [stream_begin, stream_end) of `streams` */
+} nsr_png_frame;
+int nsr_png_size(int32_t n, int32_t H, int32_t W, int32_t kind, int64_t *workspace_bytes);
+int nsr_png_decode(const uint8_t *streams, const nsr_png_frame *descriptors, int32_t n, int32_t H, int32_t W, int32_t kind,
+                   int32_t out_channels, void *workspace, int64_t workspace_bytes, void *out, int32_t *status, void *stream);
+
 /* --- Frame preparation (src/utils/datasets.py:77-113, BaseDataset.__getitem__ after the files are decoded) ---------------------
  * The raw bytes of B frames of one geometry in, the tensors the tracker and the mapper read out: undistortion of the colour image
  * (its own launch, only with distortion coefficients), then ONE launch for the channel order, / 255, the resize of the colour

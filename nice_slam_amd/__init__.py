@@ -12,6 +12,7 @@ path, drop-in behind the reference's Renderer / decoder / get_samples call surfa
     from nice_slam_amd import viewer       # visualizer.py / src/tools/viz.py: Replay, render_mesh, draw_points (headless replay)
     from nice_slam_amd import encode_jpeg, save_jpeg, MjpegWriter    # JPEG files encoded on the GPU, Motion-JPEG video (vis.avi)
     from nice_slam_amd import decode_jpeg, read_jpeg, MjpegReader    # ... and decoded there: Pillow's pixels, bit for bit
+    from nice_slam_amd import decode_png, read_png, probe_png        # PNG depth and colour frames decoded on the GPU
     from nice_slam_amd.slam import NICE_SLAM, load_config        # run.py: the run from its config; poses on the device (Trajectory)
     from nice_slam_amd import evaluate_ate, ate_curve            # src/tools/eval_ate.py: alignment, error statistics, eval_ate_plot.png
 
@@ -37,6 +38,8 @@ from .datasets import FramePreparer, get_dataset  # noqa: F401
 from . import viewer  # noqa: F401
 from . import jpeg  # noqa: F401
 from .jpeg import MjpegReader, MjpegWriter, decode_jpeg, encode_jpeg, probe_jpeg, read_jpeg, read_video, save_jpeg  # noqa: F401
+from . import png  # noqa: F401
+from .png import decode_png, probe_png, read_png  # noqa: F401
 from . import poses  # noqa: F401
 from .poses import Trajectory, get_tensor_from_camera  # noqa: F401
 from . import trajeval  # noqa: F401
@@ -51,5 +54,6 @@ __all__ = ["Renderer", "NICE", "MLP", "MLP_no_xyz", "get_samples", "get_rays", "
            "datasets", "get_dataset", "FramePreparer",
            "viewer",
            "jpeg", "encode_jpeg", "save_jpeg", "MjpegWriter", "decode_jpeg", "probe_jpeg", "read_jpeg", "read_video", "MjpegReader",
+           "png", "decode_png", "probe_png", "read_png",
            "poses", "Trajectory", "get_tensor_from_camera",
            "trajeval", "evaluate_ate", "ate_curve", "plot_trajectories", "save_plot", "AteResult"]

@@ -82,6 +82,10 @@ class NsrJpegDecFrame(C.Structure):
                 ("huff_bits", (C.c_uint8 * 16) * 8), ("huff_vals", (C.c_uint8 * 256) * 8)]
 
 
+class NsrPngFrame(C.Structure):
+    _fields_ = [("stream_begin", C.c_int64), ("stream_end", C.c_int64)]
+
+
 class NsrAdamSpan(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("step", C.c_void_p),
                 ("lr", C.c_float), ("pad_", C.c_int32)]
@@ -241,6 +245,9 @@ SYMBOLS = (
     ("nsr_jpegdec_size", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     ("nsr_jpegdec_decode", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nsr_png_size", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ("nsr_png_decode", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     ("nsr_frame_out_size", C.c_int, [C.POINTER(NsrFrameDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("nsr_frame_workspace_bytes", C.c_int64, [C.POINTER(NsrFrameDesc), C.c_int32]),
     ("nsr_frame_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NsrFrameDesc), C.c_int32, C.c_void_p, C.c_void_p,

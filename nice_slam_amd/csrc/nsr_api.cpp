@@ -26,6 +26,7 @@
 #include "../../nice_slam_amd/csrc/nsr_trajeval.h"
 #include "../../nice_slam_amd/csrc/nsr_jpeg.h"
 #include "../../nice_slam_amd/csrc/nsr_jpegdec.h"
+#include "../../nice_slam_amd/csrc/nsr_png.h"
 
 namespace {
 
@@ -2134,6 +2135,66 @@ int nsr_jpegdec_decode(const uint8_t *files, const nsr_jpegdec_frame *descriptor
     NSR_LAUNCH(nsr::jpegdec_idct_kernel, dim3(nblk(n * P.nblk, T)), dim3(T), 0, stream, P);
     NSR_LAUNCH(nsr::jpegdec_color_kernel, dim3(nblk((long long)n * H * W, T)), dim3(T), 0, stream, P);
     return finish("nsr_jpegdec_decode");
+}
+
+}  // extern "C"
+
+// ---- PNG decoding (include/nsr.h, "PNG decoding") ----
+namespace {
+
+// nullptr: the sizes are valid and P's geometry is filled; else what is wrong with them
+const char *png_geometry(int32_t n, int32_t H, int32_t W, int32_t kind, nsr::PngParams &P) {
+    if (n < 0 || n > 65535) return "the batch size must be in [0, 65535]";
+    if (H < 1 || W < 1 || H > 32768 || W > 32768) return "image sizes must be in [1, 32768]";
+    if (kind < NSR_PNG_GREY8 || kind > NSR_PNG_RGBA8) return "kind must be 0 (grey 8), 1 (grey 16), 2 (RGB 8) or 3 (RGBA 8)";
+    P.n = n; P.H = H; P.W = W; P.kind = kind;
+    P.bpp = kind == NSR_PNG_GREY8 ? 1 : kind == NSR_PNG_GREY16 ? 2 : kind == NSR_PNG_RGB8 ? 3 : 4;
+    P.slice = pad16((long long)H * (1 + (long long)W * P.bpp));
+    if (n * P.slice > (1ll << 40)) return "too many bytes for one call";
+    return nullptr;
+}
+
+void png_carve(nsr::PngParams &P, Carve &c) { P.filtered = c.take<unsigned char>(P.n * P.slice); }
+
+}  // namespace
+
+extern "C" {
+
+int nsr_png_size(int32_t n, int32_t H, int32_t W, int32_t kind, int64_t *workspace_bytes) {
+    nsr::PngParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (const char *e = png_geometry(n, H, W, kind, P)) return fail(std::string("nsr_png_size: ") + e);
+    if (!workspace_bytes) return fail("nsr_png_size: null pointer");
+    *workspace_bytes = carve(png_carve, P);
+    return 0;
+}
+
+int nsr_png_decode(const uint8_t *streams, const nsr_png_frame *descriptors, int32_t n, int32_t H, int32_t W, int32_t kind,
+                   int32_t out_channels, void *workspace, int64_t workspace_bytes, void *out, int32_t *status, void *stream) {
+    nsr::PngParams P;
+    std::memset(&P, 0, sizeof(P));
+    if (const char *e = png_geometry(n, H, W, kind, P)) return fail(std::string("nsr_png_decode: ") + e);
+    const bool fits = kind == NSR_PNG_GREY8 ? out_channels == 1 || out_channels == 3 : kind == NSR_PNG_GREY16 ? out_channels == 1
+                    : kind == NSR_PNG_RGB8 ? out_channels == 3 : out_channels == 3 || out_channels == 4;
+    if (!fits) return fail("nsr_png_decode: out_channels must be 1 or 3 for grey 8, 1 for grey 16, 3 for RGB 8, 3 or 4 for RGBA 8");
+    if (n == 0) return 0;
+    if (!streams || !descriptors || !workspace || !out || !status) return fail("nsr_png_decode: null pointer");
+    if (workspace_bytes < carve(png_carve, P, workspace)) return fail("nsr_png_decode: workspace smaller than nsr_png_size reports");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail("nsr_png_decode: the workspace must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(descriptors) & 7) return fail("nsr_png_decode: the descriptors must be 8-byte aligned");
+    if (kind == NSR_PNG_GREY16 && (reinterpret_cast<uintptr_t>(out) & 1)) return fail("nsr_png_decode: a 16-bit out must be 2-byte aligned");
+    P.streams = streams;
+    P.desc = descriptors;
+    P.out = out;
+    P.status = status;
+    P.out_channels = out_channels;
+    const dim3 grid(n), block(nsr::kPngThreads);
+    if (int rc = launch_kernel(nsr::png_inflate_kernel, grid, block, nsr::kPngInflateLds, "nsr_png_decode", stream, P)) return rc;
+    if (P.bpp == 1) NSR_LAUNCH(nsr::png_unfilter_kernel<1>, grid, block, 0, stream, P);
+    else if (P.bpp == 2) NSR_LAUNCH(nsr::png_unfilter_kernel<2>, grid, block, 0, stream, P);
+    else if (P.bpp == 3) NSR_LAUNCH(nsr::png_unfilter_kernel<3>, grid, block, 0, stream, P);
+    else NSR_LAUNCH(nsr::png_unfilter_kernel<4>, grid, block, 0, stream, P);
+    return finish("nsr_png_decode");
 }
 
 }  // extern "C"

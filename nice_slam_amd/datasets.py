@@ -11,7 +11,8 @@ the per-frame preparation on the GPU.
     color, depth = prep.prepare(color_u8, depth_u16, bgr=True)                 # e.g. what cv2.imread returned
 
 The host decodes the files (PIL) and uploads the raw bytes -- u8 colour, u16 (or fp32) depth; with ``decoder="gpu"`` the colour
-files' own bytes are uploaded and decoded on the device (nice_slam_amd.jpeg: the same pixels), depth stays on the host.  Everything
+files' own bytes are uploaded and decoded on the device (nice_slam_amd.jpeg: the same pixels), depth stays on the host; with
+``png_decoder="gpu"`` so are the compressed bytes of every PNG file, depth and colour (nice_slam_amd.png).  Everything
 ``BaseDataset.__getitem__`` (datasets.py:77-113) does after that runs in libnsr.so (include/nsr.h, "Frame preparation"; the
 arithmetic is written out in csrc/nsr_frame.h): the undistortion of the colour image, BGR -> RGB, / 255, the resize to the
 depth image's size, the depth scale, the ``crop_size`` resize, ``crop_edge`` and the cast to fp32.
@@ -174,13 +175,19 @@ class BaseDataset:
     """``ds[i]`` -> (i, colour [H, W, 3], depth [H, W], c2w [4, 4]), fp32 on the device.  Subclasses fill ``color_paths``,
     ``depth_paths`` and ``poses`` (fp32 4 x 4 tensors in the reference's convention, translation NOT yet scaled)."""
 
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine: Optional[Engine] = None, decoder: Optional[str] = None):
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine: Optional[Engine] = None, decoder: Optional[str] = None,
+                 png_decoder: Optional[str] = None):
         self.name = cfg["dataset"]
         decoder = (cfg.get("data") or {}).get("decoder", "pil") if decoder is None else decoder
         if decoder not in ("pil", "gpu"):
             raise ValueError(f"decoder must be 'pil' or 'gpu' (got {decoder!r})")
+        png_decoder = (cfg.get("data") or {}).get("png_decoder", "pil") if png_decoder is None else png_decoder
+        if png_decoder not in ("pil", "gpu"):
+            raise ValueError(f"png_decoder must be 'pil' or 'gpu' (got {png_decoder!r})")
         self.decoder = decoder
+        self.png_decoder = png_decoder
         self.decode_fallbacks = 0                  # frames of decoder="gpu" that went through PIL after all
+        self.png_fallbacks = 0                     # PNG files of png_decoder="gpu" that went through PIL after all
         self.prep = FramePreparer(cfg, engine=engine, scale=scale, device=device)
         self.device = self.prep.E.device
         self.scale = self.prep.scale
@@ -226,41 +233,102 @@ class BaseDataset:
             raise ValueError(f"{depth_path}: depth images are .png or .exr")
         return depth
 
+    def _decode_png_files(self, data, ks, mode, kinds):
+        """{k: the device pixels of data[k]} for the k in ``ks`` whose file the PNG decoder takes, of one of ``kinds``, and whose
+        stream the device found whole; the files of one size and kind go in one call"""
+        from . import png
+        groups, out, parsed = {}, {}, {}
+        for k in ks:
+            try:
+                p = parsed[k] = png.parse_png(data[k])             # the one chunk walk and CRC pass of the file
+            except png.PngRefused:
+                continue
+            if p["kind"] in kinds:
+                groups.setdefault((p["height"], p["width"], p["kind"]), []).append(k)
+        for group in groups.values():
+            frames, status = png.decode_png_status([parsed[k] for k in group], mode=mode, engine=self.prep.E)
+            for j, k in enumerate(group):
+                if status[j] == 0:
+                    out[k] = frames[j]
+        return out
+
+    def read_depth_gpu(self, indices: Sequence[int]) -> torch.Tensor:
+        """The frames' depth [B, Hd, Wd] on the device, u16 as its bytes in int16 (``FramePreparer.prepare`` takes them as they
+        are): the compressed bytes of the .png files are uploaded and decoded there (nice_slam_amd.png), 8-bit grey widened as
+        ``read_depth`` does.  A file the decoder does not take (``png.probe_png`` says why) or whose stream the device reports
+        damaged goes through ``read_depth`` and is counted in ``png_fallbacks``; an .exr file is ``read_depth``'s as before."""
+        data = {}
+        for k, i in enumerate(indices):
+            if ".png" in self.depth_paths[i]:
+                with open(self.depth_paths[i], "rb") as fh:
+                    data[k] = fh.read()
+        done = self._decode_png_files(data, list(data), None, ("grey8", "grey16"))       # (the kinds read_depth accepts)
+        out = []
+        for k, i in enumerate(indices):
+            if k in done:
+                t = done[k]
+                out.append(t.view(torch.int16) if t.dtype != torch.uint8 else t.to(torch.int16))
+                continue
+            if k in data:
+                self.png_fallbacks += 1
+            d = self.read_depth(i)
+            out.append(torch.from_numpy(d.view(np.int16) if d.dtype == np.uint16 else d).to(self.device))
+        return torch.stack(out)
+
     def read_color_gpu(self, indices: Sequence[int]) -> torch.Tensor:
         """u8 [B, Hc, Wc, 3] RGB on the device of the frames' colour files, decoded there (nice_slam_amd.jpeg): the files' bytes are
         uploaded, not their pixels.  A file the decoder does not take (not a JPEG, progressive, ...; ``jpeg.probe_jpeg`` says why)
         or whose stream the device reports damaged goes through PIL as in ``read_raw`` -- the pixels are the same either way,
-        and PIL's error is the error of a file nobody can read -- and is counted in ``decode_fallbacks``."""
+        and PIL's error is the error of a file nobody can read -- and is counted in ``decode_fallbacks``.  With
+        ``png_decoder="gpu"`` a file that starts with the PNG signature goes to nice_slam_amd.png instead, whatever ``decoder``
+        is, and is counted in ``png_fallbacks`` when it comes back from there; with ``decoder="pil"`` every other file is PIL's."""
         from PIL import Image
 
-        from . import jpeg
+        from . import jpeg, png
         data = []
         for i in indices:
             with open(self.color_paths[i], "rb") as fh:
                 data.append(fh.read())
-        info = [jpeg.probe_jpeg(d) for d in data]
         out = [None] * len(data)
-        groups = {}                                # frames of one size and sampling decode in one call
-        for k, p in enumerate(info):
-            if p["supported"]:
-                groups.setdefault((p["height"], p["width"], p["sampling"]), []).append(k)
-        for ks in groups.values():
-            frames, status = jpeg.decode_jpeg_status([data[k] for k in ks], engine=self.prep.E)
-            for j, k in enumerate(ks):
-                if status[j] == 0:
-                    out[k] = frames[j]
-        for k, i in enumerate(indices):
+
+        def through_pil(k):
+            with Image.open(self.color_paths[indices[k]]) as im:
+                out[k] = torch.from_numpy(np.array(im.convert("RGB"), dtype=np.uint8)).to(self.device)
+
+        pngs = [k for k, d in enumerate(data) if self.png_decoder == "gpu" and d[:8] == png.SIGNATURE]
+        for k, frame in self._decode_png_files(data, pngs, "RGB", ("grey8", "rgb8", "rgba8")).items():
+            out[k] = frame
+        for k in pngs:
             if out[k] is None:
-                self.decode_fallbacks += 1
-                with Image.open(self.color_paths[i]) as im:
-                    out[k] = torch.from_numpy(np.array(im.convert("RGB"), dtype=np.uint8)).to(self.device)
+                self.png_fallbacks += 1
+                through_pil(k)
+        rest = [k for k in range(len(data)) if out[k] is None]
+        if self.decoder == "gpu":
+            info = {k: jpeg.probe_jpeg(data[k]) for k in rest}
+            groups = {}                            # frames of one size and sampling decode in one call
+            for k, p in info.items():
+                if p["supported"]:
+                    groups.setdefault((p["height"], p["width"], p["sampling"]), []).append(k)
+            for ks in groups.values():
+                frames, status = jpeg.decode_jpeg_status([data[k] for k in ks], engine=self.prep.E)
+                for j, k in enumerate(ks):
+                    if status[j] == 0:
+                        out[k] = frames[j]
+        for k in rest:
+            if out[k] is None:
+                if self.decoder == "gpu":
+                    self.decode_fallbacks += 1
+                through_pil(k)
         return torch.stack(out)
+
+    def _depth_batch(self, indices):
+        return self.read_depth_gpu(indices) if self.png_decoder == "gpu" else np.stack([self.read_depth(i) for i in indices])
 
     def load_batch(self, indices: Sequence[int]):
         """(indices, colour [B, H, W, 3], depth [B, H, W], c2w [B, 4, 4]) of several frames, prepared by one launch"""
         indices = [int(i) for i in indices]
-        if self.decoder == "gpu":
-            color, depth = self.prep.prepare(self.read_color_gpu(indices), np.stack([self.read_depth(i) for i in indices]), bgr=False)
+        if self.decoder == "gpu" or self.png_decoder == "gpu":
+            color, depth = self.prep.prepare(self.read_color_gpu(indices), self._depth_batch(indices), bgr=False)
             return indices, color, depth, torch.stack([self.poses[i] for i in indices]).to(self.device)
         raw = [self.read_raw(i) for i in indices]
         color, depth = self.prep.prepare(np.stack([r[0] for r in raw]), np.stack([r[1] for r in raw]), bgr=False)
@@ -270,7 +338,9 @@ class BaseDataset:
         index = int(index)
         if not 0 <= index < self.n_img:
             raise IndexError(index)
-        if self.decoder == "gpu":
+        if self.png_decoder == "gpu":
+            color, depth = self.prep.prepare(self.read_color_gpu([index])[0], self.read_depth_gpu([index])[0], bgr=False)
+        elif self.decoder == "gpu":
             color, depth = self.prep.prepare(self.read_color_gpu([index])[0], self.read_depth(index), bgr=False)
         else:
             color, depth = self.prep.prepare(*self.read_raw(index), bgr=False)
@@ -278,8 +348,8 @@ class BaseDataset:
 
 
 class Replica(BaseDataset):
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None):
-        super().__init__(cfg, input_folder, scale, device, engine, decoder)
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None, png_decoder=None):
+        super().__init__(cfg, input_folder, scale, device, engine, decoder, png_decoder)
         self.color_paths = sorted(glob.glob(f"{self.input_folder}/results/frame*.jpg"))
         self.depth_paths = sorted(glob.glob(f"{self.input_folder}/results/depth*.png"))
         with open(f"{self.input_folder}/traj.txt", "r") as f:
@@ -290,8 +360,8 @@ class Replica(BaseDataset):
 
 
 class Azure(BaseDataset):
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None):
-        super().__init__(cfg, input_folder, scale, device, engine, decoder)
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None, png_decoder=None):
+        super().__init__(cfg, input_folder, scale, device, engine, decoder, png_decoder)
         self.color_paths = sorted(glob.glob(os.path.join(self.input_folder, "color", "*.jpg")))
         self.depth_paths = sorted(glob.glob(os.path.join(self.input_folder, "depth", "*.png")))
         path = os.path.join(self.input_folder, "scene", "trajectory.log")
@@ -306,8 +376,8 @@ class Azure(BaseDataset):
 
 
 class ScanNet(BaseDataset):
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None):
-        super().__init__(cfg, input_folder, scale, device, engine, decoder)
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None, png_decoder=None):
+        super().__init__(cfg, input_folder, scale, device, engine, decoder, png_decoder)
         self.input_folder = os.path.join(self.input_folder, "frames")
 
         def number(p):
@@ -323,8 +393,8 @@ class ScanNet(BaseDataset):
 
 
 class CoFusion(BaseDataset):
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None):
-        super().__init__(cfg, input_folder, scale, device, engine, decoder)
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None, png_decoder=None):
+        super().__init__(cfg, input_folder, scale, device, engine, decoder, png_decoder)
         self.color_paths = sorted(glob.glob(os.path.join(self.input_folder, "colour", "*.png")))
         self.depth_paths = sorted(glob.glob(os.path.join(self.input_folder, "depth_noise", "*.exr")))
         self.poses = [torch.eye(4) for _ in self.color_paths]      # the reference's proxy: the frames could not be aligned
@@ -332,8 +402,8 @@ class CoFusion(BaseDataset):
 
 
 class TUM_RGBD(BaseDataset):
-    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None):
-        super().__init__(cfg, input_folder, scale, device, engine, decoder)
+    def __init__(self, cfg, input_folder=None, scale=None, device="cuda:0", engine=None, decoder=None, png_decoder=None):
+        super().__init__(cfg, input_folder, scale, device, engine, decoder, png_decoder)
         self.color_paths, self.depth_paths, self.poses = self.loadtum(self.input_folder, frame_rate=32)
         self._finish()
 
@@ -410,9 +480,12 @@ class TUM_RGBD(BaseDataset):
 dataset_dict = {"replica": Replica, "scannet": ScanNet, "cofusion": CoFusion, "azure": Azure, "tumrgbd": TUM_RGBD}
 
 
-def get_dataset(cfg, input_folder=None, scale=None, device="cuda:0", engine: Optional[Engine] = None, decoder: Optional[str] = None) -> BaseDataset:
+def get_dataset(cfg, input_folder=None, scale=None, device="cuda:0", engine: Optional[Engine] = None, decoder: Optional[str] = None,
+                png_decoder: Optional[str] = None) -> BaseDataset:
     """The reader of ``cfg['dataset']`` (datasets.py:47-48).  ``input_folder``: instead of ``cfg['data']['input_folder']``
     (the reference's ``args.input_folder``); ``scale``: instead of ``cfg['scale']``.  ``decoder``: "pil" (the default; also
     ``cfg['data']['decoder']``) decodes the colour files on the host, "gpu" on the device (``BaseDataset.read_color_gpu``); the
-    tensors are the same."""
-    return dataset_dict[cfg["dataset"]](cfg, input_folder, scale, device, engine, decoder)
+    tensors are the same.  ``png_decoder``: "pil" (the default; also ``cfg['data']['png_decoder']``) or "gpu", a switch of its own
+    for the PNG files -- every .png depth image and every colour file that is a PNG (``BaseDataset.read_depth_gpu``,
+    ``read_color_gpu``); again the same tensors."""
+    return dataset_dict[cfg["dataset"]](cfg, input_folder, scale, device, engine, decoder, png_decoder)
